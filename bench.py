@@ -17,7 +17,17 @@ forwards, two-group SGD + PolyLR):
 
   python bench.py --arch deeplabv3plus_resnet101 --batch 2 --pgd_steps 3 --steps 10 --warmup 4
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with extra objects:
+Prints ONE JSON line on rank 0 (contract in the task statement).  A plain run only sets up, warms up, times the --steps steps
+and prints it (`value`, `ms_per_step` ...; `roofline` and `cpu_baseline` null).
+
+  --dump-outputs DIR   after the timed steps, what the last one computed as DIR/<name>.npy (float32; float64 stays float64): every
+                       tensor the trainer's step returns, `params` (the model's parameters after its update, concatenated in
+                       model.parameters() order) and `buffers` (its floating-point buffers: BatchNorm running statistics ...).  An
+                       array of more than DUMP_CAP elements is flattened and keeps a fixed, seeded sample of them.  Inputs and
+                       initial weights are seeded: the same arguments give the same inputs in every run, so two builds can be
+                       compared output for output.
+
+  --full               everything else, after the timed region (not in `value`), each skipped by its --no_* option:
   roofline     — the dominant hand-written kernel by time: achieved algorithmic FLOP/s (MFMA-bound) or GB/s (HBM-bound),
                  timed per launch with HIP events on the launch stream in a separate instrumented pass (not in `value`);
                  `traffic` = HBM bytes per launch from the newest committed rocprofv3 --pmc summary that names the kernel,
@@ -25,7 +35,11 @@ Prints ONE JSON line on rank 0 (contract in the task statement) with extra objec
   conv_mfma    — EXECUTED convolution FLOPs per step (summed over the launches of the instrumented pass) / step time;
   hbm_kernels  — the A-FAN element-wise kernels (PGD step, mix_feature, lerp, ...) as fractions of the 8 TB/s HBM peak;
   cpu_baseline — the CPU oracle (oracle/afan_oracle.py, bit-identical to the reference's Python on CPU) timed on this
-                 box's host cores on a bounded sample of the same workload (rank 0, N=1 only).
+                 box's host cores on a bounded sample of the same workload (rank 0, N=1 only);
+  kernels      — every hand-written kernel's launches, time and rate per step (the instrumented pass behind `roofline`);
+  literal_schedule, dp_schedule — the reference's schedule as written / the data-parallel program on one GPU, each a fresh
+                 model timed after the headline run (ResNet workloads, N=1 only);
+  ddp_diag     — N > 1: three more steps with every gradient exchange bracketed by events.
 """
 import argparse
 import glob
@@ -74,6 +88,9 @@ def parse():
     ap.add_argument("--no_share_head", action="store_true", help="run the head twice per step like the reference's text (A/B)")
     ap.add_argument("--dual_bn", action="store_true", help="A/B: auxiliary BatchNorm set for adversarial features (an option the "
                     "reference does not have; the headline line is measured without it)")
+    ap.add_argument("--full", action="store_true", help="after the timed steps, also the instrumented pass (roofline, kernels, conv_mfma, "
+                    "hbm_kernels), the literal and data-parallel schedules, the CPU baseline and (N > 1) ddp_diag")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed as DIR/<name>.npy")
     ap.add_argument("--no_cpu_baseline", action="store_true")
     ap.add_argument("--no_roofline", action="store_true")
     ap.add_argument("--no_literal", action="store_true", help="skip the after-the-fact run of the reference's literal schedule "
@@ -179,6 +196,43 @@ def synth_seg(batch, side, g):
     y = torch.randint(0, 21, (batch, side, side), generator=g)
     y[torch.rand(batch, side, side, generator=g) < 0.05] = 255
     return x, y
+
+
+DUMP_CAP = 1 << 20                 # elements kept per dumped array (4 MiB in float32): at most 64 MB over the ~10 arrays of a step
+DUMP_LIMIT = 64_000_000
+
+
+def step_outputs(r, model):
+    """What a caller of the timed step receives: the tensors the step returns and the model it updated."""
+    import torch
+    arrays = {k: v for k, v in r.items() if torch.is_tensor(v)}
+    arrays["params"] = torch.cat([p.detach().reshape(-1).float() for p in model.parameters()])
+    bufs = [b.detach().reshape(-1).float() for b in model.buffers() if b.is_floating_point()]
+    if bufs:
+        arrays["buffers"] = torch.cat(bufs)
+    return arrays
+
+
+def dump_outputs(out_dir, arrays):
+    """arrays (name -> tensor) as out_dir/<name>.npy: float64 stays float64, other floating dtypes become float32, integers float64
+    (exact).  More than DUMP_CAP elements: flattened, the elements at DUMP_CAP positions drawn once from a fixed seed (sorted),
+    so that the sample depends on the array's size only.  Returns the bytes written."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    host = {}
+    for name, t in arrays.items():
+        t = t.detach()
+        dt = torch.float32 if t.is_floating_point() and t.dtype != torch.float64 else torch.float64
+        if t.numel() > DUMP_CAP:
+            pos = np.sort(np.random.default_rng(0).choice(t.numel(), DUMP_CAP, replace=False))
+            t = t.reshape(-1)[torch.from_numpy(pos).to(t.device)]
+        host[name] = t.to(dt).cpu().numpy()
+    total = sum(a.nbytes for a in host.values())
+    assert total <= DUMP_LIMIT, f"--dump-outputs: {total} bytes over the {DUMP_LIMIT} limit"
+    for name, a in host.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return total
 
 
 def _csrc_files():
@@ -518,12 +572,16 @@ def main():
     # the convolution + BatchNorm launches meet at a grid-wide barrier whose spin is bounded: a spin that gave up (workgroups of a
     # launch not co-resident) invalidates everything after it — fail loudly rather than print a number
     assert not pkg.ops.grid_barrier_error(dev), "a grid barrier of the in-launch BatchNorm gave up (another process's kernels on this GPU?)"
+    # before anything below steps the model again (graph-owned outputs stay valid until the next step)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, step_outputs(r, model))
 
-    # ---- instrumented pass (not part of `value`): per-launch HIP-event timing of the hand-written kernels ----
+    # ---- --full: instrumented pass (not part of `value`): per-launch HIP-event timing of the hand-written kernels ----
     roof, kernels, conv_exec, hbm = None, None, None, None
     graphed = trainer._graph is not None or (det and bool(pkg.det_model._StageGraphs.cache))
     NP = 2
-    if not args.no_roofline:
+    instrument = args.full and not args.no_roofline
+    if instrument:
         # per-launch event timing needs eager launches: the same step body, un-captured.  EVERY rank runs it (the step
         # contains the gradient all-reduce); only rank 0 records.
         if rank == 0:
@@ -531,7 +589,7 @@ def main():
         for i in range(NP):
             one_eager(i)
         torch.cuda.synchronize()
-    if rank == 0 and not args.no_roofline:
+    if rank == 0 and instrument:
         prof = pkg.ops.profile_collect()
         pkg.ops.profile_enable(False)
         # every instrumented duration = kernel + one empty (event, event) bracket: measure that bracket and take it out
@@ -608,10 +666,10 @@ def main():
                 hbm[k] = {"achieved_GBps": round(gbs, 1), "frac_of_8TBps": round(gbs / HBM_PEAK_GBS, 4),
                           "algo_bytes_per_launch": round(prof[k]["bytes"] / prof[k]["launches"]),
                           "avg_us": round(prof[k]["ms"] * 1e3 / prof[k]["launches"], 2)}
-    # ---- N > 1: three more steps with every exchange bracketed by events (not part of `value`) ----
+    # ---- --full, N > 1: three more steps with every exchange bracketed by events (not part of `value`) ----
     ddp_diag = None
     red = getattr(trainer, "reducer", None)
-    if world > 1 and red is not None:
+    if args.full and world > 1 and red is not None:
         red.diag = True
         steps_ = []
         for i in range(3):
@@ -630,15 +688,15 @@ def main():
         dist.barrier()
 
     literal = None
-    if rank == 0 and world == 1 and not (seg or det) and not args.no_literal and trainer._fold_ok(xs[0]):
+    if args.full and rank == 0 and world == 1 and not (seg or det) and not args.no_literal and trainer._fold_ok(xs[0]):
         literal = literal_schedule(pkg, torch, nn, args, dev, idx, xs, ys, loss)
     # ---- the data-parallel PROGRAM on this one GPU (train_step.NullReducer): what a rank of an N > 1 job runs, minus the exchange
     dp_sched = None
-    if rank == 0 and world == 1 and not (seg or det) and not args.no_dp_schedule and trainer._fold_ok(xs[0]):
+    if args.full and rank == 0 and world == 1 and not (seg or det) and not args.no_dp_schedule and trainer._fold_ok(xs[0]):
         dp_sched = dp_schedule(pkg, torch, nn, args, dev, idx, xs, ys, loss)
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         pkg.host.restore(placement)
         cpu = (cpu_baseline_seg(args.arch, args.batch, args.pgd_steps, side, args.cpu_steps) if seg
                else cpu_baseline(args.arch, args.batch, args.pgd_steps, idx, args.cpu_steps))

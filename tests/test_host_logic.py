@@ -189,6 +189,27 @@ def test_bench_device_identity_is_16_bytes():
     assert len(a) == len(b) == 16 and a != b
 
 
+def test_bench_dump_outputs_are_float_arrays_with_a_fixed_sample(tmp_path):
+    """bench.py --dump-outputs: float32 (float64 kept, integers exact in float64), small arrays whole and in their shape, a larger
+    one flattened to DUMP_CAP elements at sorted, distinct positions that are the same on every call; the total within the limit."""
+    import importlib
+    import sys
+    sys.path.insert(0, ROOT)
+    bench = importlib.import_module("bench")
+    arrays = {"loss": torch.tensor(1.5, dtype=torch.bfloat16), "l2": torch.rand(4, dtype=torch.float64), "n": torch.arange(3),
+              "big": torch.arange(bench.DUMP_CAP + 5, dtype=torch.float32)}
+    written = bench.dump_outputs(str(tmp_path / "a"), arrays)
+    bench.dump_outputs(str(tmp_path / "b"), arrays)
+    got = {k: np.load(tmp_path / "a" / f"{k}.npy") for k in arrays}
+    assert got["loss"].dtype == np.float32 and got["loss"].shape == () and got["loss"] == 1.5
+    assert got["l2"].dtype == np.float64 and np.array_equal(got["l2"], arrays["l2"].numpy())
+    assert got["n"].dtype == np.float64 and got["n"].tolist() == [0, 1, 2]
+    s = got["big"]
+    assert s.dtype == np.float32 and s.shape == (bench.DUMP_CAP,) and np.all(np.diff(s) > 0) and s[-1] < bench.DUMP_CAP + 5
+    assert np.array_equal(s, np.load(tmp_path / "b" / "big.npy"))
+    assert written == sum(a.nbytes for a in got.values()) <= bench.DUMP_LIMIT
+
+
 def test_tiled_convolution_kernels_use_no_scratch():
     """Every instantiation of the tiled convolution compiles without a private segment (tools/check_isa.py's rule, here for the
     one source whose 768- and 1 024-thread variants sit exactly at their register caps: in round 4 an epilogue change pushed

@@ -11,5 +11,5 @@ mkdir -p gpurun_out
 WORLD=${WORLD:-2}
 LOG=gpurun_out/${LOG:-ddp${WORLD}_one_gpu}.log
 export AFAN_BENCH_ONE_DEVICE=1 AFAN_DIST_BACKEND=gloo
-python bench.py --gpus $WORLD --steps 6 --warmup 5 --batch 128 --no_cpu_baseline "$@" > $LOG 2>&1
+python bench.py --gpus $WORLD --full --steps 6 --warmup 5 --batch 128 --no_cpu_baseline "$@" > $LOG 2>&1
 echo "rc=$?"; grep "^{" $LOG | cut -c1-900; grep -i "error\|Traceback" -A8 $LOG | head -30

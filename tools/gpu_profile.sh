@@ -4,7 +4,7 @@
 #   gpurun_out/TAG_kernel_stats.csv      rocprofv3 --kernel-trace --stats of the same command (graph replay)
 #   gpurun_out/TAG_pmc_hbm_traffic.json  FETCH_SIZE / WRITE_SIZE per kernel (two separate --pmc passes, eager), unless NOPMC=1
 TAG=${1:-x}; shift
-ARGS="$@"
+ARGS="--full $@"
 mkdir -p gpurun_out
 export TMPDIR=/tmp
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}

@@ -29,7 +29,7 @@ case "$1" in
              bash tools/gpu_pmc_bench.sh r18 --no_literal --no_dp_schedule > $O/pmc_hbm.log 2>&1; cp gpurun_out/pmcb_r18/summary.json $O/r18_pmc_hbm_traffic.json
              continue
            fi
-           python3 bench.py ${BARGS[$N]} > $O/${N}_bench.json 2> $O/${N}_bench.err
+           python3 bench.py --full ${BARGS[$N]} > $O/${N}_bench.json 2> $O/${N}_bench.err
            A=$(echo "${BARGS[$N]}" | sed 's/--steps [0-9]*//; s/--warmup [0-9]*//; s/--cpu_steps [0-9]*//; s/--no_cpu_baseline//; s/--no_literal//; s/--no_dp_schedule//')
            rm -rf /tmp/prof_$N
            (cd /tmp && rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_$N -- python3 $R/bench.py --steps 10 --warmup 4 --no_cpu_baseline --no_roofline --no_literal --no_dp_schedule $A > $O/${N}_prof.log 2>&1)
