@@ -154,6 +154,8 @@ SIGNATURES = {
     "afan_profile_collect": (_i, [C.c_char_p, C.POINTER(_l), C.POINTER(C.c_double), C.POINTER(C.c_double),
                                   C.POINTER(C.c_double), _i]),
     "afan_profile_event_overhead": (_i, [_i, C.POINTER(_f), _p]),
+    "afan_conv_trace": (_i, [_i]),
+    "afan_conv_trace_read": (_i, [C.POINTER(_l), C.c_char_p, _i]),
 }
 
 _lib = None

@@ -127,6 +127,22 @@ struct Scope {
 // same, for MFMA-bound kernels: also records the launch's algorithmic FLOPs
 #define AFAN_PROF_FLOPS(name, bytes, flops, st) afan::prof::Scope afan_prof_scope__(name, (double)(bytes), st, (double)(flops))
 
+// ---- optional host-side record of the convolution launches (afan_trace.hip) ----
+// Off by default (one relaxed load per entry point and launch).  An entry point names the layer problem(s) it serves
+// (AFAN_TRACE_PROBLEM: slot 0 starts a new call, slots 1..3 add problems of the same launch: ASPP's branches, the projection of a
+// fused pair, a multi weight gradient); the launch site then names the instantiation it launched (AFAN_TRACE_LAUNCH, printf-style)
+// and one record per named problem is kept.  Host only, at enqueue time: a captured graph's launches are recorded once.
+namespace afan { namespace trace {
+enum { FWD = 0, DGRAD = 1, WGRAD = 2 };
+extern int g_on;
+inline bool on() { return __atomic_load_n(&g_on, __ATOMIC_RELAXED) != 0; }
+void problem(int slot, int op, int64_t n, int64_t hi, int64_t wi, int64_t ci, int64_t co, int k, int stride, int dilation);
+int op();                                    // the current call's op (slot 0), -1 when none
+void launch(const char* fmt, ...) __attribute__((format(printf, 1, 2)));
+} }
+#define AFAN_TRACE_PROBLEM(...) do { if (afan::trace::on()) afan::trace::problem(__VA_ARGS__); } while (0)
+#define AFAN_TRACE_LAUNCH(...) do { if (afan::trace::on()) afan::trace::launch(__VA_ARGS__); } while (0)
+
 #define AFAN_LAUNCH_CHECK()                     \
     do {                                        \
         ++afan::prof::g_launches;               \

@@ -1438,6 +1438,7 @@ int launch_gs(const ConvP& p_in, hipStream_t st, bool dgrad) {
     if (dgrad) conv_igemm_dgrad_kernel<BM, BN, PF, WM, WN, PW, FBT, HL, GS, BF><<<grid, THREADS, lds, st>>>(p);
     else conv_igemm_fwd_kernel<BM, BN, PF, WM, WN, PW, FBT, HL, GS, BF><<<grid, THREADS, lds, st>>>(p);
     AFAN_LAUNCH_CHECK();
+    AFAN_TRACE_LAUNCH("igemm_%s<%d,%d,%d,%d,%d,%d,%d,%d,gs%d,bf%d>", dgrad ? "dgrad" : "fwd", BM, BN, PF, WM, WN, PW, FBT, HL, (int)GS, (int)BF);
     return AFAN_OK;
 }
 
@@ -1652,6 +1653,8 @@ static int dgrad_impl(const void* dy, const void* dy_sc, const void* wt, void* d
                       const ConvP* bnf = nullptr) {
     int e = check_dims(n, hi, wi, co, ci, k, stride, dilation);   // reduction runs over co here
     if (e) return e;
+    AFAN_TRACE_PROBLEM(0, afan::trace::DGRAD, n, hi, wi, ci, co, k, stride, dilation);
+    if (dy_sc) AFAN_TRACE_PROBLEM(1, afan::trace::DGRAD, n, hi, wi, ci, co, 1, 2, 1);
     if (!dy || !wt || !dx) return AFAN_ENULL;
     if (!aligned(dy, 16) || !aligned(wt, 16) || !aligned(dx, 16)) return AFAN_EALIGN;
     const int pad = k / 2;
@@ -1796,6 +1799,7 @@ int64_t afan_conv_fwd_tiles(int64_t n, int64_t hi, int64_t wi, int64_t ci, int64
 int afan_conv_fwd_nhwc_bf16(const void* x, const void* w, void* y, int64_t n, int64_t hi, int64_t wi, int64_t ci,
                             int64_t co, int k, int stride, int dilation, float* stats_partials, const float* stats_shift,
                             double* stats_acc, int groups, afan_stream_t stream) {
+    AFAN_TRACE_PROBLEM(0, afan::trace::FWD, n, hi, wi, ci, co, k, stride, dilation);
     if (ci == 3) {                                              // the image stem has its own kernel
         if (!afan_stem::eligible(n, hi, wi, ci, co, k, stride) || stats_partials || groups > 1 || dilation != 1) return AFAN_ESHAPE;
         if (!x || !w || !y) return AFAN_ENULL;
@@ -1851,6 +1855,7 @@ int afan_conv_fwd_affine_nhwc_bf16(const void* x, const void* w, void* y, int64_
                                    int k, int stride, const float* coefs, const void* residual, int relu, afan_stream_t stream) {
     int e = check_dims(n, hi, wi, ci, co, k, stride, 1);
     if (e) return e;
+    AFAN_TRACE_PROBLEM(0, afan::trace::FWD, n, hi, wi, ci, co, k, stride, 1);
     if (!x || !w || !y || !coefs) return AFAN_ENULL;
     if (!aligned(x, 16) || !aligned(w, 16) || !aligned(y, 16) || (residual && !aligned(residual, 16))) return AFAN_EALIGN;
     if (ci % 8 != 0 || co % 8 != 0 || ci < 40 || co < 40) return AFAN_ESHAPE;
@@ -1897,6 +1902,7 @@ static int fwd_multi_impl(const void* x, const void* const* w, void* const* y, i
     for (int b = 0; b < nb; ++b) {
         int e = check_dims(n, hi, wi, ci, co, ksize[b], stride, dilation[b]);
         if (e) return e;
+        AFAN_TRACE_PROBLEM(b, afan::trace::FWD, n, hi, wi, ci, co, ksize[b], stride, dilation[b]);
         if (!w[b] || !y[b]) return AFAN_ENULL;
         if (!aligned(w[b], 16) || !aligned(y[b], 16)) return AFAN_EALIGN;
         if (stats_acc && (!stats_acc[b] || !aligned(stats_acc[b], 16))) return stats_acc[b] ? AFAN_EALIGN : AFAN_ENULL;
@@ -2088,6 +2094,7 @@ int afan_conv_fwd_bn_nhwc_bf16(const void* x, const void* w, void* y_raw, void* 
     const int k = ksize, stride = 1, pad = k / 2;
     int e = check_dims(n, hi, wi, ci, co, k, stride, dilation);
     if (e) return e;
+    AFAN_TRACE_PROBLEM(0, afan::trace::FWD, n, hi, wi, ci, co, k, stride, dilation);
     if (!x || !w || !y_raw || !y_act || !acc || !stats || !barrier) return AFAN_ENULL;
     if (!aligned(x, 16) || !aligned(w, 16) || !aligned(y_raw, 16) || !aligned(y_act, 16) || !aligned(acc, 16) || !aligned(barrier, 64) ||
         (residual && !aligned(residual, 16)) || (sc_raw && !aligned(sc_raw, 16)))

@@ -345,6 +345,7 @@ int launch(const Params& p, hipStream_t st) {
     conv3x3_c64_kernel<<<grid, THREADS, LDS_BYTES, st>>>(p, tiles, logW, nullptr, xcd_pair);
 #endif
     AFAN_LAUNCH_CHECK();
+    AFAN_TRACE_LAUNCH("%s", p.flip ? "c64_dgrad" : "c64_fwd");
     return AFAN_OK;
 }
 

@@ -213,6 +213,7 @@ int small_launch(const ConvP& p, hipStream_t st) {
     else if (p.Ci == 32) conv_small_kernel<2><<<grid, THREADS, 0, st>>>(p);
     else conv_small_kernel<4><<<grid, THREADS, 0, st>>>(p);
     AFAN_LAUNCH_CHECK();
+    AFAN_TRACE_LAUNCH("small_%s<%d>", afan::trace::op() == afan::trace::DGRAD ? "dgrad" : "fwd", p.Ci == 16 ? 1 : p.Ci == 32 ? 2 : 4);
     return AFAN_OK;
 }
 

@@ -332,6 +332,7 @@ int fwd_launch(const void* x, const void* w, void* y, int64_t n, int64_t h, int6
     if (co > 32) stem_fwd_kernel<2><<<(unsigned)g, THREADS, 0, st>>>(p);
     else stem_fwd_kernel<1><<<(unsigned)g, THREADS, 0, st>>>(p);
     AFAN_LAUNCH_CHECK();
+    AFAN_TRACE_LAUNCH("stem_fwd<%d>", co > 32 ? 2 : 1);
     return AFAN_OK;
 }
 
@@ -346,6 +347,7 @@ int wgrad_launch(const void* x, const void* dy, float* grad, int64_t n, int64_t 
     if (co > 32) stem_wgrad_kernel<2><<<S, THREADS, 0, st>>>(p);
     else stem_wgrad_kernel<1><<<S, THREADS, 0, st>>>(p);
     AFAN_LAUNCH_CHECK();
+    AFAN_TRACE_LAUNCH("stem_wgrad<%d>", co > 32 ? 2 : 1);
     const int total = (int)co * 27;
     stem_wgrad_reduce_kernel<<<(total + 63) / 64, 1024, 0, st>>>(ws, grad, total, S, accumulate);
     AFAN_LAUNCH_CHECK();

@@ -196,6 +196,7 @@ int afan_conv_stem7_supported(int64_t ci, int64_t co, int k, int stride) { retur
 // y[N,Ho,Wo,64] = conv7x7/2 pad 3 (x[N,Hi,Wi,3], w[64,7,7,3]); all bf16 channels-last.  Ho = (Hi - 1) / 2 + 1.
 int afan_conv_stem7_fwd_nhwc_bf16(const void* x, const void* w, void* y, int64_t n, int64_t hi, int64_t wi, afan_stream_t stream) {
     if (n <= 0 || hi <= 0 || wi <= 0 || n > 65535) return AFAN_ESHAPE;
+    AFAN_TRACE_PROBLEM(0, afan::trace::FWD, n, hi, wi, 3, CO, KK, 2, 1);
     if (!x || !w || !y) return AFAN_ENULL;
     if (!aligned(x, 2) || !aligned(w, 2) || !aligned(y, 2)) return AFAN_EALIGN;
     const int64_t ho = (hi - 1) / 2 + 1, wo = (wi - 1) / 2 + 1;
@@ -213,6 +214,7 @@ int afan_conv_stem7_fwd_nhwc_bf16(const void* x, const void* w, void* y, int64_t
     dim3 grid((unsigned)((wo + SEG - 1) / SEG), (unsigned)ho, (unsigned)n);
     stem7_fwd_kernel<<<grid, BLOCK, lds, st>>>((const uint16_t*)x, (const uint16_t*)w, (uint16_t*)y, (int)hi, (int)wi, (int)ho, (int)wo);
     AFAN_LAUNCH_CHECK();
+    AFAN_TRACE_LAUNCH("stem7_fwd");
     return AFAN_OK;
 }
 
@@ -259,6 +261,7 @@ int64_t afan_conv_stem7_wgrad_workspace_floats(int64_t n, int64_t hi, int64_t wi
 int afan_conv_stem7_wgrad_nhwc_bf16(const void* x, const void* dy, float* grad, int64_t n, int64_t hi, int64_t wi,
                                     float* workspace, int accumulate, afan_stream_t stream) {
     if (n <= 0 || hi <= 0 || wi <= 0) return AFAN_ESHAPE;
+    AFAN_TRACE_PROBLEM(0, afan::trace::WGRAD, n, hi, wi, 3, CO, KK, 2, 1);
     if (!x || !dy || !grad || !workspace) return AFAN_ENULL;
     if (!aligned(x, 2) || !aligned(dy, 2) || !aligned(grad, 4) || !aligned(workspace, 4)) return AFAN_EALIGN;
     const int64_t ho = (hi - 1) / 2 + 1, wo = (wi - 1) / 2 + 1;
@@ -271,6 +274,7 @@ int afan_conv_stem7_wgrad_nhwc_bf16(const void* x, const void* dy, float* grad, 
     stem7_wgrad_kernel<<<G, BLOCK, 0, st>>>((const uint16_t*)x, (const uint16_t*)dy, workspace, (int)n, (int)hi, (int)wi, (int)ho,
                                             (int)wo, segs, tiles);
     AFAN_LAUNCH_CHECK();
+    AFAN_TRACE_LAUNCH("stem7_wgrad");
     stem7_wgrad_reduce_kernel<<<(K * CO + BLOCK - 1) / BLOCK, BLOCK, 0, st>>>(workspace, grad, G, accumulate);
     AFAN_LAUNCH_CHECK();
     return AFAN_OK;

@@ -387,6 +387,7 @@ int launch(const WgradP& p, int taps, hipStream_t st) {
     if (p.dn >= 0) wgrad_kernel<BM, BN, true><<<grid, THREADS, 0, st>>>(p);
     else wgrad_kernel<BM, BN, false><<<grid, THREADS, 0, st>>>(p);
     AFAN_LAUNCH_CHECK();
+    AFAN_TRACE_LAUNCH("wgrad<%d,%d,inc%d>", BM, BN, p.dn >= 0 ? 1 : 0);
     return AFAN_OK;
 }
 
@@ -420,6 +421,7 @@ int afan_conv_wgrad2_nhwc_bf16(const void* x, const void* dy, int64_t n, const v
                                float* grad, int64_t hi, int64_t wi, int64_t ci, int64_t co, int k, int stride, int dilation,
                                float* workspace, int accumulate, afan_stream_t stream) {
     if (n <= 0 || hi <= 0 || wi <= 0 || ci <= 0 || co <= 0 || n2 < 0) return AFAN_ESHAPE;
+    AFAN_TRACE_PROBLEM(0, afan::trace::WGRAD, n + n2, hi, wi, ci, co, k, stride, dilation);
     if (dilation < 1 || (dilation > 1 && (k != 3 || stride != 1 || ci % 8 || co % 8 || ci < 40 || co < 40))) return AFAN_ESHAPE;
     if (n2 > 0 && ci == 3) return AFAN_ESHAPE;                  // (the stem runs in one pass per iteration)
     if (n2 > 0 && (!x2 || !dy2)) return AFAN_ENULL;
@@ -544,6 +546,7 @@ int afan_conv_wgrad_multi_nhwc_bf16(int nb, const void* const* x, const void* co
         if (!code || (b && code != code0)) return AFAN_ESHAPE;
         code0 = code;
         if (dilation[b] < 1 || (dilation[b] > 1 && (k[b] != 3 || stride[b] != 1))) return AFAN_ESHAPE;
+        AFAN_TRACE_PROBLEM(b, afan::trace::WGRAD, n[b], hi[b], wi[b], ci[b], co[b], k[b], stride[b], dilation[b]);
         Plan pl;
         int e = build_problem(x[b], dy[b], n[b], nullptr, nullptr, 0, grad[b], hi[b], wi[b], ci[b], co[b], k[b], stride[b],
                               dilation[b], workspace + woff, accumulate, pn.p[b], pl);
@@ -578,6 +581,7 @@ int afan_conv_wgrad_multi_nhwc_bf16(int nb, const void* const* x, const void* co
     else { if (bn == 128) AFAN_WM(64, 128); else AFAN_WM(64, 64); }
 #undef AFAN_WM
     AFAN_LAUNCH_CHECK();
+    AFAN_TRACE_LAUNCH("wgrad_multi<%d,%d,inc%d>", bm, bn, inc ? 1 : 0);
     }
     AFAN_PROF("conv_wgrad_reduce_kernel", 4.0 * (double)woff, st);
     wgrad_reduce_multi_kernel<<<dim3((unsigned)grid_for(max_vec, THREADS, 1024), (unsigned)nb), THREADS, 0, st>>>(rp, accumulate);

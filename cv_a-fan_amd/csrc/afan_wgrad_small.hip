@@ -209,6 +209,7 @@ int launch(const void* x, const void* dy, float* grad, int64_t n, int64_t hi, in
     dim3 grid((unsigned)S, (unsigned)((co + 31) / 32));
     wgrad_small_kernel<<<grid, THREADS, 0, st>>>(p);
     AFAN_LAUNCH_CHECK();
+    AFAN_TRACE_LAUNCH("wgrad_small");
     const int total = (int)(co * 9 * ci);
     wgrad_small_reduce_kernel<<<(total + 63) / 64, 1024, 0, st>>>(ws, grad, total, S, accumulate);
     AFAN_LAUNCH_CHECK();

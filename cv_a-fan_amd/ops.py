@@ -1996,3 +1996,40 @@ def profile_collect(max_kernels=96):
         out[name] = {"launches": int(launches[i]), "ms": float(ms[i]), "bytes": float(nbytes[i]),
                      "flops": float(nflops[i])}
     return out
+
+
+CONV_OPS = ("fwd", "dgrad", "wgrad")
+
+
+def _conv_trace_read():
+    lib = _lib.load()
+    total = lib.afan_conv_trace_read(None, None, 0)
+    check(min(total, 0), "afan_conv_trace_read")
+    probs = (C.c_int64 * (9 * max(total, 1)))()
+    names = C.create_string_buffer(64 * max(total, 1))
+    got = lib.afan_conv_trace_read(probs, names, total)
+    check(min(got, 0), "afan_conv_trace_read")
+    out = []
+    for i in range(min(got, total)):
+        op, *shape = (int(v) for v in probs[9 * i:9 * i + 9])
+        out.append({"op": CONV_OPS[op] if 0 <= op < 3 else None, "problem": tuple(shape),
+                    "kernel": names.raw[64 * i:64 * (i + 1)].split(b"\0", 1)[0].decode()})
+    return out
+
+
+class conv_trace:
+    """Record which kernel instantiation every convolution-family launch inside the block ran (host side, at enqueue time).
+    After the block, .records is a list of {"op": "fwd" | "dgrad" | "wgrad", "problem": (n, hi, wi, ci, co, k, stride,
+    dilation) of the layer, "kernel": the instantiation's name}."""
+
+    def __init__(self):
+        self.records = []
+
+    def __enter__(self):
+        check(_lib.load().afan_conv_trace(1), "afan_conv_trace")
+        return self
+
+    def __exit__(self, *exc):
+        check(_lib.load().afan_conv_trace(0), "afan_conv_trace")
+        self.records = _conv_trace_read()
+        return False

@@ -771,6 +771,19 @@ int afan_profile_collect(char* names_out, int64_t* launches, double* total_ms, d
  * (they otherwise read ~5-8 % longer than rocprofv3's kernel durations on 10-20 us kernels).  Synchronises the stream. */
 int afan_profile_event_overhead(int n, float* us_out, afan_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Test aid: a host-side record of the convolution-family launches (tiled implicit GEMM, 64-channel, small-channel, stems,
+ * weight gradients), taken when each launch is enqueued — no device work, no synchronisation; a captured graph's launches are
+ * recorded once, at capture.  afan_conv_trace(1) clears the record and starts recording, afan_conv_trace(0) stops.
+ * afan_conv_trace_read copies up to max_records records: problems[9 * i ..] = op (0 fwd, 1 dgrad, 2 wgrad; -1 a launch without a
+ * named problem), n, hi, wi, ci, co, k, stride, dilation of the LAYER (input hi x wi, ci -> co channels, for every op), and
+ * names[64 * i ..] the instantiation launched as a C string, e.g. "igemm_fwd<64,64,7,2,2,4,2,320,gs0,bf0>", "c64_dgrad",
+ * "small_fwd<2>", "stem_fwd<2>", "wgrad<128,64,inc1>".  A launch serving several layer problems (fused pairs, multi launches)
+ * gives one record per problem.  Returns the number of records held (may exceed max_records).
+ */
+int afan_conv_trace(int on);
+int afan_conv_trace_read(int64_t* problems, char* names, int max_records);
+
 #ifdef __cplusplus
 }
 #endif

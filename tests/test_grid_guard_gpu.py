@@ -54,7 +54,9 @@ def test_barrier_give_up_is_detected_and_recovered_exactly(pkg, gpu, grid_restor
         pytest.skip("the in-launch BatchNorm is switched off in this process (AFAN_GRID_BN=0)")
     ops.GRID_BN_SC = False          # (the projection's in-launch backward sums in another order: not part of a bit comparison)
     data = _batches(gpu, 6)
-    side = torch.cuda.Stream(device=gpu)
+    # (the spinner must run BESIDE the step: a stream of the high-priority pool never shares a hardware queue with the default
+    # stream, whereas which of the normal pool's streams does depends on how many streams earlier tests of the process drew)
+    side = torch.cuda.Stream(device=gpu, priority=-1)
     res = {}
     for spin in (False, True):
         with ops.grid_bn(spin):     # the reference run: two-launch forms throughout
