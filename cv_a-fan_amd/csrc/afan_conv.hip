@@ -1848,17 +1848,30 @@ int afan_conv_fwd_nhwc_bf16(const void* x, const void* w, void* y, int64_t n, in
 
 // The same convolution with a FROZEN BatchNorm (+ residual) (+ ReLU) applied in its epilogue: y = [relu](bf16(conv(x, w)) * alpha
 // + beta [+ residual]), coefs = an afan_affine_coefs block — bit for bit the convolution launch followed by afan_affine_apply,
-// without the raw tensor's round trip and the second launch (Detection's frozen bottlenecks: seven launches of 5-13 us per block
-// become three or four).  Shapes of the tiled kernel only: AFAN_ESHAPE for the stem, the small-channel and the 64 -> 64
-// weights-in-registers kernels (their epilogues have no such form; the caller issues the two launches).
-int afan_conv_fwd_affine_nhwc_bf16(const void* x, const void* w, void* y, int64_t n, int64_t hi, int64_t wi, int64_t ci, int64_t co,
-                                   int k, int stride, const float* coefs, const void* residual, int relu, afan_stream_t stream) {
+// without the raw tensor's round trip and the second launch.  any_family = 0 (afan_conv_fwd_affine_nhwc_bf16, Detection's frozen
+// bottlenecks: seven launches of 5-13 us per block become three or four): shapes of the tiled kernel only, AFAN_ESHAPE for the
+// others (the caller issues the two launches).  any_family = 1 (afan_conv_fwd_affine_any_nhwc_bf16, Classification's eval-mode
+// forward, infer.py: one launch per convolution): every forward family of afan_conv_fwd_nhwc_bf16 at dilation 1 — the tiled kernel,
+// the small-channel kernel (afan_conv_small.hip), the 64 -> 64 weights-in-registers kernel (afan_conv_c64.hip) and the 3-channel
+// image stem (afan_conv_stem.hip; no residual there), each in an instantiation of its own (the training kernels are not touched).
+// The 7x7 stem (afan_conv_stem7.hip) has no such form.
+static int fwd_affine_impl(const void* x, const void* w, void* y, int64_t n, int64_t hi, int64_t wi, int64_t ci, int64_t co, int k,
+                           int stride, const float* coefs, const void* residual, int relu, afan_stream_t stream, bool any_family) {
+    if (any_family && ci == 3) {                                // the image stem: affine + ReLU at its staged store
+        AFAN_TRACE_PROBLEM(0, afan::trace::FWD, n, hi, wi, ci, co, k, stride, 1);
+        if (!afan_stem::eligible(n, hi, wi, ci, co, k, stride) || residual) return AFAN_ESHAPE;
+        if (!x || !w || !y || !coefs) return AFAN_ENULL;
+        if (!aligned(x, 2) || !aligned(w, 2) || !aligned(y, 16) || !aligned(coefs, 16)) return AFAN_EALIGN;
+        hipStream_t st = (hipStream_t)stream;
+        const double M = (double)n * hi * wi;
+        AFAN_PROF_FLOPS("conv_stem_fwd_kernel", 2.0 * (M * co + M * 3 + 27.0 * co), 2.0 * M * co * 27, st);
+        return afan_stem::fwd_aff_launch(x, w, y, n, hi, wi, co, coefs, relu, st);
+    }
     int e = check_dims(n, hi, wi, ci, co, k, stride, 1);
     if (e) return e;
     AFAN_TRACE_PROBLEM(0, afan::trace::FWD, n, hi, wi, ci, co, k, stride, 1);
     if (!x || !w || !y || !coefs) return AFAN_ENULL;
     if (!aligned(x, 16) || !aligned(w, 16) || !aligned(y, 16) || (residual && !aligned(residual, 16))) return AFAN_EALIGN;
-    if (ci % 8 != 0 || co % 8 != 0 || ci < 40 || co < 40) return AFAN_ESHAPE;
     const int pad = k / 2;
     ConvP p{};
     p.max_pad = 1;
@@ -1876,12 +1889,33 @@ int afan_conv_fwd_affine_nhwc_bf16(const void* x, const void* w, void* y, int64_
             const int t = r * k + s;
             c0.dh[t] = r - pad; c0.dw[t] = s - pad; c0.wofs[t] = (int)(t * ci);
         }
-    if (small_eligible(p) || afan_c64::eligible(n, hi, wi, ci, co, k, stride)) return AFAN_ESHAPE;
+    const bool small = small_eligible(p), c64 = !small && afan_c64::eligible(n, hi, wi, ci, co, k, stride);
+    if (!any_family && (small || c64)) return AFAN_ESHAPE;
+    if (!small && (ci % 8 != 0 || co % 8 != 0 || ci < 40 || co < 40)) return AFAN_ESHAPE;
+    if ((small || c64) && !aligned(coefs, 16)) return AFAN_EALIGN;   // (those two read the coefficient rows as 16-byte vectors)
     hipStream_t st = (hipStream_t)stream;
     const double M = (double)n * p.Ho * p.Wo;
     AFAN_PROF_FLOPS("conv_igemm_fwd_kernel", 2.0 * (M * co * (residual ? 2 : 1) + (double)n * hi * wi * ci + (double)co * k * k * ci),
                     2.0 * M * co * k * k * ci, st);
+    if (small) return small_launch(p, st);
+    if (c64) {
+        afan_c64::Params q{};
+        q.x = p.x; q.w = p.w; q.y = p.y; q.N = p.N; q.H = p.Hi; q.W = p.Wi; q.flip = 0; q.acc_ns = p.acc_ns;
+        q.aff = coefs; q.aff_res = p.aff_res; q.aff_relu = p.aff_relu;
+        return afan_c64::launch(q, st);
+    }
     return dispatch(p, st, false);
+}
+
+int afan_conv_fwd_affine_nhwc_bf16(const void* x, const void* w, void* y, int64_t n, int64_t hi, int64_t wi, int64_t ci, int64_t co,
+                                   int k, int stride, const float* coefs, const void* residual, int relu, afan_stream_t stream) {
+    return fwd_affine_impl(x, w, y, n, hi, wi, ci, co, k, stride, coefs, residual, relu, stream, false);
+}
+
+int afan_conv_fwd_affine_any_nhwc_bf16(const void* x, const void* w, void* y, int64_t n, int64_t hi, int64_t wi, int64_t ci,
+                                       int64_t co, int k, int stride, const float* coefs, const void* residual, int relu,
+                                       afan_stream_t stream) {
+    return fwd_affine_impl(x, w, y, n, hi, wi, ci, co, k, stride, coefs, residual, relu, stream, true);
 }
 
 // nb <= 4 forward problems on the SAME input with the SAME output shape in one launch (grid.z = problem): ASPP's atrous 3x3

@@ -19,6 +19,11 @@ struct Params {
     int bn_relu;
     const uint16_t* bny;
     const uint16_t* addend;
+    // forward only, a separate instantiation: the frozen BatchNorm behind the convolution (afan_conv_fwd_affine_any_nhwc_bf16),
+    // y = [relu](bf16(conv) * alpha + beta [+ aff_res]) with aff an afan_affine_coefs block [4][64]; no addend, no sums
+    const float* aff;
+    const uint16_t* aff_res;
+    int aff_relu;
 };
 
 // shapes this kernel takes: ci == co == 64, k == 3, stride == 1, W a power of two in [4, 32], H a multiple of 128 / W

@@ -52,6 +52,8 @@ constexpr size_t LDS_BYTES = (size_t)NBUF * HALO_ALLOC * CH * 2 + (size_t)TP * L
 #define C64_STAMP(slot) do { } while (0)
 #endif
 
+// AFF: the frozen-BatchNorm epilogue (Params::aff) instead of the addend and the sums — its own instantiation
+template <bool AFF>
 __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(2, 2)))
 void conv3x3_c64_kernel(const Params p, int tiles, int logW, uint64_t* stamps, int xcd_pair) {
 #ifdef AFAN_C64_STAMPS
@@ -158,7 +160,7 @@ void conv3x3_c64_kernel(const Params p, int tiles, int logW, uint64_t* stamps, i
 
     // epilogue roles: 4 pieces of 8 channels per output row, 64 rows per pass
     const int pc = tid & 3, pr = tid >> 2;
-    const bool want_stats = p.acc != nullptr;
+    const bool want_stats = !AFF && p.acc != nullptr;
     const bool bn_bwd = want_stats && p.bnx != nullptr;
     float s1[8], s2[8];
 #pragma unroll
@@ -208,7 +210,15 @@ void conv3x3_c64_kernel(const Params p, int tiles, int logW, uint64_t* stamps, i
         // per-channel coefficients of this thread's 8 channels: fetched per tile as 16-byte loads (cache hits) so that
         // they do not occupy registers across the MFMA phase
         float sh[8], al[8], be[8];
-        if (want_stats) {
+        if constexpr (AFF) {
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                const f32x4 b = *reinterpret_cast<const f32x4*>(p.aff + 2 * CH + c0 + 4 * h);
+                const f32x4 c = *reinterpret_cast<const f32x4*>(p.aff + 3 * CH + c0 + 4 * h);
+                al[4 * h] = b.x; al[4 * h + 1] = b.y; al[4 * h + 2] = b.z; al[4 * h + 3] = b.w;
+                be[4 * h] = c.x; be[4 * h + 1] = c.y; be[4 * h + 2] = c.z; be[4 * h + 3] = c.w;
+            }
+        } else if (want_stats) {
             const float* src = bn_bwd ? p.bn_stats : p.shift;
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
@@ -227,7 +237,18 @@ void conv3x3_c64_kernel(const Params p, int tiles, int logW, uint64_t* stamps, i
             const int r = pr + 64 * q;
             u16x8 v = *reinterpret_cast<const u16x8*>(Cst + r * LDC + pc * 8);
             const int64_t go = out0 + (int64_t)r * CH;
-            if (p.addend) {
+            if constexpr (AFF) {
+                // the tiled kernel's `pp.aff` branch (afan_conv.hip), term for term: fmaf, the residual, the NaN-passing ReLU
+                u16x8 a = {0, 0, 0, 0, 0, 0, 0, 0};
+                if (p.aff_res) a = *reinterpret_cast<const u16x8*>(p.aff_res + go);
+#pragma unroll
+                for (int j = 0; j < 8; ++j) {
+                    float t = fmaf(bf2f(v[j]), al[j], be[j]);
+                    if (p.aff_res) t += bf2f(a[j]);
+                    if (p.aff_relu) t = (t > 0.f) ? t : ((t != t) ? t : 0.f);
+                    v[j] = f2bf(t);
+                }
+            } else if (p.addend) {
                 const u16x8 a = *reinterpret_cast<const u16x8*>(p.addend + go);
 #pragma unroll
                 for (int j = 0; j < 8; ++j) v[j] = f2bf(bf2f(v[j]) + bf2f(a[j]));
@@ -318,15 +339,18 @@ int launch(const Params& p, hipStream_t st) {
         hipDeviceProp_t prop;
         if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return AFAN_ESHAPE;
         cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-        hipError_t e = hipFuncSetAttribute((const void*)conv3x3_c64_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+        hipError_t e = hipFuncSetAttribute((const void*)conv3x3_c64_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                            (int)LDS_BYTES);
+        if (e == hipSuccess)
+            e = hipFuncSetAttribute((const void*)conv3x3_c64_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_BYTES);
         if (e != hipSuccess) { cus = 0; return (int)e; }
     }
     const int grid = 2 * (tiles < cus ? tiles : cus);   // a pair of workgroups (channel halves) per tile column
 #ifdef AFAN_C64_STAMPS
+    if (p.aff) return AFAN_ESHAPE;                 // (the diagnostic build stamps the training form only)
     static uint64_t* stamps = nullptr;
     if (!stamps && hipMalloc(&stamps, 6 * 1024 * sizeof(uint64_t)) != hipSuccess) return AFAN_ESHAPE;
-    conv3x3_c64_kernel<<<grid, THREADS, LDS_BYTES, st>>>(p, tiles, logW, stamps, 1);
+    conv3x3_c64_kernel<false><<<grid, THREADS, LDS_BYTES, st>>>(p, tiles, logW, stamps, 1);
     {
         static int calls = 0;
         if (++calls % 50 == 0) {
@@ -342,7 +366,13 @@ int launch(const Params& p, hipStream_t st) {
     }
 #else
     static const int xcd_pair = [] { const char* v = getenv("AFAN_C64_XCD"); return v ? atoi(v) : 1; }();
-    conv3x3_c64_kernel<<<grid, THREADS, LDS_BYTES, st>>>(p, tiles, logW, nullptr, xcd_pair);
+    if (p.aff) {                                   // forward with a frozen BatchNorm (afan_conv_fwd_affine_any_nhwc_bf16)
+        conv3x3_c64_kernel<true><<<grid, THREADS, LDS_BYTES, st>>>(p, tiles, logW, nullptr, xcd_pair);
+        AFAN_LAUNCH_CHECK();
+        AFAN_TRACE_LAUNCH("c64_fwd_aff");
+        return AFAN_OK;
+    }
+    conv3x3_c64_kernel<false><<<grid, THREADS, LDS_BYTES, st>>>(p, tiles, logW, nullptr, xcd_pair);
 #endif
     AFAN_LAUNCH_CHECK();
     AFAN_TRACE_LAUNCH("%s", p.flip ? "c64_dgrad" : "c64_fwd");

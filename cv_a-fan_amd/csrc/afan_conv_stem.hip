@@ -86,9 +86,12 @@ struct FwdP {
     const uint16_t* x; const uint16_t* w; uint16_t* y;
     int N, H, W, Co;
     double* acc; int acc_ns; const float* shift;
+    const float* aff; int aff_relu;   // AFF only: afan_affine_coefs block [4][Co] of the frozen BatchNorm behind the stem, ReLU flag
 };
 
-template <int CG>   // groups of 32 output channels
+// AFF: y = [relu](bf16(conv) * alpha + beta) at the staged store (afan_conv_fwd_affine_any_nhwc_bf16; no residual, no sums) —
+// its own instantiation, the training kernel's code is untouched
+template <int CG, bool AFF>   // groups of 32 output channels
 __global__ __launch_bounds__(THREADS) void stem_fwd_kernel(const FwdP p) {
     constexpr int LDO = CG * 32 + 8;
     __shared__ __attribute__((aligned(16))) uint16_t in_s[WAVES][3][ROWE];
@@ -122,12 +125,16 @@ __global__ __launch_bounds__(THREADS) void stem_fwd_kernel(const FwdP p) {
     const int ppr = Co >> 3;                       // 16-byte pieces per pixel row of the output (2, 4 or 8)
     const int pieces = 32 * ppr;
     const int chunk = lane & (ppr - 1);            // this lane's 8 channels, the same for all its pieces
-    const bool want_stats = p.acc != nullptr;
-    float s1[8], s2[8], sh[8];
+    const bool want_stats = !AFF && p.acc != nullptr;
+    float s1[8], s2[8], sh[8], al[8], be[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
         s1[j] = s2[j] = 0.f;
         sh[j] = (want_stats && p.shift) ? p.shift[chunk * 8 + j] : 0.f;
+        if constexpr (AFF) {
+            al[j] = p.aff[2 * Co + chunk * 8 + j];
+            be[j] = p.aff[3 * Co + chunk * 8 + j];
+        }
     }
 
     const int tpr = W >> 5;
@@ -158,7 +165,16 @@ __global__ __launch_bounds__(THREADS) void stem_fwd_kernel(const FwdP p) {
         uint16_t* ytile = p.y + ((int64_t)rowidx * W + w0) * Co;
         for (int q = lane; q < pieces; q += 64) {
             const int px = q / ppr;
-            const u16x8 v = *reinterpret_cast<const u16x8*>(&out_s[wave][px][chunk * 8]);
+            u16x8 v = *reinterpret_cast<const u16x8*>(&out_s[wave][px][chunk * 8]);
+            if constexpr (AFF) {
+                // the tiled kernel's `pp.aff` branch (afan_conv.hip) without the residual: fmaf, then the NaN-passing ReLU
+#pragma unroll
+                for (int j = 0; j < 8; ++j) {
+                    float t = fmaf(bf2f(v[j]), al[j], be[j]);
+                    if (p.aff_relu) t = (t > 0.f) ? t : ((t != t) ? t : 0.f);
+                    v[j] = f2bf(t);
+                }
+            }
             *reinterpret_cast<u16x8*>(ytile + px * Co + chunk * 8) = v;
             if (want_stats) {
 #pragma unroll
@@ -322,15 +338,31 @@ bool eligible(int64_t n, int64_t h, int64_t w, int64_t ci, int64_t co, int k, in
     return n * h * w * co * 2 <= 0x7fffffffLL;
 }
 
-int fwd_launch(const void* x, const void* w, void* y, int64_t n, int64_t h, int64_t wd, int64_t co, double* acc, int acc_ns,
-               const float* shift, hipStream_t st) {
-    FwdP p{(const uint16_t*)x, (const uint16_t*)w, (uint16_t*)y, (int)n, (int)h, (int)wd, (int)co, acc, acc_ns, shift};
-    const int64_t tiles = n * h * (wd / 32);
+static int64_t fwd_grid(int64_t tiles) {
     int64_t g = (tiles + WAVES - 1) / WAVES;
     static const int64_t cap = [] { const char* v = getenv("AFAN_STEM_WGS"); return v ? (int64_t)atoi(v) : (int64_t)1024; }();
     if (g > cap) g = cap;                                  // 4 workgroups per CU, then persistent (2048 measured 24.6 us against 19.0: the weight-fragment setup per workgroup)
-    if (co > 32) stem_fwd_kernel<2><<<(unsigned)g, THREADS, 0, st>>>(p);
-    else stem_fwd_kernel<1><<<(unsigned)g, THREADS, 0, st>>>(p);
+    return g;
+}
+
+int fwd_aff_launch(const void* x, const void* w, void* y, int64_t n, int64_t h, int64_t wd, int64_t co, const float* coefs, int relu,
+                   hipStream_t st) {
+    FwdP p{(const uint16_t*)x, (const uint16_t*)w, (uint16_t*)y, (int)n, (int)h, (int)wd, (int)co, nullptr, 0, nullptr, coefs, relu ? 1 : 0};
+    const int64_t g = fwd_grid(n * h * (wd / 32));
+    if (co > 32) stem_fwd_kernel<2, true><<<(unsigned)g, THREADS, 0, st>>>(p);
+    else stem_fwd_kernel<1, true><<<(unsigned)g, THREADS, 0, st>>>(p);
+    AFAN_LAUNCH_CHECK();
+    AFAN_TRACE_LAUNCH("stem_fwd_aff<%d>", co > 32 ? 2 : 1);
+    return AFAN_OK;
+}
+
+int fwd_launch(const void* x, const void* w, void* y, int64_t n, int64_t h, int64_t wd, int64_t co, double* acc, int acc_ns,
+               const float* shift, hipStream_t st) {
+    FwdP p{(const uint16_t*)x, (const uint16_t*)w, (uint16_t*)y, (int)n, (int)h, (int)wd, (int)co, acc, acc_ns, shift, nullptr, 0};
+    const int64_t tiles = n * h * (wd / 32);
+    const int64_t g = fwd_grid(tiles);
+    if (co > 32) stem_fwd_kernel<2, false><<<(unsigned)g, THREADS, 0, st>>>(p);
+    else stem_fwd_kernel<1, false><<<(unsigned)g, THREADS, 0, st>>>(p);
     AFAN_LAUNCH_CHECK();
     AFAN_TRACE_LAUNCH("stem_fwd<%d>", co > 32 ? 2 : 1);
     return AFAN_OK;

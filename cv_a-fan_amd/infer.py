@@ -1,0 +1,248 @@
+"""Eval-mode forward of the Classification ResNets (resnet_s.ARCHS) for checkpoint evaluation: main_perturb.validate,
+main_learnable (through it) and main_inference.
+
+bf16 channels-last models run a fused forward: every convolution is ONE launch with its eval-mode BatchNorm (running
+statistics, a frozen affine) (+ the block's residual) (+ ReLU) in the epilogue (afan_conv_fwd_affine_any_nhwc_bf16; the tiled,
+small-channel, 64 -> 64 and 3-channel-stem kernels all have that form) — bit for bit the eager path's convolution followed by
+its afan_bn_apply.  A projection shortcut's BatchNorm goes through its own convolution's epilogue; the option-A pad shortcut,
+the ResNet-50 max-pool and the classifier head are the eager path's calls.  The ResNet-50 7x7 stem is its im2col followed by
+a fused 1x1 convolution (the eager path's own decomposition); under AFAN_STEM7_DIRECT=1 it is the direct stem kernel followed
+by one afan_affine_apply.
+
+The forward reads only buffers the Evaluator owns (bf16 weight copies, [4][C] coefficient blocks, the head's parameters),
+rewritten in place by refresh() at the start of every evaluation pass, so one hipGraph per batch shape — captured on the
+shape's second pass, forward + criterion + accuracy — serves every epoch.  fp32, NCHW, or a criterion other than a default
+nn.CrossEntropyLoss: the model's own eager forward."""
+import torch
+import torch.nn as nn
+
+from . import ops, resnet_s
+from .deeplab import StemConv, _Stem7Fn
+
+
+def accuracy(output, target):
+    """main_perturb.accuracy: top-1 precision in percent, on the device."""
+    return (output.argmax(dim=1) == target).float().sum() * (100.0 / target.shape[0])
+
+
+class _Unfused(Exception):
+    """A layer of this batch shape is not on the library's bf16 MFMA kernels in the eager path: evaluate eagerly."""
+
+
+def _default_ce(criterion):
+    return (type(criterion) is nn.CrossEntropyLoss and criterion.weight is None and criterion.ignore_index == -100
+            and criterion.reduction == "mean" and getattr(criterion, "label_smoothing", 0.0) == 0.0)
+
+
+def _main_bn(bn):
+    """(weight, bias, running_mean, running_var) of `bn`'s main set (dual BatchNorm: the set in the module unless the
+    auxiliary one is swapped in)."""
+    src = bn.adv if getattr(bn, "adv", None) is not None and bn._branch != "main" else bn
+    return src.weight, src.bias, src.running_mean, src.running_var
+
+
+class _Conv:
+    """One convolution + its BatchNorm: a private bf16 weight copy and a coefficient block."""
+
+    def __init__(self, conv, bn, relu):
+        self.conv, self.bn, self.relu = conv, bn, relu
+        self.stride = int(conv.stride[0])
+        self.stem7 = isinstance(conv, StemConv)
+        self.w = None
+        self.coefs = None
+
+    def refresh(self):
+        w = self.conv.lp_weight().detach()
+        if self.stem7 and not _Stem7Fn.DIRECT:
+            # the eager stem's 1x1 weight over the 152 im2col columns (deeplab._Stem7Fn.forward), built in place
+            k = ops._lib.load().afan_conv_stem7_im2col_k()
+            if self.w is None:
+                self.w = torch.zeros((64, k, 1, 1), dtype=torch.bfloat16, device=w.device)   # (1x1: also channels-last)
+            self.w.view(64, k)[:, :147].copy_(w.permute(0, 2, 3, 1).reshape(64, 147))
+        else:
+            if self.w is None or self.w.shape != w.shape:
+                self.w = torch.empty_like(w, memory_format=torch.channels_last)
+            self.w.copy_(w)
+        wt, b, rm, rv = _main_bn(self.bn)
+        invstd = torch.rsqrt(rv + self.bn.eps)          # BatchNorm2d.fused's expression
+        c = ops.affine_coefs(rm, invstd, wt, b)
+        if self.coefs is None:
+            self.coefs = torch.empty_like(c)
+        self.coefs.copy_(c)
+
+    def __call__(self, x, residual=None):
+        if self.stem7:
+            w = self.conv.lp_weight()          # (the eager StemConv's test: otherwise the general kernel)
+            if not (ops.conv_stem7_ok(x, w, self.conv.stride, self.conv.padding) and w.is_contiguous(memory_format=torch.channels_last)):
+                raise _Unfused
+            if _Stem7Fn.DIRECT:
+                return ops.affine_apply(ops.conv_stem7_fwd(x, self.w), self.coefs, residual, self.relu)
+            x, stride = ops.conv_stem7_im2col(x), 1          # (the columns are already at the output's stride-2 positions)
+        elif not resnet_s._own_conv_ok(x, self.w, self.conv.stride, self.conv.padding, self.conv.dilation):
+            raise _Unfused
+        else:
+            stride = self.stride
+        y = ops.conv_fwd_affine(x, self.w, stride, self.coefs, residual, self.relu, any_kernel=True)
+        if y is None:     # (no kernel with the epilogue takes the shape: the two launches it stands for)
+            y = ops.affine_apply(ops.conv_fwd(x, self.w, stride), self.coefs, residual, self.relu)
+        return y
+
+
+class Evaluator:
+    """evaluate(inp, target) -> (loss, prec1) as device scalars, the model in eval mode, no gradients.  See the module
+    docstring; call refresh() once per evaluation pass (after the weights or running statistics changed)."""
+
+    def __init__(self, model, criterion):
+        self.model, self.criterion = model, criterion
+        self.fused = (isinstance(model, resnet_s.ResNet) and type(model).forward is resnet_s.ResNet.forward
+                      and model.compute_dtype == torch.bfloat16 and model.channels_last and _default_ce(criterion)
+                      and next(model.parameters()).is_cuda)
+        self._graphs, self._seen, self._eager_shapes = {}, {}, set()
+        self._pool = None
+        self.last_logits = None          # logits of the last evaluate() (a graph's static output after a replay)
+        if self.fused:
+            self._plan()
+
+    # ------------------------------------------------------------------------------------------------ plan
+    def _plan(self):
+        L = list(self.model.sequential_model)
+        norm = L[0]
+        assert isinstance(norm, resnet_s.NormalizeByChannelMeanStd)
+        self.norm = norm
+        self.stem = _Conv(L[1], L[2], isinstance(L[3], nn.ReLU))
+        i = 4 if isinstance(L[3], nn.ReLU) else 3
+        self.pre = []                                   # modules between the stem and the first block (ResNet-50's max-pool)
+        while not isinstance(L[i], (resnet_s.BasicBlock, resnet_s.Bottleneck)):
+            self.pre.append(L[i])
+            i += 1
+        self.blocks = []
+        while isinstance(L[i], (resnet_s.BasicBlock, resnet_s.Bottleneck)):
+            blk = L[i]
+            chain = [_Conv(c, b, True) for c, b in blk._chain()]      # every BatchNorm of the chain is followed by a ReLU
+            sc = _Conv(blk.shortcut[0], blk.shortcut[1], False) if blk._sc_kind == "conv" else None
+            self.blocks.append((blk, chain, sc))
+            i += 1
+        if not (isinstance(L[i], resnet_s._HeadPool) and isinstance(L[i + 1], nn.Flatten) and isinstance(L[i + 2], nn.Linear)):
+            raise ValueError("Evaluator: expected the pool / flatten / linear head")
+        self.lin = L[i + 2]
+        self.convs = [self.stem] + [c for _, ch, sc in self.blocks for c in ch + ([sc] if sc else [])]
+        self.mean = self.std = self.lin_w = self.lin_b = None
+
+    def refresh(self):
+        """Rewrite the private buffers (weights, coefficients, normalisation constants, head) in place from the model."""
+        if not self.fused:
+            return
+        with torch.no_grad():
+            for c in self.convs:
+                c.refresh()
+            for name, src in (("mean", self.norm.mean), ("std", self.norm.std), ("lin_w", self.lin.weight), ("lin_b", self.lin.bias)):
+                if src is None:
+                    continue
+                dst = getattr(self, name)
+                if dst is None:
+                    setattr(self, name, src.detach().clone())
+                else:
+                    dst.copy_(src.detach())
+
+    # --------------------------------------------------------------------------------------------- forward
+    def _forward(self, x):
+        """The eval forward of ResNet.forward, one fused launch per convolution."""
+        x = ops.normalize_nchw(x.contiguous().float(), self.mean, self.std, torch.bfloat16, True)
+        x = self.stem(x)
+        for m in self.pre:
+            x = m(x)
+        for blk, chain, sc in self.blocks:
+            h = x
+            for c in chain[:-1]:
+                h = c(h)
+            if sc is not None:
+                res = sc(x)
+            elif blk._sc_kind == "pad":
+                res = blk.shortcut(x).contiguous(memory_format=torch.channels_last)
+            else:
+                res = x
+            x = chain[-1](h, res)
+        lin = self.lin
+        xh = resnet_s._head_in(x)
+        if resnet_s._head_ok(xh, lin):
+            return ops.head_forward(xh, self.lin_w, self.lin_b)[0]
+        x = x.float().mean(dim=(2, 3), keepdim=True).flatten(1)          # _HeadPool, Flatten, then resnet_s._linear's kernel
+        return resnet_s._LinearFn.apply(x, self.lin_w, self.lin_b, False)
+
+    def _eager(self, inp, target):
+        m = self.model
+        out = m(inp, end_point=m.layer_number, start_point=0)
+        loss = self.criterion(out, target)
+        return out, loss.float(), accuracy(out.float(), target)
+
+    def _fused_step(self, inp, target):
+        out = self._forward(inp)
+        loss = self.criterion(out, target)
+        return out, loss.float(), accuracy(out.float(), target)
+
+    def forward(self, inp):
+        """Logits of the eval forward (fused or eager) — no graph."""
+        with torch.no_grad():
+            if self.fused and self._shape_fused(inp):
+                try:
+                    return self._forward(inp)
+                except _Unfused:
+                    self._eager_shapes.add(tuple(inp.shape))
+            m = self.model
+            return m(inp, end_point=m.layer_number, start_point=0)
+
+    def _shape_fused(self, inp):
+        return tuple(inp.shape) not in self._eager_shapes
+
+    def evaluate(self, inp, target):
+        """(loss, prec1) of one batch as device scalars; nothing is read back here."""
+        with torch.no_grad():
+            if not self.fused:
+                return self._run(self._eager, inp, target)
+            key = (tuple(inp.shape), inp.dtype, tuple(target.shape), target.dtype)
+            g = self._graphs.get(key)
+            if g is not None:
+                graph, sx, sy, out, loss, prec = g
+                sx.copy_(inp)
+                sy.copy_(target)
+                graph.replay()
+                self.last_logits = out
+                return loss.clone(), prec.clone()
+            if not self._shape_fused(inp):
+                return self._run(self._eager, inp, target)
+            try:
+                r = self._run(self._fused_step, inp, target)
+            except _Unfused:
+                self._eager_shapes.add(tuple(inp.shape))
+                return self._run(self._eager, inp, target)
+            self._seen[key] = self._seen.get(key, 0) + 1
+            if self._seen[key] >= 2:            # a shape that recurs (every epoch) gets its graph; its first pass was the warm-up
+                self._capture(key, inp, target)
+            return r
+
+    def _run(self, fn, inp, target):
+        out, loss, prec = fn(inp, target)
+        self.last_logits = out
+        return loss, prec
+
+    def _capture(self, key, inp, target):
+        dev = inp.device
+        sx, sy = inp.clone(), target.clone()
+        stream = torch.cuda.Stream(device=dev)
+        stream.wait_stream(torch.cuda.current_stream(dev))
+        graph = torch.cuda.CUDAGraph()
+        with ops.no_gc_during_capture(), torch.cuda.graph(graph, pool=self._pool, stream=stream, capture_error_mode="thread_local"):
+            out, loss, prec = self._fused_step(sx, sy)
+        torch.cuda.current_stream(dev).wait_stream(stream)
+        if self._pool is None:
+            self._pool = graph.pool()
+        self._graphs[key] = (graph, sx, sy, out, loss, prec)
+
+
+def evaluator_for(model, criterion):
+    """The model's Evaluator for `criterion` (kept on the model, so its graphs serve every epoch)."""
+    ev = getattr(model, "_afan_evaluator", None)
+    if ev is None or ev.criterion is not criterion:
+        ev = Evaluator(model, criterion)
+        object.__setattr__(model, "_afan_evaluator", ev)
+    return ev

@@ -22,9 +22,9 @@ if __package__ in (None, ""):  # executed as a script (cmd/run_perturb.sh): impo
     import importlib
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     _pkg = importlib.import_module("cv_a-fan_amd")
-    resnet_s, train_step, host = _pkg.resnet_s, _pkg.train_step, _pkg.host
+    resnet_s, train_step, host, infer = _pkg.resnet_s, _pkg.train_step, _pkg.host, _pkg.infer
 else:
-    from . import host, resnet_s, train_step
+    from . import host, infer, resnet_s, train_step
 
 parser = argparse.ArgumentParser(description="A-FAN CIFAR-10 training on MI355X")
 # ---- base setting (main_perturb.py:28-33)
@@ -82,20 +82,27 @@ class AverageMeter(object):
 
 
 # ------------------------------------------------------------------------------------------------ data
+def _cifar10_dir(root):
+    return root if os.path.basename(root.rstrip("/")) == "cifar-10-batches-py" else os.path.join(root, "cifar-10-batches-py")
+
+
+def _read_cifar10_batch(path):
+    with open(path, "rb") as f:
+        b = pickle.load(f, encoding="latin1")
+    return np.asarray(b["data"], dtype=np.uint8).reshape(-1, 3, 32, 32), np.asarray(b["labels"], dtype=np.int64)
+
+
+def _load_cifar10_test(root):
+    """The test split (cifar-10-batches-py/test_batch) as uint8 NCHW images and labels, in file order."""
+    return _read_cifar10_batch(os.path.join(_cifar10_dir(root), "test_batch"))
+
+
 def _load_cifar10(root):
     """cifar-10-batches-py pickles -> uint8 NCHW arrays; the 45k/5k train/val split of dataset.py:43-45."""
-    d = root if os.path.basename(root.rstrip("/")) == "cifar-10-batches-py" else os.path.join(root, "cifar-10-batches-py")
-    xs, ys = [], []
-    for i in range(1, 6):
-        with open(os.path.join(d, f"data_batch_{i}"), "rb") as f:
-            b = pickle.load(f, encoding="latin1")
-        xs.append(np.asarray(b["data"], dtype=np.uint8).reshape(-1, 3, 32, 32))
-        ys.append(np.asarray(b["labels"], dtype=np.int64))
-    with open(os.path.join(d, "test_batch"), "rb") as f:
-        b = pickle.load(f, encoding="latin1")
-    xt, yt = np.asarray(b["data"], dtype=np.uint8).reshape(-1, 3, 32, 32), np.asarray(b["labels"], dtype=np.int64)
+    d = _cifar10_dir(root)
+    xs, ys = zip(*(_read_cifar10_batch(os.path.join(d, f"data_batch_{i}")) for i in range(1, 6)))
     x, y = np.concatenate(xs), np.concatenate(ys)
-    return (x[:45000], y[:45000]), (x[45000:], y[45000:]), (xt, yt)
+    return (x[:45000], y[:45000]), (x[45000:], y[45000:]), _load_cifar10_test(root)
 
 
 class DeviceLoader:
@@ -210,19 +217,30 @@ def train(train_loader, trainer, optimizer, epoch, args, log):
 
 
 def validate(val_loader, model, criterion, args, log):
-    """main_perturb.py:227-263"""
+    """main_perturb.py:227-263.  The eval forward is infer.Evaluator's (bf16 channels-last: one fused launch per convolution,
+    replayed as a hipGraph per batch shape); per-batch loss and precision stay on the device and are read back at --print_freq
+    batches and at the end, in batch order, so the printed values are those of the per-batch reads."""
     losses, top1 = AverageMeter(), AverageMeter()
     model.eval()
+    ev = infer.evaluator_for(model, criterion)
+    ev.refresh()
+    pending = []
+
+    def flush():
+        for loss_t, prec_t, n in pending:
+            losses.update(loss_t.item(), n)
+            top1.update(prec_t.item(), n)
+        pending.clear()
+
     for i, (inp, target) in enumerate(val_loader):
-        with torch.no_grad():
-            output = model(inp, end_point=model.layer_number, start_point=0)
-            loss = criterion(output, target)
-        losses.update(loss.float().item(), inp.size(0))
-        top1.update(accuracy(output.float(), target).item(), inp.size(0))
+        loss, prec = ev.evaluate(inp, target)
+        pending.append((loss, prec, inp.size(0)))
         if i % args.print_freq == 0:
+            flush()
             log("Test: [{0}/{1}]\t"
                 "Loss {loss.val:.4f} ({loss.avg:.4f})\t"
                 "Accuracy {top1.val:.3f} ({top1.avg:.3f})".format(i, len(val_loader), loss=losses, top1=top1))
+    flush()
     log("valid_accuracy {top1.avg:.3f}".format(top1=top1))
     return top1.avg, losses.avg
 

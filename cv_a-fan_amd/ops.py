@@ -1164,10 +1164,13 @@ def _conv_dgrad_bn_pair(dy, pair, in_hw, bn_x, bn_stats, relu, bn_y, want_dres, 
     return dx, dres
 
 
-def conv_fwd_affine(x, w, stride, coefs, residual=None, relu=False):
-    """[relu](bf16(conv2d(x, w)) * alpha + beta [+ residual]) in ONE launch (afan_conv_fwd_affine_nhwc_bf16): a convolution with the
-    frozen BatchNorm behind it in its epilogue.  Returns None where the shape belongs to a kernel without that epilogue (the
-    caller issues conv_fwd + affine_apply: the same bits)."""
+def conv_fwd_affine(x, w, stride, coefs, residual=None, relu=False, any_kernel=False):
+    """[relu](bf16(conv2d(x, w)) * alpha + beta [+ residual]) in ONE launch: a convolution with the frozen BatchNorm behind it in its
+    epilogue.  any_kernel=False (afan_conv_fwd_affine_nhwc_bf16): the tiled kernel's shapes; None where the shape belongs to another
+    kernel (the caller issues conv_fwd + affine_apply: the same bits).  any_kernel=True (afan_conv_fwd_affine_any_nhwc_bf16, the
+    eval forward of infer.py): every forward kernel family of conv_fwd (tiled, small-channel, 64 -> 64 weights-in-registers,
+    3-channel image stem — the stem without a residual), coefs a 16-byte aligned afan_affine_coefs block; None where no kernel takes
+    the shape."""
     lib = _lib.load()
     _cl4(x, "x"), _cl4(w, "w")
     n, ci, hi, wi = x.shape
@@ -1175,11 +1178,12 @@ def conv_fwd_affine(x, w, stride, coefs, residual=None, relu=False):
     pad = k // 2
     ho, wo = (hi + 2 * pad - k) // stride + 1, (wi + 2 * pad - k) // stride + 1
     y = torch.empty((n, co, ho, wo), dtype=torch.bfloat16, device=x.device, memory_format=torch.channels_last)
-    rc = lib.afan_conv_fwd_affine_nhwc_bf16(_ptr(x), _ptr(w), _ptr(y), n, hi, wi, ci, co, k, int(stride), _ptr(coefs), _ptr(residual),
-                                            int(bool(relu)), _stream(x))
+    name = "afan_conv_fwd_affine_any_nhwc_bf16" if any_kernel else "afan_conv_fwd_affine_nhwc_bf16"
+    rc = getattr(lib, name)(_ptr(x), _ptr(w), _ptr(y), n, hi, wi, ci, co, k, int(stride), _ptr(coefs), _ptr(residual),
+                            int(bool(relu)), _stream(x))
     if rc == -3:
         return None
-    check(rc, "afan_conv_fwd_affine_nhwc_bf16")
+    check(rc, name)
     CALLS["conv_fwd"] += 1
     return y
 

@@ -264,6 +264,13 @@ int afan_conv_fwd_nhwc_bf16(const void* x, const void* w, void* y, int64_t n, in
  * afan_conv_fwd_nhwc_bf16 followed by afan_affine_apply.  AFAN_ESHAPE for shapes the stem / small-channel / 64 -> 64 kernels take. */
 int afan_conv_fwd_affine_nhwc_bf16(const void* x, const void* w, void* y, int64_t n, int64_t hi, int64_t wi, int64_t ci, int64_t co,
                                    int k, int stride, const float* coefs, const void* residual, int relu, afan_stream_t stream);
+/* afan_conv_fwd_affine_any_nhwc_bf16 — the same, on every forward family of afan_conv_fwd_nhwc_bf16 at dilation 1 (Classification's
+ * eval-mode forward): the tiled kernel, the small-channel kernel, the 64 -> 64 weights-in-registers kernel and the 3-channel image
+ * stem (ci == 3: no residual, AFAN_ESHAPE with one), each in an instantiation of its own; coefs 16-byte aligned.  AFAN_ESHAPE where
+ * no forward kernel takes the shape. */
+int afan_conv_fwd_affine_any_nhwc_bf16(const void* x, const void* w, void* y, int64_t n, int64_t hi, int64_t wi, int64_t ci,
+                                       int64_t co, int k, int stride, const float* coefs, const void* residual, int relu,
+                                       afan_stream_t stream);
 /* nb (1..4) forward convolutions on the SAME input x with the SAME output shape in ONE launch: w[b] / y[b] / ksize[b] (1 or 3)
  * / dilation[b] per problem (host arrays; device pointers inside), BatchNorm moments of y[b] around stats_shift[b] into the
  * f64 accumulator block stats_acc[b] (both arrays NULL: no moments).  (1) The atrous branches of ASPP,
