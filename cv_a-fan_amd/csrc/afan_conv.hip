@@ -1650,7 +1650,7 @@ static int dgrad_impl(const void* dy, const void* dy_sc, const void* wt, void* d
                       int64_t ci, int64_t co, int k, int stride, int dilation, const void* addend, const void* bn_x,
                       const float* bn_stats, int bn_relu, const void* bn_y, float* bn_partials, double* bn_acc, int groups,
                       afan_stream_t stream, const float* aff_alpha = nullptr, const void* aff_act = nullptr, void* dx2 = nullptr,
-                      const ConvP* bnf = nullptr) {
+                      const ConvP* bnf = nullptr, bool any_family = false) {
     int e = check_dims(n, hi, wi, co, ci, k, stride, dilation);   // reduction runs over co here
     if (e) return e;
     AFAN_TRACE_PROBLEM(0, afan::trace::DGRAD, n, hi, wi, ci, co, k, stride, dilation);
@@ -1678,10 +1678,13 @@ static int dgrad_impl(const void* dy, const void* dy_sc, const void* wt, void* d
     p.max_pad = dilation;
     p.addend = (const uint16_t*)addend;
     if (aff_alpha) {                                         // the layer in front's frozen BatchNorm + ReLU backward in the epilogue
-        if (!aff_act) return AFAN_ENULL;
+        // any_family (afan_conv_dgrad_affine_any_nhwc_bf16): the small-channel and the 64 -> 64 kernels too, in instantiations of their
+        // own, and there the ReLU mask is optional (aff_act == NULL: a frozen BatchNorm without a ReLU)
+        any_family = any_family && !dx2;
+        if (!aff_act && !any_family) return AFAN_ENULL;
         if ((addend && !dx2) || bn_partials || bn_acc || dy_sc || groups > 1 || !aligned(aff_act, 16)) return AFAN_ESHAPE;
         if (dx2 && (!aligned(dx2, 16) || (addend && !aligned(addend, 16)))) return AFAN_EALIGN;
-        if (afan_c64::eligible(n, hi, wi, co, ci, k, stride)) return AFAN_ESHAPE;      // (that kernel's epilogue has no such form)
+        if (!any_family && afan_c64::eligible(n, hi, wi, co, ci, k, stride)) return AFAN_ESHAPE;      // (that kernel's training epilogue has no such form)
         p.aff = aff_alpha; p.aff_res = (const uint16_t*)aff_act; p.aff_bwd = dx2 ? 2 : 1; p.y2 = (uint16_t*)dx2;
     }
     if (bn_partials && bn_acc) return AFAN_ESHAPE;
@@ -1713,6 +1716,10 @@ static int dgrad_impl(const void* dy, const void* dy_sc, const void* wt, void* d
         q.x = p.x; q.w = p.w; q.y = p.y; q.N = p.N; q.H = (int)hi; q.W = (int)wi; q.flip = 1;
         q.acc = bn_acc; q.acc_ns = p.acc_ns; q.bnx = p.bnx; q.bn_stats = p.bn_stats; q.bn_relu = p.bn_relu; q.bny = p.bny;
         q.addend = p.addend;
+        if (p.aff) {                                         // (any_family: the c64_dgrad_aff instantiation reads its alpha row as 16-byte vectors)
+            if (!aligned(aff_alpha, 16)) return AFAN_EALIGN;
+            q.aff = p.aff; q.aff_res = p.aff_res; q.aff_relu = p.aff_res ? 1 : 0;
+        }
         return afan_c64::launch(q, st);
     }
     if (stride == 1) {
@@ -1726,8 +1733,13 @@ static int dgrad_impl(const void* dy, const void* dy_sc, const void* wt, void* d
                 c0.dh[t] = (pad - r) * dilation; c0.dw[t] = (pad - s) * dilation; c0.wofs[t] = (int)(t * co);
             }
         if (bnf) return small_eligible(p) ? AFAN_ESHAPE : dispatch_bnf(p, st, true);
-        if (small_eligible(p)) return (p.aff || !small_groups_ok(p)) ? AFAN_ESHAPE : small_launch(p, st);
+        if (small_eligible(p)) {
+            if ((p.aff && !any_family) || !small_groups_ok(p)) return AFAN_ESHAPE;
+            if (p.aff && !aligned(aff_alpha, 16)) return AFAN_EALIGN;              // (small_dgrad_aff reads its alpha row as 16-byte vectors)
+            return small_launch(p, st);
+        }
         if (co % 8 != 0 || ci % 8 != 0 || co < 40 || ci < 40) return AFAN_ESHAPE;   // (small shape asked for the partial-slab sums)
+        if (p.aff && !p.aff_res) return AFAN_ESHAPE;                                // (the tiled kernel's backward epilogue always masks)
         return dispatch(p, st, true);
     }
     // stride 2: output pixel (2h'+ph, 2w'+pw) receives tap (r,s) iff (ph + pad - r) and (pw + pad - s) are even;
@@ -1762,8 +1774,13 @@ static int dgrad_impl(const void* dy, const void* dy_sc, const void* wt, void* d
         }
     p.n_classes = nc;
     if (bnf) return nc == 4 ? dispatch_bnf(p, st, true) : AFAN_ESHAPE;      // (even sizes: four classes of equal size, no idle tiles)
-    if (!dy_sc && small_eligible(p)) return (p.aff || !small_groups_ok(p)) ? AFAN_ESHAPE : small_launch(p, st);
+    if (!dy_sc && small_eligible(p)) {
+        if ((p.aff && !any_family) || !small_groups_ok(p)) return AFAN_ESHAPE;
+        if (p.aff && !aligned(aff_alpha, 16)) return AFAN_EALIGN;
+        return small_launch(p, st);
+    }
     if (co % 8 != 0 || ci % 8 != 0 || co < 40 || ci < 40) return AFAN_ESHAPE;
+    if (p.aff && !p.aff_res) return AFAN_ESHAPE;
     return dispatch(p, st, true);
 }
 
@@ -2068,6 +2085,18 @@ int afan_conv_dgrad_affine_nhwc_bf16(const void* dy, const void* wt, void* dx, i
     if (!alpha || !act) return AFAN_ENULL;
     return dgrad_impl(dy, nullptr, wt, dx, n, hi, wi, ci, co, k, stride, 1, nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr, 1, stream,
                       alpha, act);
+}
+
+// The same on every input-gradient family of afan_conv_dgrad_nhwc_bf16 at dilation 1 (Classification's eval-mode backward, infer.py:
+// one launch per convolution): the tiled kernel as above, the small-channel kernel (small_dgrad_aff<KK>) and the 64 -> 64
+// weights-in-registers kernel (c64_dgrad_aff), each in an instantiation of its own (the training kernels are not touched).  On those
+// two the ReLU mask is optional (act == NULL: dx = bf16(bf16(dgrad(dy)) * alpha[c]), afan_affine_relu_bwd(relu = 0)) and alpha is
+// 16-byte aligned; the tiled kernel answers AFAN_ESHAPE without a mask.  AFAN_ESHAPE where no input-gradient kernel takes the shape.
+int afan_conv_dgrad_affine_any_nhwc_bf16(const void* dy, const void* wt, void* dx, int64_t n, int64_t hi, int64_t wi, int64_t ci,
+                                         int64_t co, int k, int stride, const float* alpha, const void* act, afan_stream_t stream) {
+    if (!alpha) return AFAN_ENULL;
+    return dgrad_impl(dy, nullptr, wt, dx, n, hi, wi, ci, co, k, stride, 1, nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr, 1, stream,
+                      alpha, act, nullptr, nullptr, true);
 }
 
 // The input gradient that arrives at the OUTPUT of a frozen-BatchNorm residual block (Detection's bottlenecks: out = relu(bn3(conv3) +

@@ -52,8 +52,10 @@ constexpr size_t LDS_BYTES = (size_t)NBUF * HALO_ALLOC * CH * 2 + (size_t)TP * L
 #define C64_STAMP(slot) do { } while (0)
 #endif
 
-// AFF: the frozen-BatchNorm epilogue (Params::aff) instead of the addend and the sums — its own instantiation
-template <bool AFF>
+// AFF = 1: the frozen-BatchNorm epilogue (Params::aff) instead of the addend and the sums; AFF = 2 (input gradient): the frozen
+// BatchNorm (+ ReLU) backward on the way out (Params::aff = the alpha row, aff_res = the stored activation) — instantiations of
+// their own
+template <int AFF>
 __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(2, 2)))
 void conv3x3_c64_kernel(const Params p, int tiles, int logW, uint64_t* stamps, int xcd_pair) {
 #ifdef AFAN_C64_STAMPS
@@ -160,7 +162,7 @@ void conv3x3_c64_kernel(const Params p, int tiles, int logW, uint64_t* stamps, i
 
     // epilogue roles: 4 pieces of 8 channels per output row, 64 rows per pass
     const int pc = tid & 3, pr = tid >> 2;
-    const bool want_stats = !AFF && p.acc != nullptr;
+    const bool want_stats = AFF == 0 && p.acc != nullptr;
     const bool bn_bwd = want_stats && p.bnx != nullptr;
     float s1[8], s2[8];
 #pragma unroll
@@ -210,7 +212,13 @@ void conv3x3_c64_kernel(const Params p, int tiles, int logW, uint64_t* stamps, i
         // per-channel coefficients of this thread's 8 channels: fetched per tile as 16-byte loads (cache hits) so that
         // they do not occupy registers across the MFMA phase
         float sh[8], al[8], be[8];
-        if constexpr (AFF) {
+        if constexpr (AFF == 2) {
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                const f32x4 b = *reinterpret_cast<const f32x4*>(p.aff + c0 + 4 * h);
+                al[4 * h] = b.x; al[4 * h + 1] = b.y; al[4 * h + 2] = b.z; al[4 * h + 3] = b.w;
+            }
+        } else if constexpr (AFF == 1) {
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
                 const f32x4 b = *reinterpret_cast<const f32x4*>(p.aff + 2 * CH + c0 + 4 * h);
@@ -237,7 +245,19 @@ void conv3x3_c64_kernel(const Params p, int tiles, int logW, uint64_t* stamps, i
             const int r = pr + 64 * q;
             u16x8 v = *reinterpret_cast<const u16x8*>(Cst + r * LDC + pc * 8);
             const int64_t go = out0 + (int64_t)r * CH;
-            if constexpr (AFF) {
+            if constexpr (AFF == 2) {
+                // the tiled kernel's `aff_bwd` branch (afan_conv.hip) = affine_bwd_kernel's expression: the mask from the stored
+                // activation (where there is one), then the plain multiply
+                u16x8 a = {0, 0, 0, 0, 0, 0, 0, 0};
+                if (p.aff_res) a = *reinterpret_cast<const u16x8*>(p.aff_res + go);
+#pragma unroll
+                for (int j = 0; j < 8; ++j) {
+                    float t = bf2f(v[j]);
+                    if (p.aff_res) t = (bf2f(a[j]) > 0.f) ? t : 0.f;
+                    t *= al[j];
+                    v[j] = f2bf(t);
+                }
+            } else if constexpr (AFF == 1) {
                 // the tiled kernel's `pp.aff` branch (afan_conv.hip), term for term: fmaf, the residual, the NaN-passing ReLU
                 u16x8 a = {0, 0, 0, 0, 0, 0, 0, 0};
                 if (p.aff_res) a = *reinterpret_cast<const u16x8*>(p.aff_res + go);
@@ -339,10 +359,12 @@ int launch(const Params& p, hipStream_t st) {
         hipDeviceProp_t prop;
         if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return AFAN_ESHAPE;
         cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-        hipError_t e = hipFuncSetAttribute((const void*)conv3x3_c64_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize,
+        hipError_t e = hipFuncSetAttribute((const void*)conv3x3_c64_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                            (int)LDS_BYTES);
         if (e == hipSuccess)
-            e = hipFuncSetAttribute((const void*)conv3x3_c64_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_BYTES);
+            e = hipFuncSetAttribute((const void*)conv3x3_c64_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_BYTES);
+        if (e == hipSuccess)
+            e = hipFuncSetAttribute((const void*)conv3x3_c64_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_BYTES);
         if (e != hipSuccess) { cus = 0; return (int)e; }
     }
     const int grid = 2 * (tiles < cus ? tiles : cus);   // a pair of workgroups (channel halves) per tile column
@@ -350,7 +372,7 @@ int launch(const Params& p, hipStream_t st) {
     if (p.aff) return AFAN_ESHAPE;                 // (the diagnostic build stamps the training form only)
     static uint64_t* stamps = nullptr;
     if (!stamps && hipMalloc(&stamps, 6 * 1024 * sizeof(uint64_t)) != hipSuccess) return AFAN_ESHAPE;
-    conv3x3_c64_kernel<false><<<grid, THREADS, LDS_BYTES, st>>>(p, tiles, logW, stamps, 1);
+    conv3x3_c64_kernel<0><<<grid, THREADS, LDS_BYTES, st>>>(p, tiles, logW, stamps, 1);
     {
         static int calls = 0;
         if (++calls % 50 == 0) {
@@ -366,13 +388,19 @@ int launch(const Params& p, hipStream_t st) {
     }
 #else
     static const int xcd_pair = [] { const char* v = getenv("AFAN_C64_XCD"); return v ? atoi(v) : 1; }();
+    if (p.aff && p.flip) {                         // input gradient + frozen BatchNorm / ReLU backward (afan_conv_dgrad_affine_any_nhwc_bf16)
+        conv3x3_c64_kernel<2><<<grid, THREADS, LDS_BYTES, st>>>(p, tiles, logW, nullptr, xcd_pair);
+        AFAN_LAUNCH_CHECK();
+        AFAN_TRACE_LAUNCH("c64_dgrad_aff");
+        return AFAN_OK;
+    }
     if (p.aff) {                                   // forward with a frozen BatchNorm (afan_conv_fwd_affine_any_nhwc_bf16)
-        conv3x3_c64_kernel<true><<<grid, THREADS, LDS_BYTES, st>>>(p, tiles, logW, nullptr, xcd_pair);
+        conv3x3_c64_kernel<1><<<grid, THREADS, LDS_BYTES, st>>>(p, tiles, logW, nullptr, xcd_pair);
         AFAN_LAUNCH_CHECK();
         AFAN_TRACE_LAUNCH("c64_fwd_aff");
         return AFAN_OK;
     }
-    conv3x3_c64_kernel<false><<<grid, THREADS, LDS_BYTES, st>>>(p, tiles, logW, nullptr, xcd_pair);
+    conv3x3_c64_kernel<0><<<grid, THREADS, LDS_BYTES, st>>>(p, tiles, logW, nullptr, xcd_pair);
 #endif
     AFAN_LAUNCH_CHECK();
     AFAN_TRACE_LAUNCH("%s", p.flip ? "c64_dgrad" : "c64_fwd");

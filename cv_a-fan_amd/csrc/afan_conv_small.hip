@@ -29,9 +29,11 @@ typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 constexpr int THREADS = 256;
 constexpr int NB = 32;       // output channels per workgroup column
 
-// AFF: the frozen-BatchNorm epilogue of afan_conv_fwd_affine_any_nhwc_bf16 (ConvP::aff, forward only) in place of the addend
-// and the BatchNorm sums: a separate instantiation, so the training kernels' code is untouched
-template <int KK, bool AFF>  // MFMA k-steps per tap = reduction channels / 16
+// AFF = 1: the frozen-BatchNorm epilogue of afan_conv_fwd_affine_any_nhwc_bf16 (ConvP::aff, forward only) in place of the addend
+// and the BatchNorm sums; AFF = 2: the frozen BatchNorm (+ ReLU) BACKWARD on an input gradient's way out
+// (afan_conv_dgrad_affine_any_nhwc_bf16: ConvP::aff = the alpha row, aff_res = the stored activation or NULL).  Separate
+// instantiations, so the training kernels' (AFF = 0) code is untouched
+template <int KK, int AFF>   // MFMA k-steps per tap = reduction channels / 16
 __global__ __launch_bounds__(THREADS) void conv_small_kernel(const ConvP pp) {
     const ConvClass& cc = pp.cls[blockIdx.y];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, half = lane >> 5, col = lane & 31;
@@ -47,7 +49,7 @@ __global__ __launch_bounds__(THREADS) void conv_small_kernel(const ConvP pp) {
     const int out_bytes = (int)((int64_t)pp.N * pp.Ho * pp.Wo * Co * 2);
     const uint16_t* const addp = AFF ? pp.aff_res : pp.addend;    // the output-shaped operand: residual / addend
     const __amdgpu_buffer_rsrc_t ar = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(addp), 0, addp ? out_bytes : 0, 0x00020000);
-    const bool want_stats = !AFF && pp.acc != nullptr;
+    const bool want_stats = AFF == 0 && pp.acc != nullptr;
     const bool bn_bwd = want_stats && pp.bnx != nullptr;
     const __amdgpu_buffer_rsrc_t bxr = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(pp.bnx), 0, bn_bwd ? out_bytes : 0, 0x00020000);
     const __amdgpu_buffer_rsrc_t byr = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(pp.bny), 0, (bn_bwd && pp.bny) ? out_bytes : 0, 0x00020000);
@@ -117,7 +119,7 @@ __global__ __launch_bounds__(THREADS) void conv_small_kernel(const ConvP pp) {
             u16x4 v;
 #pragma unroll
             for (int e = 0; e < 4; ++e) v[e] = f2bf(acc[4 * g + e]);
-            if constexpr (AFF) {
+            if constexpr (AFF == 1) {
                 // a frozen BatchNorm (+ residual) (+ ReLU) on the bf16-rounded convolution output: the tiled kernel's `pp.aff`
                 // branch (afan_conv.hip), term for term
                 u16x4 a = {0, 0, 0, 0};
@@ -132,6 +134,21 @@ __global__ __launch_bounds__(THREADS) void conv_small_kernel(const ConvP pp) {
                     float t = fmaf(bf2f(v[e]), al[e], be[e]);
                     if (addp) t += bf2f(a[e]);
                     if (pp.aff_relu) t = (t > 0.f) ? t : ((t != t) ? t : 0.f);
+                    v[e] = f2bf(t);
+                }
+            } else if constexpr (AFF == 2) {
+                // the backward of the frozen BatchNorm (+ ReLU) in front of this convolution on the bf16-rounded input gradient: the
+                // tiled kernel's `aff_bwd` branch (afan_conv.hip) = affine_bwd_kernel's expression (mask from the stored
+                // activation where there is one, then the plain multiply)
+                u16x4 a = {0, 0, 0, 0};
+                if (addp) a = __builtin_bit_cast(u16x4, __builtin_amdgcn_raw_buffer_load_b64(ar, (int)bo, 0, 0));
+                f32x4 al = {0.f, 0.f, 0.f, 0.f};
+                if (st_ok) al = *reinterpret_cast<const f32x4*>(pp.aff + ch);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    float t = bf2f(v[e]);
+                    if (addp) t = (bf2f(a[e]) > 0.f) ? t : 0.f;
+                    t *= al[e];
                     v[e] = f2bf(t);
                 }
             } else if (pp.addend) {
@@ -229,17 +246,25 @@ int small_launch(const ConvP& p, hipStream_t st) {
     if (gx < 1) gx = 1;
     if (p.groups == 2) gx = (gx + 1) & ~(int64_t)1;            // a workgroup never mixes the two image groups
     dim3 grid((unsigned)gx, (unsigned)p.n_classes, (unsigned)((p.Co + NB - 1) / NB));
+    if (p.aff && p.aff_bwd) {                                  // input gradient + frozen BatchNorm / ReLU backward (afan_conv_dgrad_affine_any_nhwc_bf16)
+        if (p.Ci == 16) conv_small_kernel<1, 2><<<grid, THREADS, 0, st>>>(p);
+        else if (p.Ci == 32) conv_small_kernel<2, 2><<<grid, THREADS, 0, st>>>(p);
+        else conv_small_kernel<4, 2><<<grid, THREADS, 0, st>>>(p);
+        AFAN_LAUNCH_CHECK();
+        AFAN_TRACE_LAUNCH("small_dgrad_aff<%d>", p.Ci == 16 ? 1 : p.Ci == 32 ? 2 : 4);
+        return AFAN_OK;
+    }
     if (p.aff) {                                               // forward with a frozen BatchNorm (afan_conv_fwd_affine_any_nhwc_bf16)
-        if (p.Ci == 16) conv_small_kernel<1, true><<<grid, THREADS, 0, st>>>(p);
-        else if (p.Ci == 32) conv_small_kernel<2, true><<<grid, THREADS, 0, st>>>(p);
-        else conv_small_kernel<4, true><<<grid, THREADS, 0, st>>>(p);
+        if (p.Ci == 16) conv_small_kernel<1, 1><<<grid, THREADS, 0, st>>>(p);
+        else if (p.Ci == 32) conv_small_kernel<2, 1><<<grid, THREADS, 0, st>>>(p);
+        else conv_small_kernel<4, 1><<<grid, THREADS, 0, st>>>(p);
         AFAN_LAUNCH_CHECK();
         AFAN_TRACE_LAUNCH("small_fwd_aff<%d>", p.Ci == 16 ? 1 : p.Ci == 32 ? 2 : 4);
         return AFAN_OK;
     }
-    if (p.Ci == 16) conv_small_kernel<1, false><<<grid, THREADS, 0, st>>>(p);
-    else if (p.Ci == 32) conv_small_kernel<2, false><<<grid, THREADS, 0, st>>>(p);
-    else conv_small_kernel<4, false><<<grid, THREADS, 0, st>>>(p);
+    if (p.Ci == 16) conv_small_kernel<1, 0><<<grid, THREADS, 0, st>>>(p);
+    else if (p.Ci == 32) conv_small_kernel<2, 0><<<grid, THREADS, 0, st>>>(p);
+    else conv_small_kernel<4, 0><<<grid, THREADS, 0, st>>>(p);
     AFAN_LAUNCH_CHECK();
     AFAN_TRACE_LAUNCH("small_%s<%d>", afan::trace::op() == afan::trace::DGRAD ? "dgrad" : "fwd", p.Ci == 16 ? 1 : p.Ci == 32 ? 2 : 4);
     return AFAN_OK;

@@ -12,7 +12,10 @@ by one afan_affine_apply.
 The forward reads only buffers the Evaluator owns (bf16 weight copies, [4][C] coefficient blocks, the head's parameters),
 rewritten in place by refresh() at the start of every evaluation pass, so one hipGraph per batch shape — captured on the
 shape's second pass, forward + criterion + accuracy — serves every epoch.  fp32, NCHW, or a criterion other than a default
-nn.CrossEntropyLoss: the model's own eager forward."""
+nn.CrossEntropyLoss: the model's own eager forward.
+
+Attacker (below) is its counterpart for robust accuracy: image-space PGD on the eval-mode model, forward and backward one launch per
+convolution, the whole attack one hipGraph per batch shape."""
 import torch
 import torch.nn as nn
 
@@ -237,6 +240,193 @@ class Evaluator:
         if self._pool is None:
             self._pool = graph.pool()
         self._graphs[key] = (graph, sx, sy, out, loss, prec)
+
+
+class Attacker:
+    """Image-space L-inf PGD on the model in eval mode — the robust-accuracy counterpart of Evaluator, whose private weight
+    copies and coefficient blocks it shares (refresh() rewrites both).  attack(inp, target) -> (x_adv, loss_adv, prec_adv) on the
+    device.  The schedule is seg_attack_algo.adv_input's (Segmentation/attack_algo.py:86-105): start at the clean image (plus
+    (2u - 1) * eps with u drawn by the HOST's default generator when randinit), `steps` times x_adv += gamma * sign(d loss / d x_adv)
+    projected onto the eps-ball around the clean image (ops.pgd_step_(clip=True)), then one clamp to [0, 1]; loss_adv / prec_adv are
+    the criterion and top-1 precision of the model on x_adv.  eps and gamma are in pixel units ([0, 1] images).
+
+    bf16 channels-last BasicBlock ResNets (ResNet-20s / -56s / -18) run fused: the forward is Evaluator's (one launch per convolution)
+    with its activations kept, the backward one launch per convolution where a kernel has the form — the input gradient with the
+    frozen BatchNorm + ReLU backward it runs into in its epilogue (ops.conv_dgrad_affine(any_kernel=True)), ops.conv_dgrad_dual where a
+    residual joins, the two launches they stand for elsewhere — then the stem's input gradient on the general kernel, the
+    normalisation's 1 / std and the sign step.  The whole attack (steps x (forward, loss, backward, step), the clamp, the final
+    forward, loss and accuracy) is ONE hipGraph per batch shape, captured on the shape's second sight; nothing synchronises with the
+    host.  Everything else (fp32, NCHW, another criterion, Bottleneck networks) runs attack_eager(): the same schedule through the
+    model's own eval-mode autograd (resnet_s._BNEvalFn), which the fused path equals bit for bit."""
+
+    def __init__(self, model, criterion, eps, gamma, steps, randinit=False):
+        self.model, self.criterion = model, criterion
+        self.eps, self.gamma, self.steps, self.randinit = float(eps), float(gamma), int(steps), bool(randinit)
+        self.ev = evaluator_for(model, criterion)
+        ev = self.ev
+        self.fused = bool(ev.fused and not ev.pre and not ev.stem.stem7 and ev.stem.relu
+                          and all(isinstance(blk, resnet_s.BasicBlock) for blk, _, _ in ev.blocks))
+        self._graphs, self._seen, self._eager_shapes = {}, {}, set()
+        self._pool = None
+        self.inv_std = None
+
+    def refresh(self):
+        """Evaluator.refresh() plus the backward's operands: the transposed weight copies and 1 / std, rewritten in place."""
+        self.ev.refresh()
+        if not self.fused:
+            return
+        with torch.no_grad():
+            for c in self.ev.convs[1:]:                 # (the stem's input gradient reads the untransposed weight)
+                wt = c.w.permute(1, 0, 2, 3)
+                if getattr(c, "wt", None) is None or c.wt.shape != wt.shape:
+                    c.wt = torch.empty(wt.shape, dtype=wt.dtype, device=wt.device, memory_format=torch.channels_last)
+                c.wt.copy_(wt)
+            inv = (1.0 / self.ev.std.float()).contiguous()          # resnet_s._NormalizeFn's expression
+            if self.inv_std is None:
+                self.inv_std = inv
+            else:
+                self.inv_std.copy_(inv)
+
+    # ------------------------------------------------------------------------------------------ fused passes
+    def _forward(self, x):
+        """Evaluator._forward with the activations the backward needs."""
+        ev = self.ev
+        xn = ops.normalize_nchw(x.contiguous().float(), ev.mean, ev.std, torch.bfloat16, True)
+        h = ev.stem(xn)
+        tape = []
+        for blk, chain, sc in ev.blocks:
+            a1 = chain[0](h)
+            if sc is not None:
+                res = sc(h)
+            elif blk._sc_kind == "pad":
+                res = blk.shortcut(h).contiguous(memory_format=torch.channels_last)
+            else:
+                res = h
+            out = chain[1](a1, res)
+            tape.append((h, a1, out))
+            h = out
+        xh = resnet_s._head_in(h)
+        if not resnet_s._head_ok(xh, ev.lin):
+            raise _Unfused
+        logits, pooled = ops.head_forward(xh, ev.lin_w, ev.lin_b)
+        return logits, (xn, tape, xh, pooled)
+
+    def _backward(self, dlogits, saved):
+        """d loss / d image (fp32 NCHW) from d loss / d logits: the eval-mode autograd graph's launches, fused where a kernel has the form."""
+        ev = self.ev
+        xn, tape, xh, pooled = saved
+        g = ops.head_backward(dlogits, ev.lin_w, pooled, xh, True)
+        pend = None                     # (gradient entering the block's last convolution's output, the shortcut's share)
+        for bi in range(len(ev.blocks) - 1, -1, -1):
+            blk, (c1, c2), sc = ev.blocks[bi]
+            xin, a1, out = tape[bi]
+            d_raw2, dres = pend if pend is not None else ops.affine_relu_backward(g, out, c2.coefs[2], True, True, True)
+            d_raw1 = ops.conv_dgrad_affine(d_raw2, c2.wt, a1.shape[2:], c2.stride, c1.coefs[2], a1, any_kernel=True)
+            if d_raw1 is None:
+                d_raw1, _ = ops.affine_relu_backward(ops.conv_dgrad(d_raw2, c2.wt, a1.shape[2:], c2.stride), a1, c1.coefs[2], True)
+            if sc is not None:          # projection shortcut: its BatchNorm (no ReLU), then its 1x1 input gradient
+                d_sc, _ = ops.affine_relu_backward(dres, None, sc.coefs[2], False)
+                add = ops.conv_dgrad(d_sc, sc.wt, xin.shape[2:], sc.stride)
+            elif blk._sc_kind == "pad":  # option A: the middle channels of the share land on the even pixels
+                pad = blk.shortcut.pad
+                add = torch.zeros_like(xin)
+                add[:, :, ::2, ::2] = dres[:, pad:pad + xin.shape[1]]
+            else:
+                add = dres
+            # the two branches' sum at the block input, then the producer's (previous block's last / the stem's) BatchNorm + ReLU backward
+            alpha = (ev.blocks[bi - 1][1][-1] if bi else ev.stem).coefs[2]
+            pend = ops.conv_dgrad_dual(d_raw1, c1.wt, xin.shape[2:], c1.stride, add, alpha, xin)
+            if pend is None:
+                gin = ops.conv_dgrad(d_raw1, c1.wt, xin.shape[2:], c1.stride, addend=add)
+                pend = ops.affine_relu_backward(gin, xin, alpha, True, True, bi > 0)
+        st = ev.stem
+        gx = ops.conv_general_dgrad(pend[0], st.w, xn.shape[2:], st.stride, int(st.conv.padding[0]), 1)
+        return ops.affine_relu_backward(gx.float().contiguous(), None, self.inv_std, False)[0]
+
+    def _start(self, x, u):
+        x_adv = x.clone()
+        if self.randinit:
+            ops.axpy_noise_(x_adv, u, self.eps)
+        return x_adv
+
+    def _finish(self, x_adv):
+        ops.tensor_clamp_(x_adv, torch.zeros_like(x_adv), torch.ones_like(x_adv))
+
+    def _fused_attack(self, x, target, u):
+        x_adv = self._start(x, u)
+        for _ in range(self.steps):
+            logits, saved = self._forward(x_adv)
+            _, dlogits = ops.cross_entropy(logits, target)
+            ops.pgd_step_(x_adv, self._backward(dlogits, saved), self.gamma, x, self.eps, True)
+        self._finish(x_adv)
+        out = self.ev._forward(x_adv)
+        return x_adv, self.criterion(out, target).float(), accuracy(out.float(), target)
+
+    # ------------------------------------------------------------------------------------------- eager path
+    def attack_eager(self, inp, target, u=None):
+        """The same schedule through the model's own eval-mode forward and autograd (any dtype, layout and criterion)."""
+        m = self.model
+        x = inp.detach().float().contiguous()
+        if self.randinit and u is None:
+            u = torch.rand(x.shape).to(x.device, non_blocking=True)
+        x_adv = self._start(x, u)
+        crit = resnet_s.fused_criterion(self.criterion, m)
+        for _ in range(self.steps):
+            xin = x_adv.detach().requires_grad_(True)
+            with torch.enable_grad(), resnet_s.dgrad_only():
+                loss = crit(m(xin, end_point=m.layer_number, start_point=0), target)
+                root = ops.one(loss.device) if (loss.dim() == 0 and loss.dtype == torch.float32) else None
+                grad = torch.autograd.grad(loss, xin, grad_outputs=root, only_inputs=True)[0]
+            ops.pgd_step_(x_adv, grad.float().contiguous(), self.gamma, x, self.eps, True)
+        self._finish(x_adv)
+        with torch.no_grad():
+            out = m(x_adv, end_point=m.layer_number, start_point=0)
+            return x_adv, self.criterion(out, target).float(), accuracy(out.float(), target)
+
+    # ---------------------------------------------------------------------------------------------- attack
+    def attack(self, inp, target):
+        if self.model.training:
+            raise ValueError("Attacker.attack: the model must be in eval mode (model.eval())")
+        if inp.dim() != 4 or not inp.is_cuda:
+            raise ops.AfanLibraryError("Attacker.attack: images [N, 3, H, W] on the MI355X")
+        x = inp.detach().float().contiguous()
+        # the host draws the random start (the reference's attack_algo.py:44), whichever path runs
+        u = torch.rand(x.shape).to(x.device, non_blocking=True) if self.randinit else None
+        if not self.fused or tuple(x.shape) in self._eager_shapes:
+            return self.attack_eager(x, target, u)
+        with torch.no_grad():
+            key = (tuple(x.shape), tuple(target.shape), target.dtype)
+            g = self._graphs.get(key)
+            if g is not None:
+                graph, sx, sy, su, x_adv, loss, prec = g
+                sx.copy_(x)
+                sy.copy_(target)
+                if su is not None:
+                    su.copy_(u)
+                graph.replay()
+                return x_adv.clone(), loss.clone(), prec.clone()
+            try:
+                r = self._fused_attack(x, target, u)
+            except _Unfused:
+                self._eager_shapes.add(tuple(x.shape))
+                return self.attack_eager(x, target, u)
+            self._seen[key] = self._seen.get(key, 0) + 1
+            if self._seen[key] >= 2:            # (as Evaluator: a shape that recurs gets its graph, its first pass was the warm-up)
+                self._capture(key, x, target, u)
+            return r
+
+    def _capture(self, key, x, target, u):
+        dev = x.device
+        sx, sy, su = x.clone(), target.clone(), (u.clone() if u is not None else None)
+        stream = torch.cuda.Stream(device=dev)
+        stream.wait_stream(torch.cuda.current_stream(dev))
+        graph = torch.cuda.CUDAGraph()
+        with ops.no_gc_during_capture(), torch.cuda.graph(graph, pool=self._pool, stream=stream, capture_error_mode="thread_local"):
+            x_adv, loss, prec = self._fused_attack(sx, sy, su)
+        torch.cuda.current_stream(dev).wait_stream(stream)
+        if self._pool is None:
+            self._pool = graph.pool()
+        self._graphs[key] = (graph, sx, sy, su, x_adv, loss, prec)
 
 
 def evaluator_for(model, criterion):

@@ -1,6 +1,9 @@
 """Checkpoint evaluation entry point — same flags, defaults and stdout lines as the reference's Classification/main_inference.py
 (flags :28-32, main :38-53, validate :57-96), so `bash cmd/run_test.sh` works.  Additions (all optional): --arch, --dtype,
---layout, --synthetic.
+--layout, --synthetic, and robust accuracy: --attack_steps N (> 0: after the clean pass, an N-step L-inf PGD on every test image
+through the eval-mode model, infer.Attacker; `Robust:` lines in the format of the `Test:` lines and a final `robust_accuracy` line),
+--attack_eps, --attack_gamma (radius and step size in /255 pixel units), --attack_randinit.  --attack_steps 0 (the default) is the
+clean evaluation alone, its output unchanged.
 
 The checkpoint's `state_dict` is a main_perturb.py checkpoint's or one in the reference's layout (the same keys).  The
 CIFAR-10 test split is evaluated in file order with its last partial batch; the evaluation is main_perturb.validate
@@ -16,9 +19,9 @@ if __package__ in (None, ""):  # executed as a script (cmd/run_test.sh): import 
     import importlib
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     _pkg = importlib.import_module("cv_a-fan_amd")
-    resnet_s, main_perturb = _pkg.resnet_s, importlib.import_module("cv_a-fan_amd.main_perturb")
+    resnet_s, infer, main_perturb = _pkg.resnet_s, _pkg.infer, importlib.import_module("cv_a-fan_amd.main_perturb")
 else:
-    from . import main_perturb, resnet_s
+    from . import infer, main_perturb, resnet_s
 
 parser = argparse.ArgumentParser(description="A-FAN CIFAR-10 checkpoint evaluation on MI355X")
 # ---- base setting (main_inference.py:28-32)
@@ -33,11 +36,48 @@ parser.add_argument("--dtype", default="bf16", choices=["bf16", "fp32"], help="b
 parser.add_argument("--layout", default="nhwc", choices=["nhwc", "nchw"],
                     help="internal activation / weight layout (nhwc: the library's MFMA convolutions; nchw: the general fp32-arithmetic kernels)")
 parser.add_argument("--synthetic", type=int, default=0, help="evaluate on N synthetic images instead of the CIFAR-10 test split")
+# ---- robust accuracy (image-space L-inf PGD on the eval-mode model)
+parser.add_argument("--attack_steps", type=int, default=0, help="PGD steps of the robust-accuracy pass (0: clean evaluation only)")
+parser.add_argument("--attack_eps", type=float, default=8.0, help="L-inf radius of the attack, in /255 pixel units")
+parser.add_argument("--attack_gamma", type=float, default=2.0, help="PGD step size, in /255 pixel units")
+parser.add_argument("--attack_randinit", action="store_true", help="start the attack at a uniform random point of the eps-ball")
+
+
+def robust_validate(val_loader, model, criterion, args, log):
+    """The robust counterpart of main_perturb.validate: every batch attacked (infer.Attacker), the adversarial loss and precision
+    kept on the device and read back at --print_freq batches and at the end, in batch order."""
+    losses, top1 = main_perturb.AverageMeter(), main_perturb.AverageMeter()
+    model.eval()
+    at = infer.Attacker(model, criterion, args.attack_eps / 255.0, args.attack_gamma / 255.0, args.attack_steps, args.attack_randinit)
+    at.refresh()
+    pending = []
+
+    def flush():
+        for loss_t, prec_t, n in pending:
+            losses.update(loss_t.item(), n)
+            top1.update(prec_t.item(), n)
+        pending.clear()
+
+    for i, (inp, target) in enumerate(val_loader):
+        _, loss, prec = at.attack(inp, target)
+        pending.append((loss, prec, inp.size(0)))
+        if i % args.print_freq == 0:
+            flush()
+            log("Robust: [{0}/{1}]\t"
+                "Loss {loss.val:.4f} ({loss.avg:.4f})\t"
+                "Accuracy {top1.val:.3f} ({top1.avg:.3f})".format(i, len(val_loader), loss=losses, top1=top1))
+    flush()
+    log("robust_accuracy {top1.avg:.3f}".format(top1=top1))
+    return top1.avg, losses.avg
 
 
 def main(argv=None):
     args = parser.parse_args(argv)
-    print(args, flush=True)
+    if args.attack_steps < 0:
+        parser.error("--attack_steps must be >= 0")
+    # (without an attack the printed namespace is the clean evaluation's own: the attack flags are not part of it)
+    shown = args if args.attack_steps else argparse.Namespace(**{k: v for k, v in vars(args).items() if not k.startswith("attack_")})
+    print(shown, flush=True)
     if not torch.cuda.is_available():
         raise RuntimeError("main_inference.py needs an MI355X: this build has no CPU path (oracle/ is test infrastructure)")
     torch.cuda.set_device(int(args.gpu))
@@ -67,6 +107,8 @@ def main(argv=None):
         print(*a, flush=True)
 
     main_perturb.validate(loader, model, criterion, args, log)
+    if args.attack_steps:
+        robust_validate(loader, model, criterion, args, log)
 
 
 if __name__ == "__main__":

@@ -1682,20 +1682,31 @@ def maxpool2d_backward(dy, idx, in_shape, k, stride, pad=0, x=None, channels_las
     return dx
 
 
-def conv_dgrad_affine(dy, wt, in_hw, stride, alpha, act):
-    """dx = bf16((act > 0 ? bf16(dgrad(dy, wt)) : 0) * alpha[c]) in ONE launch (afan_conv_dgrad_affine_nhwc_bf16): an input gradient
-    with the backward of the frozen BatchNorm + ReLU it runs into.  None where another kernel owns the shape (the caller issues
-    conv_dgrad + affine_relu_backward: the same bits)."""
+def conv_dgrad_affine(dy, wt, in_hw, stride, alpha, act, any_kernel=False):
+    """dx = bf16((act > 0 ? bf16(dgrad(dy, wt)) : 0) * alpha[c]) in ONE launch: an input gradient with the backward of the frozen
+    BatchNorm + ReLU it runs into.  any_kernel=False (afan_conv_dgrad_affine_nhwc_bf16): the tiled kernel's shapes; None where another
+    kernel owns the shape (the caller issues conv_dgrad + affine_relu_backward: the same bits).  any_kernel=True
+    (afan_conv_dgrad_affine_any_nhwc_bf16, the eval backward of infer.py): every input-gradient family of conv_dgrad (tiled,
+    small-channel, 64 -> 64 weights-in-registers), alpha 16-byte aligned; act=None (no ReLU mask: bf16(bf16(dgrad) * alpha[c])) on
+    the latter two; None where no kernel takes the problem."""
     lib = _lib.load()
-    _cl4(dy, "dy"), _cl4(wt, "wt"), _cl4(act, "act")
+    _cl4(dy, "dy"), _cl4(wt, "wt")
+    if act is not None:
+        _cl4(act, "act")
+    elif not any_kernel:
+        raise ValueError("conv_dgrad_affine: the ReLU mask `act` is optional only with any_kernel=True")
+    _need(alpha, "alpha", torch.float32)
     n, co, ho, wo = dy.shape
     ci, _, k, _ = wt.shape
     hi, wi = in_hw
+    if alpha.numel() != ci or (act is not None and tuple(act.shape) != (n, ci, hi, wi)):
+        raise ValueError("conv_dgrad_affine: alpha [Ci] and act of dx's shape")
     dx = torch.empty((n, ci, hi, wi), dtype=torch.bfloat16, device=dy.device, memory_format=torch.channels_last)
-    rc = lib.afan_conv_dgrad_affine_nhwc_bf16(_ptr(dy), _ptr(wt), _ptr(dx), n, hi, wi, ci, co, k, int(stride), _ptr(alpha), _ptr(act), _stream(dy))
+    name = "afan_conv_dgrad_affine_any_nhwc_bf16" if any_kernel else "afan_conv_dgrad_affine_nhwc_bf16"
+    rc = getattr(lib, name)(_ptr(dy), _ptr(wt), _ptr(dx), n, hi, wi, ci, co, k, int(stride), _ptr(alpha), _ptr(act), _stream(dy))
     if rc == -3:
         return None
-    check(rc, "afan_conv_dgrad_affine_nhwc_bf16")
+    check(rc, name)
     CALLS["conv_dgrad"] += 1
     return dx
 

@@ -214,9 +214,9 @@ class _ConvFn(torch.autograd.Function):
         st, pad, dil = ctx.stride[0], ctx.padding[0], ctx.dilation[0]
         own = ctx.own and gy.is_contiguous(memory_format=torch.channels_last)
         if need_gx:
-            if own:
+            if own and x.shape[1] != 3:
                 gx = ops.conv_dgrad(gy, ctx.wt_fn(), x.shape[2:], st, dilation=dil)
-            else:
+            else:      # (also the gradient that reaches the image through the 3-channel stem: no tuned input-gradient kernel has 3 channels)
                 gx = ops.conv_general_dgrad(gy, w_lp, x.shape[2:], st, pad, dil)
         if need_gw:
             w_master = ctx.w_master
@@ -509,6 +509,34 @@ class _BNTrainFn(torch.autograd.Function):
         if direct:
             dw = db = None
         return dx, dw, db, dres, None, None, None, None, None, None, None, None, None
+
+
+class _BNEvalFn(torch.autograd.Function):
+    """y = [relu](bn_eval(x) [+ residual]) with the running statistics, a frozen affine: the forward is BatchNorm2d.fused's no-gradient
+    call (afan_bn_apply, the same values), the backward afan_affine_relu_bwd with alpha = weight * invstd — the gradient to x and
+    the residual's share.  The BatchNorm's parameters and buffers are read from the module: no parameter gradients in eval mode."""
+
+    @staticmethod
+    def forward(ctx, x, residual, bn, relu):
+        invstd = torch.rsqrt(bn.running_var + bn.eps)
+        x = _dense(x)
+        y = ops.bn_apply(x, bn.running_mean, invstd, bn.weight, bn.bias, None if residual is None else _like_layout(residual, x), relu)
+        ctx.alpha = ops.affine_coefs(bn.running_mean, invstd, bn.weight, bn.bias)[2]
+        ctx.relu, ctx.has_res = relu, residual is not None
+        ctx.save_for_backward(y)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        (y,) = ctx.saved_tensors
+        gy = _like_layout(gy, y)
+        if gy.dtype != y.dtype:
+            gy = gy.to(y.dtype)
+        want_dres = ctx.has_res and ctx.needs_input_grad[1]
+        if not (ctx.needs_input_grad[0] or want_dres):
+            return None, None, None, None
+        dx, dres = ops.affine_relu_backward(gy, y, ctx.alpha, ctx.relu, want_dx=ctx.needs_input_grad[0], want_dres=want_dres)
+        return dx, dres, None, None
 
 
 class _BlockFn(torch.autograd.Function):
@@ -965,10 +993,10 @@ class BatchNorm2d(nn.BatchNorm2d):
                 raise ValueError("grouped BatchNorm statistics: the batch must split into equal half-batches on the GPU")
             return _BNTrainFn.apply(x, self.weight, self.bias, residual, relu, self.eps, mom, self.running_mean,
                                     self.running_var, self.num_batches_tracked, _Flags.param_grads, conv_stats, G)
-        if torch.is_grad_enabled() and (x.requires_grad or self.weight.requires_grad and _Flags.param_grads):
-            if x.requires_grad:
-                raise NotImplementedError("eval-mode BatchNorm backward is not on the A-FAN path (the reference "
-                                          "runs PGD and the joint step in train mode, main_perturb.py:159)")
+        if torch.is_grad_enabled() and (x.requires_grad or (residual is not None and residual.requires_grad)):
+            # an input gradient through a trained classifier (attack_algo.PGD on model.eval(), infer.Attacker's eager path): the
+            # frozen affine as an autograd node; the parameters get no gradient in eval mode
+            return _BNEvalFn.apply(x, residual, self, relu)
         with torch.no_grad():
             invstd = torch.rsqrt(self.running_var + self.eps)
             x = _dense(x)

@@ -302,6 +302,13 @@ int afan_conv_dgrad_nhwc_bf16(const void* dy, const void* wt, void* dx, int64_t 
  * afan_conv_dgrad_nhwc_bf16 followed by afan_affine_relu_bwd(relu = 1).  AFAN_ESHAPE where another kernel owns the shape. */
 int afan_conv_dgrad_affine_nhwc_bf16(const void* dy, const void* wt, void* dx, int64_t n, int64_t hi, int64_t wi, int64_t ci, int64_t co,
                                      int k, int stride, const float* alpha, const void* act, afan_stream_t stream);
+/* afan_conv_dgrad_affine_any_nhwc_bf16 — the same, on every input-gradient family of afan_conv_dgrad_nhwc_bf16 at dilation 1
+ * (Classification's eval-mode backward): the tiled kernel, the small-channel kernel and the 64 -> 64 weights-in-registers kernel,
+ * the latter two in instantiations of their own.  There act may be NULL (no ReLU mask: dx = bf16(bf16(dgrad(dy)) * alpha[c]),
+ * afan_affine_relu_bwd(relu = 0)) and alpha is 16-byte aligned; the tiled kernel answers AFAN_ESHAPE without act.  AFAN_ESHAPE where no
+ * input-gradient kernel takes the shape. */
+int afan_conv_dgrad_affine_any_nhwc_bf16(const void* dy, const void* wt, void* dx, int64_t n, int64_t hi, int64_t wi, int64_t ci,
+                                         int64_t co, int k, int stride, const float* alpha, const void* act, afan_stream_t stream);
 /* The gradient arriving at the OUTPUT of a frozen-BatchNorm residual block with that block's first backward step applied on the way
  * out: g = bf16(bf16(dgrad(dy)) + addend) (addend optional), m = act > 0 ? g : 0, dres = m, d3 = bf16(m * alpha[c]) — bit for bit
  * afan_conv_dgrad_nhwc_bf16(addend) followed by afan_affine_relu_bwd(relu = 1) with both outputs (Detection/backbone/
