@@ -4,7 +4,7 @@ The directory name carries a hyphen (it is fixed by the build contract), so impo
     import importlib; afan = importlib.import_module("cv_a-fan_amd")
 Sub-modules: attack_algo (PGD & friends, reference signatures), resnet_s (slice-protocol models),
 arena (flat parameter arena + fused SGD), train_step (the joint step, data parallel), ops (tensor
-wrappers over the C-ABI in include/afan_hip.h), main_perturb (entry point for cmd/run_perturb.sh), infer (the fused, graph-replayed eval forward; main_inference evaluates a checkpoint), deeplab (the
+wrappers over the C-ABI in include/afan_hip.h), main_perturb (entry point for cmd/run_perturb.sh; DeviceLoader: one-launch batches), main_base (the baseline trainer, cmd/run_base.sh), infer (the fused, graph-replayed eval forward; main_inference evaluates a checkpoint), deeplab (the
 DeepLabv3+ split-forward network), seg_attack_algo / seg_trainer (the Segmentation A-FAN operators and iteration), det_ops / det_attack_algo / det_model / det_trainer
 (the Detection operators, iteration, the Faster-RCNN / ResNet-101 model and its data-parallel trainer).
 """

@@ -22,9 +22,9 @@ if __package__ in (None, ""):  # executed as a script (cmd/run_perturb.sh): impo
     import importlib
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     _pkg = importlib.import_module("cv_a-fan_amd")
-    resnet_s, train_step, host, infer = _pkg.resnet_s, _pkg.train_step, _pkg.host, _pkg.infer
+    resnet_s, train_step, host, infer, ops = _pkg.resnet_s, _pkg.train_step, _pkg.host, _pkg.infer, _pkg.ops
 else:
-    from . import host, infer, resnet_s, train_step
+    from . import host, infer, ops, resnet_s, train_step
 
 parser = argparse.ArgumentParser(description="A-FAN CIFAR-10 training on MI355X")
 # ---- base setting (main_perturb.py:28-33)
@@ -105,14 +105,34 @@ def _load_cifar10(root):
     return (x[:45000], y[:45000]), (x[45000:], y[45000:]), _load_cifar10_test(root)
 
 
+def _augment_torch(x_u8, top=None, left=None, flip=None, pad=4):
+    """dataset.py:36-39 on a gathered uint8 batch [m, c, h, w] as a chain of torch calls: RandomCrop(h, padding=pad) at offsets
+    (top, left) in [0, 2*pad], RandomHorizontalFlip where flip, ToTensor's /255.  The draws are the caller's.  DeviceLoader's path on a
+    device without the library's kernels, and what tests hold ops.batch_crop_flip to, bit for bit.  top is None: scale only."""
+    x = x_u8
+    if top is not None:
+        m, _, h, w = x.shape
+        dev = x.device
+        xp = torch.nn.functional.pad(x, (pad, pad, pad, pad))                     # [m, c, h + 2 pad, w + 2 pad]
+        rows = top[:, None] + torch.arange(h, device=dev)[None, :]
+        cols = left[:, None] + torch.arange(w, device=dev)[None, :]
+        cols = torch.where(flip[:, None], cols.flip(1), cols)
+        bi = torch.arange(m, device=dev)[:, None, None]
+        x = xp[bi, :, rows[:, :, None], cols[:, None, :]].permute(0, 3, 1, 2).contiguous()
+    return x.float().div_(255.0)
+
+
 class DeviceLoader:
     """Whole split resident in HBM as uint8 (CIFAR-10 train = 138 MB of 288 GB); per batch: shuffle index, random
-    crop (pad 4) + horizontal flip (dataset.py:36-39) and the /255 ToTensor scaling run on the device."""
+    crop (pad 4) + horizontal flip (dataset.py:36-39) and the /255 ToTensor scaling run on the device — on a GPU as ONE launch
+    (ops.batch_crop_flip: gather, crop, flip, scale and the labels), fed by three draws on the device generator; the epoch's
+    permutation is uploaded once."""
 
-    def __init__(self, x_u8, y, batch, device, train, rank=0, world=1, drop_last=True, seed=None):
-        self.x = torch.as_tensor(x_u8).to(device)
-        self.y = torch.as_tensor(y).to(device)
+    def __init__(self, x_u8, y, batch, device, train, rank=0, world=1, drop_last=True, seed=None, pad=4):
+        self.x = torch.as_tensor(x_u8).to(device).contiguous()
+        self.y = torch.as_tensor(y).to(device).contiguous()
         self.batch, self.train, self.rank, self.world, self.device = batch, train, rank, world, device
+        self.pad = int(pad)
         # data parallel: every rank must slice the SAME permutation (its own CPU generator would give overlapping shards):
         # a generator seeded with (seed + epoch), `seed` agreed on by all ranks (main() broadcasts rank 0's draw)
         self.seed, self.epoch = seed, 0
@@ -134,22 +154,28 @@ class DeviceLoader:
         else:
             perm = torch.randperm(n)                                  # CPU generator, like DataLoader's sampler
         per = self.batch // self.world
+        idxs = []
         for b in range(self.n_batches):
             idx = perm[b * self.batch:(b + 1) * self.batch]
-            idx = idx[self.rank * per:(self.rank + 1) * per] if self.world > 1 else idx
-            idx = idx.to(self.device)
-            x, y = self.x[idx], self.y[idx]
+            idxs.append(idx[self.rank * per:(self.rank + 1) * per] if self.world > 1 else idx)
+        on_gpu = torch.device(self.device).type == "cuda"
+        if on_gpu and idxs:
+            # one upload per epoch: this rank's index list of every batch, back to back
+            every = torch.cat(idxs).to(self.device)
+            ends = torch.tensor([i.shape[0] for i in idxs]).cumsum(0).tolist()
+            idxs = [every[e - i.shape[0]:e] for i, e in zip(idxs, ends)]
+        for idx in idxs:
+            m = idx.shape[0]
+            top = left = flip = None
             if self.train:
-                m = x.shape[0]
-                xp = torch.nn.functional.pad(x, (4, 4, 4, 4))                         # [m, 3, 40, 40]
-                ar = torch.arange(32, device=self.device)
-                rows = torch.randint(0, 9, (m,), device=self.device)[:, None] + ar[None, :]
-                cols = torch.randint(0, 9, (m,), device=self.device)[:, None] + ar[None, :]
+                top = torch.randint(0, 2 * self.pad + 1, (m,), device=self.device)
+                left = torch.randint(0, 2 * self.pad + 1, (m,), device=self.device)
                 flip = torch.rand(m, device=self.device) < 0.5
-                cols = torch.where(flip[:, None], cols.flip(1), cols)
-                bi = torch.arange(m, device=self.device)[:, None, None]
-                x = xp[bi, :, rows[:, :, None], cols[:, None, :]].permute(0, 3, 1, 2).contiguous()
-            yield x.float().div_(255.0), y
+            if on_gpu:
+                yield ops.batch_crop_flip(self.x, idx, top, left, flip, labels=self.y, pad=self.pad if self.train else 0)
+            else:
+                idx = idx.to(self.device)
+                yield _augment_torch(self.x[idx], top, left, flip, self.pad), self.y[idx]
 
 
 class SyntheticLoader:

@@ -233,59 +233,31 @@ def _out_shape(mod, c, h, w):
     return c, h, w
 
 
-class AfanTrainer(GuardedTrainer):
-    """Owns the arena, the optimizer and the per-step schedule of one rank.
+class StepTrainer(GuardedTrainer):
+    """What the trainers of one rank share, whatever their iteration body: the parameter arena and its fused SGD (learning rate in
+    device memory), the gradient exchange (GradAllReducer, or NullReducer for the data-parallel program on one GPU), the grid-barrier
+    guard, and the eager-then-captured schedule — `graph_warmup` eager iterations, then one capture per input shape, replayed from
+    then on; a failed capture falls back to eager launches with a warning.  A subclass provides _step_eager, _capture and
+    _step_graph."""
+    _what = "the step"
 
-    use_graph=True (default): after `graph_warmup` eager iterations the whole iteration body — head forward, K PGD
-    steps, both final forwards, backward and (single GPU) the SGD step, ~1300 launches — is captured once into a
-    hipGraph and replayed from then on: static shapes, the learning rate in device memory and on-device metrics make
-    the step capturable, and replay removes the host launch cost that otherwise bounds the step (PyTorch's eager
-    dispatch + autograd tape is ~15 us per launch).  With world_size > 1 the graph stops after the backward and the
-    gradient all-reduce + SGD run eagerly.  randinit draws on the host generator every step, so it stays eager."""
-
-    def __init__(self, model, criterion, *, steps=5, gamma=0.5, eps=2.0, perturb_idx=13, layer_number=None,
-                 randinit=False, clip=False, lr=0.1, momentum=0.9, weight_decay=5e-4, allreduce_chunks=4,
-                 group=None, use_graph=True, graph_warmup=3, batch_final=True,
-                 share_head=True, fold_clean=None, segmented=None, dual_bn=False, emulate_dp=False):
+    def _init_state(self, model, criterion, lr, momentum, weight_decay, allreduce_chunks, group, emulate_dp):
         self.model, self.criterion = model, criterion
-        # dual-BN option (off = the reference's single BatchNorm set): adversarial features — every PGD pass and the
-        # adversarial final pass — are normalised by an auxiliary BatchNorm set.  The first PGD pass is then no longer the
-        # clean pass and the two final passes no longer share their affine parameters: no fold, no grouped final pass.
-        self.dual_bn = bool(dual_bn)
-        if self.dual_bn:
-            from . import resnet_s
-            resnet_s.enable_dual_bn(model)
-            fold_clean, batch_final = False, False
-        self.steps, self.gamma, self.eps = steps, gamma, eps
-        self.perturb_idx = perturb_idx
-        self.layer_number = layer_number if layer_number is not None else model.layer_number
-        self.randinit, self.clip = randinit, clip
         self.arena = ParamArena(model)
         self.optimizer = ArenaSGD(self.arena, lr, momentum, weight_decay)
         self.group = group
         self.world = dist.get_world_size(group) if dist.is_initialized() else 1
         self.reducer = GradAllReducer(self.arena, allreduce_chunks, group) if self.world > 1 else None
-        if self.world > 1:
-            self.optimizer.grad_scale = 1.0 / self.world
-            self.sync_replicas()
-        elif emulate_dp:
+        if self.world <= 1 and emulate_dp:
             self.reducer = NullReducer(self.arena)      # one GPU, the data-parallel program (see NullReducer)
         # a grid barrier of the in-launch BatchNorm that gives up: detected every step without a host synchronisation, no update
         # applied meanwhile (the optimizer's device-side guard), the lost steps run again on the two-launch forms (grid_guard.py)
         self._guard_init(model, self.arena.param.device)
-        import os
-        # exchange the tail's gradients stage by stage while the rest of the backward runs (folded schedule); 0: one
-        # blocking all-reduce after the backward (A/B, and the fallback if a piece-wise capture fails)
-        self.ddp_overlap = self.reducer is not None and os.environ.get("AFAN_DDP_OVERLAP", "1") != "0"
-        self.segmented = bool(segmented)          # True: run the segmented (piece-wise) step on one GPU too (tests)
-        self._pieces = None
-        self.batch_final = bool(batch_final)      # adv + clean final passes as one grouped pass over the tail
-        self._groupable_key, self._groupable = None, False
-        self.share_head = bool(share_head)
-        self.fold_clean = fold_clean if fold_clean is None else bool(fold_clean)
-        self._fold_auto = {}
-        self.use_graph = bool(use_graph) and not randinit
+
+    def _init_graph(self, use_graph, graph_warmup):
+        self.use_graph = bool(use_graph)
         self.graph_warmup = graph_warmup
+        self._pieces = None
         self._graph = None
         self._graph_failed = None
         self._graph_unsafe = None
@@ -307,6 +279,94 @@ class AfanTrainer(GuardedTrainer):
         for b in self.model.buffers():
             dist.broadcast(b, src=src, group=self.group)
         a.refresh_shadow()
+
+    def _graph_safe(self):
+        """Every configuration runs on the library's own kernels (tuned bf16 or general f32 MFMA) and is capturable; a
+        convolution that left the library would be listed by resnet_s.vendor_convs (empty by construction) and keep the
+        step eager: rounds 1-2 measured a captured vendor input-gradient pass reading memory the graph did not own."""
+        if self._graph_unsafe is None:
+            from . import resnet_s
+            self._graph_unsafe = resnet_s.vendor_convs(self.model) if hasattr(self.model, "sequential_model") else []
+            if self._graph_unsafe:
+                self.use_graph = False
+        return not self._graph_unsafe
+
+    def _pre_sgd(self):
+        """Data parallel: the grid barrier's error word becomes the maximum over the ranks before the (device-guarded) optimizer
+        launch reads it — every rank skips the same updates (grid_guard.GridGuard.sync_ranks)."""
+        if self._guard is not None and self.world > 1:
+            self._guard.sync_ranks(self.group)
+
+    def _drop_graphs(self):
+        """After a grid barrier gave up: the captured graphs hold in-launch-BatchNorm launches; capture again (two-launch forms)."""
+        self._graph = self._pieces = self._static_in = self._static_out = self._shape_key = None
+        self._graph_failed = None
+
+    def step(self, inp, target):
+        """One iteration.  Returns device tensors only (see the subclass); no host synchronisation."""
+        return self._guarded((inp, target), self._step_once)
+
+    def _step_once(self, inp, target):
+        if self._graph is not None and self._shape_key == (tuple(inp.shape), inp.dtype, tuple(target.shape)):
+            return self._step_graph(inp, target)
+        if (self.use_graph and self._graph is None and self._graph_failed is None
+                and self._eager_steps >= self.graph_warmup and inp.is_cuda and self.model.training
+                and self._graph_safe()):
+            try:
+                self._capture(inp, target)
+                return self._step_graph(inp, target)
+            except Exception as e:  # noqa: BLE001 — stay correct: fall back to eager launches, loudly
+                import warnings
+                self._graph, self._graph_failed = None, e
+                warnings.warn(f"hipGraph capture of {self._what} failed ({type(e).__name__}: {e}); running eagerly")
+                torch.cuda.synchronize()
+        self._eager_steps += 1
+        return self._step_eager(inp, target)
+
+
+class AfanTrainer(StepTrainer):
+    """Owns the arena, the optimizer and the per-step schedule of one rank.
+
+    use_graph=True (default): after `graph_warmup` eager iterations the whole iteration body — head forward, K PGD
+    steps, both final forwards, backward and (single GPU) the SGD step, ~1300 launches — is captured once into a
+    hipGraph and replayed from then on: static shapes, the learning rate in device memory and on-device metrics make
+    the step capturable, and replay removes the host launch cost that otherwise bounds the step (PyTorch's eager
+    dispatch + autograd tape is ~15 us per launch).  With world_size > 1 the graph stops after the backward and the
+    gradient all-reduce + SGD run eagerly.  randinit draws on the host generator every step, so it stays eager."""
+    _what = "the A-FAN step"
+
+    def __init__(self, model, criterion, *, steps=5, gamma=0.5, eps=2.0, perturb_idx=13, layer_number=None,
+                 randinit=False, clip=False, lr=0.1, momentum=0.9, weight_decay=5e-4, allreduce_chunks=4,
+                 group=None, use_graph=True, graph_warmup=3, batch_final=True,
+                 share_head=True, fold_clean=None, segmented=None, dual_bn=False, emulate_dp=False):
+        self.model, self.criterion = model, criterion
+        # dual-BN option (off = the reference's single BatchNorm set): adversarial features — every PGD pass and the
+        # adversarial final pass — are normalised by an auxiliary BatchNorm set.  The first PGD pass is then no longer the
+        # clean pass and the two final passes no longer share their affine parameters: no fold, no grouped final pass.
+        self.dual_bn = bool(dual_bn)
+        if self.dual_bn:
+            from . import resnet_s
+            resnet_s.enable_dual_bn(model)
+            fold_clean, batch_final = False, False
+        self.steps, self.gamma, self.eps = steps, gamma, eps
+        self.perturb_idx = perturb_idx
+        self.layer_number = layer_number if layer_number is not None else model.layer_number
+        self.randinit, self.clip = randinit, clip
+        self._init_state(model, criterion, lr, momentum, weight_decay, allreduce_chunks, group, emulate_dp)
+        if self.world > 1:
+            self.optimizer.grad_scale = 1.0 / self.world
+            self.sync_replicas()
+        import os
+        # exchange the tail's gradients stage by stage while the rest of the backward runs (folded schedule); 0: one
+        # blocking all-reduce after the backward (A/B, and the fallback if a piece-wise capture fails)
+        self.ddp_overlap = self.reducer is not None and os.environ.get("AFAN_DDP_OVERLAP", "1") != "0"
+        self.segmented = bool(segmented)          # True: run the segmented (piece-wise) step on one GPU too (tests)
+        self.batch_final = bool(batch_final)      # adv + clean final passes as one grouped pass over the tail
+        self._groupable_key, self._groupable = None, False
+        self.share_head = bool(share_head)
+        self.fold_clean = fold_clean if fold_clean is None else bool(fold_clean)
+        self._fold_auto = {}
+        self._init_graph(bool(use_graph) and not randinit, graph_warmup)
 
     # ------------------------------------------------------------------------------------------------ body
     FOLD_MIN_ELEMS = 0            # feature-map elements (batch x C x H x W) from which fold_clean=None folds (0: always)
@@ -589,17 +649,6 @@ class AfanTrainer(GuardedTrainer):
         self._groupable_key, self._groupable = key, bool(ok)
         return self._groupable
 
-    def _graph_safe(self):
-        """Every configuration runs on the library's own kernels (tuned bf16 or general f32 MFMA) and is capturable; a
-        convolution that left the library would be listed by resnet_s.vendor_convs (empty by construction) and keep the
-        step eager: rounds 1-2 measured a captured vendor input-gradient pass reading memory the graph did not own."""
-        if self._graph_unsafe is None:
-            from . import resnet_s
-            self._graph_unsafe = resnet_s.vendor_convs(self.model) if hasattr(self.model, "sequential_model") else []
-            if self._graph_unsafe:
-                self.use_graph = False
-        return not self._graph_unsafe
-
     def _step_eager(self, inp, target):
         self.optimizer._sync_lr()
         if self._ddp_phases_ok(inp):
@@ -620,17 +669,6 @@ class AfanTrainer(GuardedTrainer):
         self._pre_sgd()
         self.optimizer.step()
         return out
-
-    def _pre_sgd(self):
-        """Data parallel: the grid barrier's error word becomes the maximum over the ranks before the (device-guarded) optimizer
-        launch reads it — every rank skips the same updates (grid_guard.GridGuard.sync_ranks)."""
-        if self._guard is not None and self.world > 1:
-            self._guard.sync_ranks(self.group)
-
-    def _drop_graphs(self):
-        """After a grid barrier gave up: the captured graphs hold in-launch-BatchNorm launches; capture again (two-launch forms)."""
-        self._graph = self._pieces = self._static_in = self._static_out = self._shape_key = None
-        self._graph_failed = None
 
     # ----------------------------------------------------------------------------------------------- graph
     def _capture_pieces(self, inp, target):
@@ -713,19 +751,80 @@ class AfanTrainer(GuardedTrainer):
         feature_map, out_clean — in graph mode these three are views of graph-owned buffers, valid until the next step)."""
         return self._guarded((inp, target), self._step_once)
 
-    def _step_once(self, inp, target):
-        if self._graph is not None and self._shape_key == (tuple(inp.shape), inp.dtype, tuple(target.shape)):
-            return self._step_graph(inp, target)
-        if (self.use_graph and self._graph is None and self._graph_failed is None
-                and self._eager_steps >= self.graph_warmup and inp.is_cuda and self.model.training
-                and self._graph_safe()):
-            try:
-                self._capture(inp, target)
-                return self._step_graph(inp, target)
-            except Exception as e:  # noqa: BLE001 — stay correct: fall back to eager launches, loudly
-                import warnings
-                self._graph, self._graph_failed = None, e
-                warnings.warn(f"hipGraph capture of the A-FAN step failed ({type(e).__name__}: {e}); running eagerly")
-                torch.cuda.synchronize()
-        self._eager_steps += 1
-        return self._step_eager(inp, target)
+
+class BaseTrainer(StepTrainer):
+    """The baseline iteration (Classification/main_base.py:157-162) on AfanTrainer's parts: one train-mode forward of the whole
+    network (every BatchNorm updates its running statistics once), the criterion, zero_grad, backward, one fused SGD launch.
+    The in-launch convolution + BatchNorm forms and the block fusions apply as in AfanTrainer's passes — the layers are the same.
+
+    use_graph=True (default): after `graph_warmup` eager iterations the iteration is captured once per input shape and replayed.
+    Data parallel (or emulate_dp=True, the same program on one GPU): the graph ends after the backward; one blocking all-reduce of the
+    gradient arena, the ranks' agreement on the barrier error word and the guarded SGD launch follow eagerly.  Nothing is launched
+    between the exchange's start and its end, so no grid barrier can meet it.
+
+    step(inp, target) returns device tensors only: loss, prec1, out_clean (in graph mode a view of a graph-owned buffer, valid
+    until the next step)."""
+    _what = "the baseline step"
+
+    def __init__(self, model, criterion, *, lr=0.1, momentum=0.9, weight_decay=5e-4, allreduce_chunks=4, group=None,
+                 use_graph=True, graph_warmup=3, emulate_dp=False):
+        self._init_state(model, criterion, lr, momentum, weight_decay, allreduce_chunks, group, emulate_dp)
+        if self.world > 1:
+            self.optimizer.grad_scale = 1.0 / self.world        # the all-reduce is a plain SUM
+            self.sync_replicas()
+        self.layer_number = model.layer_number
+        self._init_graph(use_graph, graph_warmup)
+
+    def _forward_backward(self, inp, target):
+        from . import resnet_s
+        m = self.model
+        if inp.is_cuda:
+            ops.acc_reset(inp.device)   # BatchNorm accumulator arena: one memset per step, blocks are bump-allocated
+        output_clean = m(inp, end_point=self.layer_number, start_point=0)        # main_base.py:157
+        crit = resnet_s.fused_criterion(self.criterion, m)
+        loss = crit(output_clean.contiguous() if output_clean.dim() == 2 else output_clean, target)
+        self.optimizer.zero_grad()
+        if loss.is_cuda and loss.dtype == torch.float32 and loss.dim() == 0:
+            loss.backward(gradient=ops.one(loss.device))
+        else:
+            loss.backward()
+        with torch.no_grad():
+            prec1 = (output_clean.argmax(dim=1) == target).float().sum() * (100.0 / target.shape[0])
+        return {"loss": loss.detach(), "prec1": prec1, "out_clean": output_clean.detach()}
+
+    def _exchange_and_update(self):
+        if self.reducer is not None:
+            self.reducer.begin(explicit=True)
+            self.reducer.launch_params(0, len(self.arena.params))        # the whole arena, one message
+            self.reducer.finish()
+        self._pre_sgd()
+        self.optimizer.step()
+
+    def _step_eager(self, inp, target):
+        self.optimizer._sync_lr()
+        out = self._forward_backward(inp, target)
+        self._exchange_and_update()
+        return out
+
+    def _capture(self, inp, target):
+        dev = inp.device
+        self._stream = torch.cuda.Stream(device=dev)
+        self._static_in = (inp.clone(), target.clone())
+        self._stream.wait_stream(torch.cuda.current_stream(dev))
+        g = torch.cuda.CUDAGraph()
+        with ops.no_gc_during_capture(), torch.cuda.graph(g, stream=self._stream, capture_error_mode="thread_local"):
+            out = self._forward_backward(self._static_in[0], self._static_in[1])
+            if self.reducer is None:
+                self.optimizer.step()
+        self._graph, self._static_out = g, out
+        self._shape_key = (tuple(inp.shape), inp.dtype, tuple(target.shape))
+
+    def _step_graph(self, inp, target):
+        self._static_in[0].copy_(inp, non_blocking=True)
+        self._static_in[1].copy_(target, non_blocking=True)
+        self.optimizer._sync_lr()          # lr lives in device memory: the graph reads it, the host only writes it here
+        self._graph.replay()
+        if self.reducer is not None:
+            self._exchange_and_update()
+        # graph-owned outputs are overwritten by the next replay: hand out copies of the small ones
+        return {k: (v.clone() if k in ("loss", "prec1") else v) for k, v in self._static_out.items()}

@@ -770,6 +770,21 @@ int afan_pgd_init(const void* x, int dtype, float* x32, float* x_adv, uint16_t* 
 int afan_normalize_nchw(const float* x, void* y, int out_dtype, int out_layout, int64_t n, int64_t c, int64_t hw,
                         const float* mean, const float* std, afan_stream_t stream);
 
+/* One augmented training batch in one launch — Classification/dataset.py:36-39 (RandomCrop(h, padding=pad), RandomHorizontalFlip,
+ * ToTensor) over a split resident in device memory.  src: uint8 NCHW [n_src, c, h, w]; out: fp32 NCHW [m, c, h, w].  For output pixel
+ * (b, ch, i, j): jj = flip[b] ? w-1-j : j, r = i + top[b] - pad, s = jj + left[b] - pad, out = src[index[b], ch, r, s] / 255, or 0 where
+ * (r, s) lies outside the image.  The scaling is bit-equal to x.float().div_(255.0) ON THE DEVICE, which multiplies by the fp32
+ * reciprocal: fl(v * fl(1/255)), from a 256-entry table computed at compile time (126 byte values are one ulp off fl(v / 255.0f)).  top / left lie in [0, 2*pad].  labels_out[b] = labels_src[index[b]] in the same launch (both NULL:
+ * no labels).  top, left and flip all NULL: a plain gather and scale (the evaluation path).
+ * An index outside [0, n_src) is CLAMPED into it by the kernel (top / left likewise into [0, 2*pad]): no value of the index arrays
+ * makes the launch read outside src.
+ * Errors: a negative size or pad, or n_src == 0 with m > 0, AFAN_ESHAPE; src / index / out NULL with m > 0, exactly one label pointer
+ * NULL, or a proper subset of top / left / flip NULL, AFAN_ENULL; m == 0 returns 0 without a launch. */
+int afan_batch_crop_flip_u8(const uint8_t* src, const int64_t* labels_src, int64_t n_src,
+                            const int64_t* index, const int64_t* top, const int64_t* left, const uint8_t* flip,
+                            float* out, int64_t* labels_out,
+                            int64_t m, int64_t c, int64_t h, int64_t w, int pad, afan_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Measurement aid (no reference counterpart): per-launch HIP-event timing of the kernels above, recorded
  * on the launch stream.  afan_profile_enable(1) starts recording (launches are then not graph-capturable),
