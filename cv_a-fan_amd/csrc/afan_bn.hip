@@ -166,7 +166,9 @@ __device__ __forceinline__ void write_stats(const Moments& m, int c, float eps, 
     mean[c] = m.mean;
     invstd[c] = 1.0f / sqrtf(var_b + eps);
     if (rmean) {
-        const float var_u = m.m2 / (m.n - 1.0f);  // torch uses the unbiased estimate for running_var
+        // torch uses the unbiased estimate for running_var; one element per channel: 0 / 0 otherwise, guarded as the
+        // accumulator path guards its M / (M - 1)
+        const float var_u = m.m2 / (m.n > 1.0f ? m.n - 1.0f : 1.0f);
         rmean[c] = (1.0f - momentum) * rmean[c] + momentum * m.mean;
         rvar[c] = (1.0f - momentum) * rvar[c] + momentum * var_u;
     }

@@ -266,7 +266,8 @@ __global__ __launch_bounds__(BLOCK) void finalize_kernel(const float* __restrict
         if (rmean)
             for (int u = 0; u < updates; ++u) {    // updates > 1: this pass stands for that many identical train-mode passes
                 rmean[c] = (1.0f - momentum) * rmean[c] + momentum * mean;
-                rvar[c] = (1.0f - momentum) * rvar[c] + momentum * (m2 / (m_count - 1.0f));
+                // (one row: 0 / 0 otherwise — the accumulator path and afan_bn_running_update guard their M / (M - 1) the same way)
+                rvar[c] = (1.0f - momentum) * rvar[c] + momentum * (m2 / (m_count > 1.0f ? m_count - 1.0f : 1.0f));
             }
         if (c == 0 && nbt) *nbt += updates;
     } else {
