@@ -1,0 +1,306 @@
+// The segmentation training batch in one launch (gfx950): gather from a resident, variably sized uint8 split + Pillow's bilinear
+// (image) and nearest (label) resize + pad_if_needed + crop + horizontal flip + /255.
+// Reference behaviour: Segmentation/args.py:113-121 (ExtRandomScale((0.5, 2.0)), ExtRandomCrop(513, pad_if_needed=True),
+// ExtRandomHorizontalFlip, ExtToTensor) applied per image by two DataLoader workers on PIL images; the validation transforms
+// (:123-136: ExtResize + ExtCenterCrop, or the image as it is) are the same function with other parameters.  The draws are the
+// caller's (seg_data.SegDeviceLoader); the kernel is a pure function of them.
+//
+// What is reproduced bit for bit (seg_data._augment_numpy restates it; tests/golden/seg_aug_pillow.npz holds Pillow's own output):
+//   * bilinear: Pillow's separable 8-bit resampler — triangle filter of support max(in/out, 1) around (x + 0.5) * in/out, double
+//     coefficients summed left to right and normalised, int(+-0.5 + k * 2^22), accumulator 2^21, >> 22, clip; the HORIZONTAL pass
+//     first, ROUNDED TO uint8, then the vertical pass.  A pass whose size does not change is the identity (one tap of 2^22).
+//   * nearest: Pillow's ACCUMULATED source coordinate, xo = a/2; tab[x] = int(xo); xo += a — a serial double sum, not
+//     int((x + 0.5) * a), which lands on other pixels.
+//   * pad_if_needed (ext_transforms.py:383-390): width short -> ALL FOUR sides by p1, then the padded height short -> all four
+//     again by p2; fill 0 for the image and for the label.
+//   * ToTensor on the CPU: the correctly rounded quotient fl(v / 255) (not afan_data.hip's device product).
+#include "afan_common.h"
+
+#include <limits.h>
+
+using namespace afan;
+
+// the coefficient and coordinate arithmetic below must round operation by operation: 0.5 + k * 2^22 as an fma rounds differently
+#pragma clang fp contract(off)
+
+namespace {
+constexpr int BLOCK = 256;
+constexpr int TW = 128;              // tile: TH output rows x TW output columns per workgroup
+constexpr int TH = 16;
+constexpr int KMAX = 8;              // taps per axis: ceil(in/out) * 2 + 1 <= 7 for in/out <= 3
+constexpr int PREC = 22;             // Pillow's PRECISION_BITS (32 - 8 - 2)
+constexpr int MAX_SIDE = 1 << 15;    // a resized side is clamped to this (the reference's largest is 2 x 500)
+constexpr double MAX_SHRINK = 3.0;
+
+// ToTensor's scaling as the CPU computes it, torch.from_numpy(u8).float().div(255): a true fp32 division, correctly rounded.
+struct Quot255 {
+    float v[256];
+    constexpr Quot255() : v() {
+        for (int i = 0; i < 256; ++i) v[i] = (float)i / 255.0f;
+    }
+};
+__constant__ Quot255 kQuot255 = Quot255();
+
+__device__ __forceinline__ int clip8(int acc) {
+    const int v = acc >> PREC;
+    return v < 0 ? 0 : (v > 255 ? 255 : v);
+}
+
+// Pillow's precompute_coeffs + normalize_coeffs_8bpc for ONE output coordinate x of a resize in -> out (bilinear: support 1).
+__device__ void bilinear_taps(int x, int in, int out, int& xmin_o, int& n_o, int (&coef)[KMAX]) {
+#pragma unroll
+    for (int u = 0; u < KMAX; ++u) coef[u] = 0;
+    if (in == out) {                       // the pass is skipped: identity
+        xmin_o = x;
+        n_o = 1;
+        coef[0] = 1 << PREC;
+        return;
+    }
+    const double scale = (double)in / (double)out;
+    const double fs = scale < 1.0 ? 1.0 : scale;
+    const double support = 1.0 * fs;
+    const double center = (x + 0.5) * scale;
+    const double ss = 1.0 / fs;
+    int xmin = (int)(center - support + 0.5);
+    if (xmin < 0) xmin = 0;
+    int xmax = (int)(center + support + 0.5);
+    if (xmax > in) xmax = in;
+    int n = xmax - xmin;
+    n = n < 0 ? 0 : (n > KMAX ? KMAX : n);
+    double k[KMAX];
+    double ww = 0.0;
+#pragma unroll
+    for (int u = 0; u < KMAX; ++u) {
+        double w = 0.0;
+        if (u < n) {
+            double t = ((u + xmin) - center + 0.5) * ss;
+            if (t < 0.0) t = -t;
+            w = t < 1.0 ? 1.0 - t : 0.0;
+            ww += w;
+        }
+        k[u] = w;
+    }
+#pragma unroll
+    for (int u = 0; u < KMAX; ++u) {
+        if (u < n) {
+            double v = k[u];
+            if (ww != 0.0) v /= ww;
+            coef[u] = v < 0.0 ? (int)(-0.5 + v * (double)(1 << PREC)) : (int)(0.5 + v * (double)(1 << PREC));
+        }
+    }
+    xmin_o = xmin;
+    n_o = n;
+}
+
+// One workgroup = one TH x TW tile of ONE sample's output.  Its tables live in LDS: per tile column the horizontal taps (first
+// source column, count, KMAX coefficients) and the nearest source column; per tile row the same vertically.  Waves 0-1 build the
+// column taps, wave 2 the row taps and then the rows' nearest table, one lane of wave 3 the columns' nearest table (the serial
+// accumulated sums, up to the tile's last coordinate).  A count of -1 marks a row / column of the padding.
+// An item is 4 consecutive columns of one output row (VEC, out_w % 4 == 0: 16-byte stores) or one pixel.
+template <bool VEC>
+__global__ __launch_bounds__(BLOCK) void seg_batch_aug_kernel(
+    const uint8_t* __restrict__ images, const int64_t* __restrict__ img_off, const uint8_t* __restrict__ labels,
+    const int32_t* __restrict__ hs, const int32_t* __restrict__ ws, int64_t n_src, int64_t total_pixels,
+    const int64_t* __restrict__ index, const int64_t* __restrict__ p_oh, const int64_t* __restrict__ p_ow,
+    const int64_t* __restrict__ p_top, const int64_t* __restrict__ p_left, const int64_t* __restrict__ p_flip,
+    float* __restrict__ out, int64_t* __restrict__ labels_out, int out_h, int out_w, double max_shrink, int tiles_x, int tiles_y) {
+    __shared__ int s_cmin[TW], s_cn[TW], s_ccoef[KMAX][TW], s_ncol[TW];
+    __shared__ int s_rmin[TH], s_rn[TH], s_rcoef[KMAX][TH], s_nrow[TH];
+    __shared__ float s_quot[256];
+    static_assert(BLOCK == 256 && TW + TH <= 192, "thread roles below");
+    const int tid = threadIdx.x;
+    const int tx = blockIdx.x % tiles_x;
+    const int ty = (blockIdx.x / tiles_x) % tiles_y;
+    const int64_t b = blockIdx.x / (tiles_x * tiles_y);
+    const int i0 = ty * TH, j0 = tx * TW;
+
+    // ---- the sample's parameters, clamped (uniform over the workgroup)
+    int64_t k = index[b];
+    k = k < 0 ? 0 : (k >= n_src ? n_src - 1 : k);
+    int h = hs[k], w = ws[k];
+    const int64_t off = img_off[k];
+    int64_t base = off / 3;                                       // the image's first pixel in the packed split
+    // never read outside the split, whatever the tables say: an entry that does not fit gives an all-padding sample
+    const bool valid = h >= 1 && w >= 1 && h <= MAX_SIDE && w <= MAX_SIDE && off >= 0 && base + (int64_t)h * w <= total_pixels;
+    if (!valid) { h = 1; w = 1; base = 0; }
+    int lo_h = (int)ceil((double)h / max_shrink), lo_w = (int)ceil((double)w / max_shrink);
+    lo_h = lo_h < 1 ? 1 : lo_h;
+    lo_w = lo_w < 1 ? 1 : lo_w;
+    int64_t v = p_oh[b];
+    const int oh = (int)(v < lo_h ? lo_h : (v > MAX_SIDE ? MAX_SIDE : v));
+    v = p_ow[b];
+    const int ow = (int)(v < lo_w ? lo_w : (v > MAX_SIDE ? MAX_SIDE : v));
+    const int p1 = ow < out_w ? (1 + out_w - ow) / 2 : 0;         // ext_transforms.py:383-385
+    const int ph1 = oh + 2 * p1;
+    const int p2 = ph1 < out_h ? (1 + out_h - ph1) / 2 : 0;       // :388-390, on the already padded height
+    const int P = p1 + p2;
+    const int ph = oh + 2 * P, pw = ow + 2 * P;                   // (>= out_h, out_w)
+    v = p_top[b];
+    const int top = (int)(v < 0 ? 0 : (v > ph - out_h ? ph - out_h : v));
+    v = p_left[b];
+    const int left = (int)(v < 0 ? 0 : (v > pw - out_w ? pw - out_w : v));
+    const bool fl = p_flip[b] != 0;
+
+    // ---- tables
+    s_quot[tid] = kQuot255.v[tid];
+    if (tid < TW) {
+        const int j = j0 + tid;
+        const int jj = fl ? out_w - 1 - j : j;
+        const int c = left + jj - P;
+        int xmin = 0, n = -1, coef[KMAX];
+#pragma unroll
+        for (int u = 0; u < KMAX; ++u) coef[u] = 0;
+        if (j < out_w && c >= 0 && c < ow && valid) bilinear_taps(c, w, ow, xmin, n, coef);
+        s_cmin[tid] = xmin;
+        s_cn[tid] = n;
+#pragma unroll
+        for (int u = 0; u < KMAX; ++u) s_ccoef[u][tid] = coef[u];
+    } else if (tid < TW + TH) {
+        const int t = tid - TW;
+        const int r = top + i0 + t - P;
+        int xmin = 0, n = -1, coef[KMAX];
+#pragma unroll
+        for (int u = 0; u < KMAX; ++u) coef[u] = 0;
+        if (i0 + t < out_h && r >= 0 && r < oh && valid) bilinear_taps(r, h, oh, xmin, n, coef);
+        s_rmin[t] = xmin;
+        s_rn[t] = n;
+#pragma unroll
+        for (int u = 0; u < KMAX; ++u) s_rcoef[u][t] = coef[u];
+    }
+    if (tid == TW + TH) {                                         // (wave 2) rows: Pillow's accumulated nearest coordinate
+        for (int t = 0; t < TH; ++t) s_nrow[t] = 0;
+        const int r_first = top + i0 - P;                         // tile row t <-> resized row r_first + t
+        int r_last = r_first + TH - 1;
+        r_last = r_last > oh - 1 ? oh - 1 : r_last;
+        const double a = (double)h / (double)oh;
+        double xo = a * 0.5;
+        for (int r = 0; r <= r_last; ++r) {
+            if (r >= r_first) {
+                int s = (int)xo;
+                s_nrow[r - r_first] = s > h - 1 ? h - 1 : s;
+            }
+            xo += a;
+        }
+    }
+    if (tid == 192) {                                             // (wave 3) columns
+        for (int t = 0; t < TW; ++t) s_ncol[t] = 0;
+        // tile column t <-> resized column c = left + (fl ? out_w - 1 - (j0 + t) : j0 + t) - P
+        const int ca = left + (fl ? out_w - 1 - j0 : j0) - P;     // t = 0
+        const int cb = fl ? ca - (TW - 1) : ca + (TW - 1);        // t = TW - 1
+        const int c_first = ca < cb ? ca : cb;
+        int c_last = ca < cb ? cb : ca;
+        c_last = c_last > ow - 1 ? ow - 1 : c_last;
+        const double a = (double)w / (double)ow;
+        double xo = a * 0.5;
+        for (int c = 0; c <= c_last; ++c) {
+            if (c >= c_first) {
+                int s = (int)xo;
+                s_ncol[fl ? ca - c : c - ca] = s > w - 1 ? w - 1 : s;
+            }
+            xo += a;
+        }
+    }
+    __syncthreads();
+
+    // ---- pixels
+    const uint8_t* __restrict__ img = images + 3 * base;
+    const uint8_t* __restrict__ lab = labels + base;
+    const int64_t plane = (int64_t)out_h * out_w;
+    float* __restrict__ dst = out + b * 3 * plane;
+    int64_t* __restrict__ ldst = labels_out + b * plane;
+    constexpr int E = VEC ? 4 : 1;
+    constexpr int WQ = TW / E;
+    for (int it = tid; it < TH * WQ; it += BLOCK) {
+        const int ti = it / WQ;
+        const int tq = it - ti * WQ;
+        const int i = i0 + ti;
+        const int jq = j0 + tq * E;
+        if (i >= out_h || jq >= out_w) continue;                  // (VEC: out_w % 4 == 0, so the 4 columns are in or out together)
+        const int rn = s_rn[ti], rmin = s_rmin[ti], nr = s_nrow[ti];
+        float px[3][E];
+        int64_t lb[E];
+#pragma unroll
+        for (int e = 0; e < E; ++e) {
+            const int tj = tq * E + e;
+            const int cn = s_cn[tj], cmin = s_cmin[tj];
+            if (rn < 0 || cn < 0) {                               // padding: 0 for the image AND the label
+                px[0][e] = px[1][e] = px[2][e] = 0.f;
+                lb[e] = 0;
+                continue;
+            }
+            int a0 = 1 << (PREC - 1), a1 = a0, a2 = a0;
+            for (int vv = 0; vv < rn; ++vv) {
+                const uint8_t* __restrict__ sp = img + ((int64_t)(rmin + vv) * w + cmin) * 3;
+                int h0 = 1 << (PREC - 1), h1 = h0, h2 = h0;
+                for (int u = 0; u < cn; ++u) {
+                    const int cc = s_ccoef[u][tj];
+                    h0 += (int)sp[3 * u] * cc;
+                    h1 += (int)sp[3 * u + 1] * cc;
+                    h2 += (int)sp[3 * u + 2] * cc;
+                }
+                const int cv = s_rcoef[vv][ti];
+                a0 += clip8(h0) * cv;                             // the horizontal pass is rounded to uint8 before the vertical one
+                a1 += clip8(h1) * cv;
+                a2 += clip8(h2) * cv;
+            }
+            px[0][e] = s_quot[clip8(a0)];
+            px[1][e] = s_quot[clip8(a1)];
+            px[2][e] = s_quot[clip8(a2)];
+            lb[e] = (int64_t)lab[(int64_t)nr * w + s_ncol[tj]];
+        }
+        const int64_t o = (int64_t)i * out_w + jq;
+        if (VEC) {
+#pragma unroll
+            for (int ch = 0; ch < 3; ++ch) {
+                const float t4[4] = {px[ch][0], px[ch][E > 1 ? 1 : 0], px[ch][E > 2 ? 2 : 0], px[ch][E > 3 ? 3 : 0]};
+                Elt<float>::stv(dst + ch * plane + o, t4);
+            }
+            typedef int64_t i64x2 __attribute__((ext_vector_type(2)));
+            const i64x2 l01 = {lb[0], lb[E > 1 ? 1 : 0]}, l23 = {lb[E > 2 ? 2 : 0], lb[E > 3 ? 3 : 0]};
+            *reinterpret_cast<i64x2*>(ldst + o) = l01;
+            *reinterpret_cast<i64x2*>(ldst + o + 2) = l23;
+        } else {
+            dst[o] = px[0][0];
+            dst[plane + o] = px[1][0];
+            dst[2 * plane + o] = px[2][0];
+            ldst[o] = lb[0];
+        }
+    }
+}
+}  // namespace
+
+extern "C" int afan_seg_batch_aug_u8(const uint8_t* images, const int64_t* img_off, const uint8_t* labels, const int32_t* hs,
+                                     const int32_t* ws, int64_t n_src, int64_t total_pixels, const int64_t* index,
+                                     const int64_t* oh, const int64_t* ow, const int64_t* top, const int64_t* left,
+                                     const int64_t* flip, float* out, int64_t* labels_out, int64_t m, int64_t out_h,
+                                     int64_t out_w, double max_shrink, afan_stream_t stream) {
+    if (m < 0 || out_h < 0 || out_w < 0 || n_src < 0 || total_pixels < 0) return AFAN_ESHAPE;
+    if (out_h > (1 << 20) || out_w > (1 << 20)) return AFAN_ESHAPE;
+    if (!(max_shrink >= 1.0) || max_shrink > MAX_SHRINK) return AFAN_ESHAPE;   // more than KMAX taps per axis (NaN included)
+    const int64_t plane = out_h * out_w;
+    if (plane > INT_MAX || (plane > 0 && m > (INT64_MAX / 8) / (3 * plane))) return AFAN_ESHAPE;
+    if (m == 0 || plane == 0) return AFAN_OK;
+    if (!images || !img_off || !labels || !hs || !ws || !index || !oh || !ow || !top || !left || !flip || !out || !labels_out)
+        return AFAN_ENULL;
+    if (n_src == 0 || total_pixels == 0) return AFAN_ESHAPE;      // a non-empty batch cannot be gathered from an empty split
+    if (!aligned(out, 4) || !aligned(labels_out, 8) || !aligned(img_off, 8) || !aligned(hs, 4) || !aligned(ws, 4) ||
+        !aligned(index, 8) || !aligned(oh, 8) || !aligned(ow, 8) || !aligned(top, 8) || !aligned(left, 8) || !aligned(flip, 8))
+        return AFAN_EALIGN;
+    const int64_t tiles_x = (out_w + TW - 1) / TW, tiles_y = (out_h + TH - 1) / TH;
+    if (tiles_x * tiles_y > INT_MAX / m) return AFAN_ESHAPE;
+    const bool vec = (out_w % 4 == 0) && aligned(out, 16) && aligned(labels_out, 16);
+    hipStream_t st = (hipStream_t)stream;
+    // algorithmic bytes per output pixel: 12 (image) + 8 (label) written, ~3 + 1 source bytes read
+    AFAN_PROF("seg_batch_aug_kernel", (double)m * (double)plane * 24.0, st);
+    const dim3 grid((unsigned)(m * tiles_x * tiles_y));
+    if (vec)
+        seg_batch_aug_kernel<true><<<grid, BLOCK, 0, st>>>(images, img_off, labels, hs, ws, n_src, total_pixels, index, oh, ow, top, left,
+                                                          flip, out, labels_out, (int)out_h, (int)out_w, max_shrink, (int)tiles_x,
+                                                          (int)tiles_y);
+    else
+        seg_batch_aug_kernel<false><<<grid, BLOCK, 0, st>>>(images, img_off, labels, hs, ws, n_src, total_pixels, index, oh, ow, top,
+                                                           left, flip, out, labels_out, (int)out_h, (int)out_w, max_shrink, (int)tiles_x,
+                                                           (int)tiles_y);
+    AFAN_LAUNCH_CHECK();
+    return AFAN_OK;
+}

@@ -20,7 +20,7 @@ _tls = threading.local()
 # "conv_general" counts passes of the fp32-arithmetic general kernels, afan_conv_f32.hip)
 class _Calls(dict):
     """The convolution counters are the dict's own items: what the logs and the tests enumerate (`dict(CALLS)`, `set(CALLS)`).
-    Counters of launches outside the convolution path (`batch_crop_flip`: the loader's kernel) live in `.other` and are read and
+    Counters of launches outside the convolution path (`batch_crop_flip`, `seg_batch_aug`: the loaders' kernels) live in `.other` and are read and
     written through the same subscript, `in` and `.get`, so that the enumerated table stays the convolution table
     (tests/test_host_logic.py::test_no_convolution_leaves_the_library pins `set(CALLS)` to the six convolution counters)."""
 
@@ -45,7 +45,7 @@ class _Calls(dict):
 
 
 CALLS = _Calls({"conv_fwd": 0, "conv_dgrad": 0, "conv_wgrad": 0, "conv_general": 0, "vendor_conv": 0, "conv_bn_fused": 0},
-               {"batch_crop_flip": 0})
+               {"batch_crop_flip": 0, "seg_batch_aug": 0})
 
 
 def _need(t, name, dtype=None):
@@ -2043,6 +2043,37 @@ def batch_crop_flip(src, index, top=None, left=None, flip=None, labels=None, pad
     check(lib.afan_batch_crop_flip_u8(_ptr(src), _ptr(labels), n, _ptr(index), _ptr(top), _ptr(left), _ptr(flip), _ptr(out),
                                       _ptr(labels_out), m, c, h, w, int(pad), _stream(src)), "afan_batch_crop_flip_u8")
     CALLS["batch_crop_flip"] += 1
+    return out, labels_out
+
+
+def seg_batch_aug(images, offsets, labels, hs, ws, index, oh, ow, top, left, flip, out_h, out_w, max_shrink=3.0):
+    """One segmentation batch from a resident split of variably sized images in one launch (afan_seg_batch_aug_u8): Pillow's bilinear
+    (image) / nearest (label) resize of images[index[b]] to (oh[b], ow[b]), the reference's pad_if_needed, the (out_h, out_w) window
+    at (top[b], left[b]) of the padded image, mirrored where flip[b], scaled by the correctly rounded v / 255.  images: packed HWC
+    uint8, labels: packed HW uint8, offsets: int64 byte offsets, hs / ws: int32; the six per-sample vectors are int64 [m] (rows of one
+    uploaded tensor will do).  Returns (fp32 [m, 3, out_h, out_w], int64 [m, out_h, out_w]).  Out-of-range parameters are clamped by the
+    kernel; max_shrink (<= 3) is the caller's bound on in/out."""
+    lib = _lib.load()
+    _need(images, "images", torch.uint8)
+    _need(labels, "labels", torch.uint8)
+    _need(offsets, "offsets", torch.int64)
+    _need(hs, "hs", torch.int32)
+    _need(ws, "ws", torch.int32)
+    per = (index, oh, ow, top, left, flip)
+    for t, name in zip(per, ("index", "oh", "ow", "top", "left", "flip")):
+        _need(t, name, torch.int64)
+    m = index.shape[0]
+    if any(t.dim() != 1 or t.shape[0] != m for t in per):
+        raise ValueError("seg_batch_aug: index, oh, ow, top, left and flip are int64 vectors with one entry per sample")
+    n = offsets.shape[0]
+    if images.dim() != 1 or labels.dim() != 1 or images.shape[0] != 3 * labels.shape[0] or hs.shape != (n,) or ws.shape != (n,):
+        raise ValueError("seg_batch_aug: images is packed HWC uint8 (3 bytes per label byte), offsets / hs / ws have one entry per image")
+    out = torch.empty((m, 3, int(out_h), int(out_w)), dtype=torch.float32, device=images.device)
+    labels_out = torch.empty((m, int(out_h), int(out_w)), dtype=torch.int64, device=images.device)
+    check(lib.afan_seg_batch_aug_u8(_ptr(images), _ptr(offsets), _ptr(labels), _ptr(hs), _ptr(ws), n, labels.shape[0], _ptr(index),
+                                    _ptr(oh), _ptr(ow), _ptr(top), _ptr(left), _ptr(flip), _ptr(out), _ptr(labels_out), m, int(out_h),
+                                    int(out_w), float(max_shrink), _stream(images)), "afan_seg_batch_aug_u8")
+    CALLS["seg_batch_aug"] += 1
     return out, labels_out
 
 

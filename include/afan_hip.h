@@ -785,6 +785,27 @@ int afan_batch_crop_flip_u8(const uint8_t* src, const int64_t* labels_src, int64
                             float* out, int64_t* labels_out,
                             int64_t m, int64_t c, int64_t h, int64_t w, int pad, afan_stream_t stream);
 
+/* One segmentation batch in one launch — Segmentation/args.py:113-136 (ExtRandomScale / ExtResize, ExtRandomCrop(pad_if_needed) /
+ * ExtCenterCrop, ExtRandomHorizontalFlip, ExtToTensor) over a split of VARIABLY SIZED images resident in device memory.
+ * Split: images packed HWC uint8 back to back, image k at byte img_off[k] (a multiple of 3) with hs[k] x ws[k] pixels; labels
+ * packed HW uint8 at pixel img_off[k] / 3; total_pixels pixels in all.  Per sample b: index[b]; the resized size (oh[b], ow[b]);
+ * the crop origin (top[b], left[b]) in the PADDED image's coordinates; flip[b] != 0 mirrors the cropped window.
+ * out: fp32 NCHW [m, 3, out_h, out_w]; labels_out: int64 [m, out_h, out_w].
+ * Image: Pillow's 8-bit bilinear resize (horizontal pass, rounded to uint8, then vertical; double coefficients, 22 fraction bits),
+ * label: Pillow's nearest resize (accumulated source coordinate).  Padding, derived by the kernel: ow < out_w pads all four sides
+ * by p1 = (1 + out_w - ow) / 2, then oh + 2 p1 < out_h pads all four again by p2; fill 0 for image and label.  Scaling: the
+ * correctly rounded fl(v / 255.0f), as torch's CPU division gives (NOT afan_batch_crop_flip_u8's device product).
+ * max_shrink in [1, 3] is the caller's bound on in/out of either axis (3 = 8 taps per axis at most): oh / ow are CLAMPED into
+ * [ceil(h / max_shrink), 32768], index into [0, n_src), top / left into the padded image; a table entry (offset, size) that does
+ * not fit into total_pixels yields an all-zero sample.  No value of the device arrays makes the launch read outside the split.
+ * Errors: a negative size, out_h or out_w above 2^20, more than INT_MAX pixels per plane, max_shrink outside [1, 3] (more taps
+ * than the kernel holds), or an empty split with m > 0: AFAN_ESHAPE; any pointer NULL with m > 0: AFAN_ENULL; m == 0 or an empty
+ * plane returns 0 without a launch. */
+int afan_seg_batch_aug_u8(const uint8_t* images, const int64_t* img_off, const uint8_t* labels, const int32_t* hs, const int32_t* ws,
+                          int64_t n_src, int64_t total_pixels, const int64_t* index, const int64_t* oh, const int64_t* ow,
+                          const int64_t* top, const int64_t* left, const int64_t* flip, float* out, int64_t* labels_out,
+                          int64_t m, int64_t out_h, int64_t out_w, double max_shrink, afan_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Measurement aid (no reference counterpart): per-launch HIP-event timing of the kernels above, recorded
  * on the launch stream.  afan_profile_enable(1) starts recording (launches are then not graph-capturable),
