@@ -1124,13 +1124,18 @@ int64_t afan_ce2d_upsampled_workspace_floats(int64_t n, int64_t c, int64_t h, in
     return 1 + (int64_t)ce2d_blocks(n * ho * wo) + tiles + tiles * UP_SW * UP_SW * c;
 }
 
+// every shape check of afan_ce2d_upsampled (host only): up-scaling, and the source window of a 16-pixel output tile fits UP_SW
+int afan_ce2d_upsampled_supported(int64_t c, int64_t h, int64_t w, int64_t ho, int64_t wo) {
+    if (h <= 0 || w <= 0 || ho < h || wo < w || ho > 0x7fffffffLL || wo > 0x7fffffffLL || c <= 0 || c > CE_MAX_C) return 0;
+    return up_window((int)h, (int)ho) <= UP_SW && up_window((int)w, (int)wo) <= UP_SW;   // (down-scaling: not this kernel)
+}
+
 int afan_ce2d_upsampled(const float* logits, const int64_t* target, int64_t n, int64_t c, int64_t h, int64_t w, int64_t ho,
                         int64_t wo, int64_t ignore_index, float grad_scale, float* workspace, float* loss, float* dlogits,
                         afan_stream_t stream) {
-    if (n <= 0 || h <= 0 || w <= 0 || ho < h || wo < w || c <= 0 || c > CE_MAX_C) return AFAN_ESHAPE;
+    if (n <= 0 || !afan_ce2d_upsampled_supported(c, h, w, ho, wo)) return AFAN_ESHAPE;
     if (!logits || !target || !workspace || !loss) return AFAN_ENULL;
     if (!aligned(logits, 4) || !aligned(target, 8) || !aligned(workspace, 4)) return AFAN_EALIGN;
-    if (up_window((int)h, (int)ho) > UP_SW || up_window((int)w, (int)wo) > UP_SW) return AFAN_ESHAPE;   // (down-scaling: not this kernel)
     hipStream_t st = (hipStream_t)stream;
     const int64_t P = n * ho * wo;
     const int Gc = ce2d_blocks(P);

@@ -1628,13 +1628,14 @@ def ce2d(logits, target, ignore_index=255, grad_scale=1.0, want_grad=True):
 
 
 def ce2d_upsampled_ok(logits, size):
-    """The fused resize + cross-entropy kernel takes channels-last fp32 logits of up to 32 classes, resized UP."""
+    """The fused resize + cross-entropy kernel takes channels-last fp32 logits of up to 32 classes, resized UP by a ratio at which
+    the source window of a 16-pixel output tile fits the kernel's (afan_ce2d_upsampled_supported: the entry point's own checks)."""
     if not (logits.is_cuda and logits.dtype == torch.float32 and logits.dim() == 4 and logits.shape[1] <= CE2D_MAX_CLASSES):
         return False
     h, w = logits.shape[2:]
     if layout_of(logits) != AFAN_NHWC and not (logits.shape[1] == 1 or h * w == 1):
         return False
-    return size[0] >= h and size[1] >= w
+    return bool(_lib.load().afan_ce2d_upsampled_supported(int(logits.shape[1]), int(h), int(w), int(size[0]), int(size[1])))
 
 
 def ce2d_upsampled(logits, target, ignore_index=255, grad_scale=1.0, want_grad=True):

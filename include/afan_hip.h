@@ -510,7 +510,11 @@ int afan_ce2d(const float* logits, const int64_t* target, int layout, int64_t n,
  * pass over 16 x 16 output tiles (+ a small gather of per-tile partials), the gradient returned at the LOW resolution:
  * dlogits [n,h,w,c] (nullable) = grad_scale * d(loss)/d(logits).  The arithmetic is afan_upsample_bilinear_fwd + afan_ce2d +
  * afan_upsample_bilinear_bwd operation for operation (sums grouped by tile: equal to rounding) without the four passes over
- * the [n,ho,wo,c] tensor.  ho >= h, wo >= w (up-scaling); deterministic; workspace: afan_ce2d_upsampled_workspace_floats(...). */
+ * the [n,ho,wo,c] tensor.  ho >= h, wo >= w (up-scaling) and the source rows / columns a 16-pixel output tile reads span at most 8
+ * (a ratio of about 2.3 or more on a map larger than one tile): afan_ce2d_upsampled_supported applies exactly the entry point's
+ * shape checks on the host (1: taken, 0: AFAN_ESHAPE - resize, then afan_ce2d).  Deterministic; workspace:
+ * afan_ce2d_upsampled_workspace_floats(...). */
+int afan_ce2d_upsampled_supported(int64_t c, int64_t h, int64_t w, int64_t ho, int64_t wo);
 int64_t afan_ce2d_upsampled_workspace_floats(int64_t n, int64_t c, int64_t h, int64_t w, int64_t ho, int64_t wo);
 int afan_ce2d_upsampled(const float* logits, const int64_t* target, int64_t n, int64_t c, int64_t h, int64_t w, int64_t ho,
                         int64_t wo, int64_t ignore_index, float grad_scale, float* workspace, float* loss, float* dlogits,

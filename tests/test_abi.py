@@ -66,6 +66,9 @@ def test_argument_errors_without_gpu(pkg):
     assert lib.afan_ce2d(p, p, 0, 1, 33, 4, 255, 1.0, p, p, None, None) == -3               # more than 32 classes
     assert lib.afan_ce2d(p, None, 0, 1, 4, 4, 255, 1.0, p, p, None, None) == -4
     assert lib.afan_ce2d_workspace_floats(513 * 513) == 1 + 2 * 1029
+    assert lib.afan_ce2d_upsampled_supported(21, 129, 129, 513, 513) == 1 and lib.afan_ce2d_upsampled_supported(21, 33, 33, 65, 65) == 0
+    assert lib.afan_ce2d_upsampled(p, p, 1, 21, 33, 33, 65, 65, 255, 1.0, p, p, None, None) == -3   # a tile's source window > 8 rows
+    assert lib.afan_ce2d_upsampled(p, p, 1, 33, 33, 33, 129, 129, 255, 1.0, p, p, None, None) == -3  # more than 32 classes
     assert lib.afan_maxpool3x3s2_fwd(p, p, 3, 0, 1, 1, 4, 4, None) == -1
     assert lib.afan_pointwise_fwd(p, 1, p, None, p, 4, 12, 4, None) == -3                   # ci % 8
     assert lib.afan_pointwise_fwd(p, 1, p, None, p, 4, 16, 33, None) == -3                  # co > afan_pointwise_max_co()
