@@ -6,12 +6,13 @@ Sub-modules: attack_algo (PGD & friends, reference signatures), resnet_s (slice-
 arena (flat parameter arena + fused SGD), train_step (the joint step, data parallel), ops (tensor
 wrappers over the C-ABI in include/afan_hip.h), main_perturb (entry point for cmd/run_perturb.sh; DeviceLoader: one-launch batches), main_base (the baseline trainer, cmd/run_base.sh), infer (the fused, graph-replayed eval forward; main_inference evaluates a checkpoint), deeplab (the
 DeepLabv3+ split-forward network), seg_attack_algo / seg_trainer (the Segmentation A-FAN operators and iteration), seg_data (SegDeviceLoader: one-launch
-segmentation batches; main_aug_final is the entry point for cmd/run_seg.sh), det_ops / det_attack_algo / det_model / det_trainer
+segmentation batches; main_aug_final is the entry point for cmd/run_seg.sh), seg_eval (StreamSegMetrics with a one-launch confusion
+matrix, validate; main_seg_val scores a checkpoint, cmd/run_seg_val.sh), det_ops / det_attack_algo / det_model / det_trainer
 (the Detection operators, iteration, the Faster-RCNN / ResNet-101 model and its data-parallel trainer).
 """
 from . import _lib, ops  # noqa: F401
 from ._lib import AfanLibraryError, LIB_PATH  # noqa: F401
-from . import resnet_s, attack_algo, arena, grid_guard, train_step, learnable, seg_attack_algo, deeplab, seg_trainer, seg_data, det_ops, det_attack_algo, det_model, det_trainer, host, infer  # noqa: F401
+from . import resnet_s, attack_algo, arena, grid_guard, train_step, learnable, seg_attack_algo, deeplab, seg_trainer, seg_data, seg_eval, det_ops, det_attack_algo, det_model, det_trainer, host, infer  # noqa: F401
 from .attack_algo import PGD, get_sample_points, linfball_proj, mix_feature, tensor_clamp  # noqa: F401
 
 __version__ = "0.1.0"

@@ -6,8 +6,10 @@ What differs from the reference is execution only: the iteration body is seg_tra
 hipGraph), the batch is built on the device by seg_data.SegDeviceLoader in one launch, and the loss stays on the device until the
 `Epoch:[..], Itrs:[..], Loss:[..]` line needs it, every 10 iterations.
 
-Not built here: validation (--test_only, --eval_pgd, --save_val_results raise; at --val_interval only latest_* is saved and
-best_score stays 0.0), --dataset cityscapes (its ExtColorJitter has no kernel), visdom and tensorboard (accepted, ignored)."""
+Validation (seg_eval.validate: one eager low-resolution forward and one scoring launch per batch) runs at every --val_interval on the
+`val` image set and keeps best_*; a --synthetic run has no validation split and skips it.  Scoring a checkpoint on its own
+(the reference's --test_only) is main_seg_val.py.  Not built here: --test_only, --eval_pgd, --save_val_results (they raise),
+--dataset cityscapes (its ExtColorJitter has no kernel), visdom and tensorboard (accepted, ignored)."""
 import argparse
 import os
 import random
@@ -22,11 +24,14 @@ if __package__ in (None, ""):  # executed as a script (cmd/run_seg.sh): import t
     import importlib
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     _pkg = importlib.import_module("cv_a-fan_amd")
-    deeplab, seg_trainer, seg_data, host = _pkg.deeplab, _pkg.seg_trainer, _pkg.seg_data, _pkg.host
+    deeplab, seg_trainer, seg_data, seg_eval, host = _pkg.deeplab, _pkg.seg_trainer, _pkg.seg_data, _pkg.seg_eval, _pkg.host
 else:
-    from . import deeplab, host, seg_data, seg_trainer
+    from . import deeplab, host, seg_data, seg_eval, seg_trainer
 
-VALIDATION_ISSUE = "segmentation validation (mIoU, args.validate) is a separate issue and is not built yet"
+UNBUILT_VALIDATION = {"test_only": "validation of a checkpoint on its own is main_seg_val.py (cmd/run_seg_val.sh), not a flag of this program",
+                      "eval_pgd": "validation under an image-space PGD attack (args.pgd_validate) is not built; main_seg_val.py scores clean images",
+                      "save_val_results": "writing validation images is not built; validation itself runs at --val_interval and in main_seg_val.py"}
+NO_VAL_SPLIT = "a --synthetic run has no validation split (main_seg_val.py --synthetic N scores a checkpoint on a synthetic one)"
 # network/modeling.py's map without the mobilenets, which main_aug_final.py can name but this build has no kernels for
 MODEL_MAP = deeplab.MODELS
 
@@ -137,7 +142,7 @@ def check_unbuilt(opts):
     """The reference's options this build has nothing behind: raise before any work is done."""
     for flag in ("test_only", "eval_pgd", "save_val_results"):
         if getattr(opts, flag):
-            raise NotImplementedError(f"--{flag}: {VALIDATION_ISSUE}")
+            raise NotImplementedError(f"--{flag}: {UNBUILT_VALIDATION[flag]}")
     if opts.dataset.lower() == "cityscapes":
         raise NotImplementedError("--dataset cityscapes: its training transform has ExtColorJitter, which the batch kernel does not do")
     if opts.model not in MODEL_MAP:
@@ -176,17 +181,23 @@ def main(argv=None):
         split = seg_data.SyntheticSegSplit(opts.synthetic, seed=opts.random_seed, min_side=max(3 * hi // 4, 1), max_side=hi,
                                            classes=opts.num_classes)
         images, labels = split.images, split.labels
+        val_loader, n_val = None, 0
     else:
         images, labels = seg_data.load_voc(opts.data_root, opts.year, "train")
+        val_images, val_labels = seg_data.load_voc(opts.data_root, opts.year, "val")
+        val_loader = seg_data.SegDeviceLoader(val_images, val_labels, opts.val_batch_size, device, False, opts.crop_size,
+                                              crop_val=opts.crop_val)      # (without --crop_val: batches of 1, :50-51)
+        n_val = len(val_images)
     train_loader = seg_data.SegDeviceLoader(images, labels, opts.batch_size, device, True, opts.crop_size, seed=opts.random_seed)
     if len(train_loader) == 0:
         raise ValueError(f"{len(images)} images make no batch of {opts.batch_size} (drop_last)")
-    print("Dataset: %s, Train set: %d, Val set: %d" % (opts.dataset, len(images), 0))
+    print("Dataset: %s, Train set: %d, Val set: %d" % (opts.dataset, len(images), n_val))
 
     # ---- model, trainer (optimizer + scheduler), criterion
     model = MODEL_MAP[opts.model](num_classes=opts.num_classes, output_stride=opts.output_stride)
     model.set_compute_dtype(torch.bfloat16 if opts.dtype == "bf16" else torch.float32)
     model.set_channels_last(opts.layout == "nhwc").to(device).train()
+    metrics = seg_eval.StreamSegMetrics(opts.num_classes, device)
     criterion = nn.CrossEntropyLoss(ignore_index=255, reduction='mean')
     trainer = seg_trainer.SegTrainer(model, criterion, steps=opts.steps, eps=opts.eps, gamma_se=opts.gamma_se, gamma_sd=opts.gamma_sd,
                                      pertub_idx_se=opts.pertub_idx_se, pertub_idx_sd=opts.pertub_idx_sd, mix_layer=opts.mix_layer,
@@ -249,7 +260,18 @@ def main(argv=None):
             if cur_itrs % opts.val_interval == 0:
                 trainer.flush_guard()
                 save_ckpt(ckpt_path(opts))
-                print("validation skipped: " + VALIDATION_ISSUE)
+                if val_loader is None:
+                    print("validation skipped: " + NO_VAL_SPLIT)
+                else:
+                    # main_aug_final.py:252-263,276 — eager, outside the step's graph and its buffers
+                    print("validation...")
+                    model.eval()
+                    val_score, _ = seg_eval.validate(opts=opts, model=model, loader=val_loader, device=device, metrics=metrics)
+                    print(metrics.to_str(val_score))
+                    if val_score['Mean IoU'] > best_score:                # save best model
+                        best_score = float(val_score['Mean IoU'])
+                        save_ckpt('checkpoints/' + opts.exp + '/best_%s_%s_os%d.pth' % (opts.model, opts.dataset, opts.output_stride))
+                    model.train()
             scheduler.step()
             total_time += time.time() - t0
             if cur_itrs >= opts.total_itrs:

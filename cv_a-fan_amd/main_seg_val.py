@@ -1,0 +1,107 @@
+"""Score a segmentation checkpoint on the validation set: what the reference's Segmentation/main_aug_final.py does under --test_only
+(:139-144), as a program of its own, so `bash cmd/run_seg_val.sh` works.  The flags it shares with the reference keep the reference's
+names and defaults (args.py:14-105): --ckpt --model --output_stride --data_root --year --crop_val --crop_size --val_batch_size --gpu_id
+--random_seed.  Additions: --dtype, --layout, --synthetic N, --max_side (as main_aug_final.py's).
+
+Per batch: SegDeviceLoader's one launch, the model's eval-mode forward up to the classifier's low-resolution logits, and one scoring
+launch (seg_eval.validate); the confusion matrix is read back once, for the printed scores."""
+import argparse
+import os
+import random
+import sys
+
+import numpy as np
+import torch
+
+if __package__ in (None, ""):  # executed as a script (cmd/run_seg_val.sh): import the hyphenated package by path
+    import importlib
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    _pkg = importlib.import_module("cv_a-fan_amd")
+    deeplab, seg_data, seg_eval = _pkg.deeplab, _pkg.seg_data, _pkg.seg_eval
+else:
+    from . import deeplab, seg_data, seg_eval
+
+MODEL_MAP = deeplab.MODELS
+DATASET, NUM_CLASSES = "voc", 21                                     # (main_aug_final.py:29-30)
+ADDITIONS = ("dtype", "layout", "synthetic", "max_side")
+
+
+def get_argparser():
+    parser = argparse.ArgumentParser()
+    # the reference's options (args.py), names and defaults unchanged
+    parser.add_argument("--ckpt", default=None, type=str, help="restore from checkpoint")
+    parser.add_argument("--model", type=str, default='deeplabv3plus_resnet50',
+                        choices=['deeplabv3_resnet50', 'deeplabv3plus_resnet50', 'deeplabv3_resnet101', 'deeplabv3plus_resnet101',
+                                 'deeplabv3_mobilenet', 'deeplabv3plus_mobilenet'], help='model name')
+    parser.add_argument("--output_stride", type=int, default=16, choices=[8, 16])
+    parser.add_argument("--data_root", type=str, default='./datasets/data', help="path to Dataset")
+    parser.add_argument("--year", type=str, default='2012', choices=['2012_aug', '2012', '2011', '2009', '2008', '2007'],
+                        help='year of VOC')
+    parser.add_argument("--crop_val", action='store_true', default=False, help='crop validation (default: False)')
+    parser.add_argument("--crop_size", type=int, default=513)
+    parser.add_argument("--val_batch_size", type=int, default=4, help='batch size for validation (default: 4)')
+    parser.add_argument("--gpu_id", type=str, default='0', help="GPU ID")
+    parser.add_argument("--random_seed", type=int, default=1, help="random seed (default: 1)")
+    # additions
+    parser.add_argument("--dtype", default="bf16", choices=["bf16", "fp32"], help="backbone compute dtype")
+    parser.add_argument("--layout", default="nhwc", choices=["nhwc", "nchw"], help="internal activation / weight layout")
+    parser.add_argument("--synthetic", type=int, default=0, help="score on N synthetic images of random sizes instead of VOC's val set")
+    parser.add_argument("--max_side", type=int, default=0, help="--synthetic: the longest image side (0: 500, VOC's; the shortest is 3/4 of it)")
+    return parser
+
+
+def synthetic_split(opts):
+    """The split --synthetic N scores on (main_aug_final.py draws its training split the same way)."""
+    hi = opts.max_side or 500
+    return seg_data.SyntheticSegSplit(opts.synthetic, seed=opts.random_seed, min_side=max(3 * hi // 4, 1), max_side=hi,
+                                      classes=NUM_CLASSES)
+
+
+def main(argv=None):
+    opts = get_argparser().parse_args(argv)
+    for arg, val in opts.__dict__.items():                              # (args.py:259-262)
+        print(arg + '.' * (80 - len(arg) - len(str(val))) + str(val))
+    print()
+    if opts.model not in MODEL_MAP:
+        raise NotImplementedError(f"--model {opts.model}: the mobilenet backbones are not built (no kernels for depthwise convolutions)")
+    opts.save_val_results = False
+    local = int(opts.gpu_id.split(",")[0])
+    if not torch.cuda.is_available():
+        raise RuntimeError("main_seg_val.py needs an MI355X: this build has no CPU path (oracle/ is test infrastructure)")
+    torch.cuda.set_device(local)
+    device = torch.device("cuda", local)
+    print("Device: %s" % device)
+
+    torch.manual_seed(opts.random_seed)
+    np.random.seed(opts.random_seed)
+    random.seed(opts.random_seed)
+
+    model = MODEL_MAP[opts.model](num_classes=NUM_CLASSES, output_stride=opts.output_stride)
+    model.set_compute_dtype(torch.bfloat16 if opts.dtype == "bf16" else torch.float32)
+    model.set_channels_last(opts.layout == "nhwc")
+    if opts.ckpt is not None and os.path.isfile(opts.ckpt):
+        checkpoint = torch.load(opts.ckpt, map_location=torch.device('cpu'))
+        model.load_state_dict(checkpoint["model_state"])
+        print("Model restored from %s" % opts.ckpt)
+        del checkpoint
+    else:
+        print("[!] Retrain")
+    model.to(device)
+
+    if opts.synthetic:
+        split = synthetic_split(opts)
+        images, labels = split.images, split.labels
+    else:
+        images, labels = seg_data.load_voc(opts.data_root, opts.year, "val")
+    loader = seg_data.SegDeviceLoader(images, labels, opts.val_batch_size, device, False, opts.crop_size, crop_val=opts.crop_val)
+    print("Dataset: %s, Val set: %d" % (DATASET, len(images)))
+
+    metrics = seg_eval.StreamSegMetrics(NUM_CLASSES, device)
+    model.eval()
+    val_score, _ = seg_eval.validate(opts=opts, model=model, loader=loader, device=device, metrics=metrics)
+    print(metrics.to_str(val_score))
+    return val_score
+
+
+if __name__ == '__main__':
+    main()

@@ -20,7 +20,8 @@ _tls = threading.local()
 # "conv_general" counts passes of the fp32-arithmetic general kernels, afan_conv_f32.hip)
 class _Calls(dict):
     """The convolution counters are the dict's own items: what the logs and the tests enumerate (`dict(CALLS)`, `set(CALLS)`).
-    Counters of launches outside the convolution path (`batch_crop_flip`, `seg_batch_aug`: the loaders' kernels) live in `.other` and are read and
+    Counters of launches outside the convolution path (`batch_crop_flip`, `seg_batch_aug`: the loaders' kernels; `seg_confusion`:
+    validation's scoring kernel) live in `.other` and are read and
     written through the same subscript, `in` and `.get`, so that the enumerated table stays the convolution table
     (tests/test_host_logic.py::test_no_convolution_leaves_the_library pins `set(CALLS)` to the six convolution counters)."""
 
@@ -45,7 +46,7 @@ class _Calls(dict):
 
 
 CALLS = _Calls({"conv_fwd": 0, "conv_dgrad": 0, "conv_wgrad": 0, "conv_general": 0, "vendor_conv": 0, "conv_bn_fused": 0},
-               {"batch_crop_flip": 0, "seg_batch_aug": 0})
+               {"batch_crop_flip": 0, "seg_batch_aug": 0, "seg_confusion": 0})
 
 
 def _need(t, name, dtype=None):
@@ -1654,6 +1655,30 @@ def ce2d_upsampled(logits, target, ignore_index=255, grad_scale=1.0, want_grad=T
     check(lib.afan_ce2d_upsampled(_ptr(logits), _ptr(target), n, c, h, w, ho, wo, int(ignore_index), float(grad_scale), _ptr(ws),
                                   _ptr(loss), _ptr(dl), _stream(logits)), "afan_ce2d_upsampled")
     return loss, dl
+
+
+def seg_confusion_upsampled(logits, target, hist):
+    """hist[t * C + argmax_c F.interpolate(logits, target.shape[1:], 'bilinear')[:, c]] += 1 over the pixels whose label t is in
+    [0, C) (stream_metrics.py:42-49's _fast_hist on utils.py:30's resize and args.py:187's max(dim=1)) in one launch
+    (afan_seg_confusion_upsampled); equal sizes: arg-max + count of full-resolution logits.  logits [N,C,h,w] fp32 on the GPU, made
+    dense channels-last here when they are not (the entry takes no layout argument); target [N,H,W] int64; hist: int64, C*C
+    elements, contiguous, ADDED to in place.  No host synchronisation."""
+    lib = _lib.load()
+    if not (isinstance(logits, torch.Tensor) and logits.is_cuda and logits.dtype == torch.float32 and logits.dim() == 4):
+        raise TypeError("seg_confusion_upsampled: logits [N,C,h,w] fp32 on the GPU")
+    n, c, h, w = logits.shape
+    if not (isinstance(target, torch.Tensor) and target.is_cuda and target.dim() == 3 and target.dtype == torch.int64
+            and target.shape[0] == n):
+        raise TypeError("seg_confusion_upsampled: target [N,H,W] int64 on the GPU")
+    if not (isinstance(hist, torch.Tensor) and hist.device == logits.device and hist.dtype == torch.int64 and hist.numel() == c * c
+            and hist.is_contiguous()):
+        raise TypeError("seg_confusion_upsampled: hist must be a contiguous int64 tensor of C*C elements on the logits' device")
+    logits = logits.contiguous(memory_format=torch.channels_last)        # (no copy when they already are)
+    target = target.contiguous()
+    CALLS["seg_confusion"] += 1
+    check(lib.afan_seg_confusion_upsampled(_ptr(logits), _ptr(target), n, c, h, w, int(target.shape[1]), int(target.shape[2]),
+                                           _ptr(hist), _stream(logits)), "afan_seg_confusion_upsampled")
+    return hist
 
 
 def maxpool3x3s2(x):

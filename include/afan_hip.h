@@ -519,6 +519,16 @@ int64_t afan_ce2d_upsampled_workspace_floats(int64_t n, int64_t c, int64_t h, in
 int afan_ce2d_upsampled(const float* logits, const int64_t* target, int64_t n, int64_t c, int64_t h, int64_t w, int64_t ho,
                         int64_t wo, int64_t ignore_index, float grad_scale, float* workspace, float* loss, float* dlogits,
                         afan_stream_t stream);
+/* Validation's scoring, Segmentation/args.py:187-196 + metrics/stream_metrics.py:42-49, in ONE launch: resize the classifier's
+ * logits [n,h,w,c] (channels-last fp32, dense, c <= 32) bilinearly (align_corners=False) to the labels' [n,ho,wo], take each
+ * pixel's arg-max over the classes (torch.max(dim=1): the lowest class among equal maxima, a NaN is the maximum and the first
+ * NaN wins) and count hist[t * c + pred] += 1 for every pixel whose label t is in [0, c) — every other label (255, negative,
+ * >= c) is skipped, _fast_hist's mask.  The interpolated logits are afan_upsample_bilinear_fwd's to the bit and are never
+ * stored.  hist: int64 [c * c] on the device; the entry ADDS to it (64-bit integer atomics: independent of order) and never
+ * zeroes it.  Every h <= ho, w <= wo, h == ho and w == wo included (then it is arg-max + count of full-resolution logits).
+ * n == 0: AFAN_OK without a launch; c > 32, h > ho, w > wo (or more than 2^31 - 1 output tiles): AFAN_ESHAPE. */
+int afan_seg_confusion_upsampled(const float* logits, const int64_t* target, int64_t n, int64_t c, int64_t h, int64_t w,
+                                 int64_t ho, int64_t wo, int64_t* hist, afan_stream_t stream);
 /* nn.MaxPool2d(kernel_size=3, stride=2, padding=1) (backbone/resnet.py:146): ho = (hi-1)/2+1.  The backward routes each
  * output gradient to the FIRST maximum of its window in (h, w) scan order, NaN winning — ATen's CPU rule. */
 int afan_maxpool3x3s2_fwd(const void* x, void* y, int dtype, int layout, int64_t n, int64_t c, int64_t hi, int64_t wi,
