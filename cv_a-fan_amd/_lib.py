@@ -156,6 +156,8 @@ SIGNATURES = {
     "afan_normalize_nchw": (_i, [_p, _p, _i, _i, _l, _l, _l, _p, _p, _p]),
     "afan_batch_crop_flip_u8": (_i, [_p, _p, _l, _p, _p, _p, _p, _p, _p, _l, _l, _l, _l, _i, _p]),
     "afan_seg_batch_aug_u8": (_i, [_p, _p, _p, _p, _p, _l, _l, _p, _p, _p, _p, _p, _p, _p, _p, _l, _l, _l, C.c_double, _p]),
+    "afan_seg_batch_aug_jitter_u8": (_i, [_p, _p, _p, _p, _p, _l, _l, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _l, _l, _l,
+                                          C.c_double, _p]),
     "afan_profile_enable": (_i, [_i]),
     "afan_profile_collect": (_i, [C.c_char_p, C.POINTER(_l), C.POINTER(C.c_double), C.POINTER(C.c_double),
                                   C.POINTER(C.c_double), _i]),

@@ -20,7 +20,8 @@ _tls = threading.local()
 # "conv_general" counts passes of the fp32-arithmetic general kernels, afan_conv_f32.hip)
 class _Calls(dict):
     """The convolution counters are the dict's own items: what the logs and the tests enumerate (`dict(CALLS)`, `set(CALLS)`).
-    Counters of launches outside the convolution path (`batch_crop_flip`, `seg_batch_aug`: the loaders' kernels; `seg_confusion`:
+    Counters of launches outside the convolution path (`batch_crop_flip`, `seg_batch_aug`, `seg_batch_aug_jitter`: the loaders'
+    kernels; `seg_confusion`:
     validation's scoring kernel) live in `.other` and are read and
     written through the same subscript, `in` and `.get`, so that the enumerated table stays the convolution table
     (tests/test_host_logic.py::test_no_convolution_leaves_the_library pins `set(CALLS)` to the six convolution counters)."""
@@ -46,7 +47,7 @@ class _Calls(dict):
 
 
 CALLS = _Calls({"conv_fwd": 0, "conv_dgrad": 0, "conv_wgrad": 0, "conv_general": 0, "vendor_conv": 0, "conv_bn_fused": 0},
-               {"batch_crop_flip": 0, "seg_batch_aug": 0, "seg_confusion": 0})
+               {"batch_crop_flip": 0, "seg_batch_aug": 0, "seg_batch_aug_jitter": 0, "seg_confusion": 0})
 
 
 def _need(t, name, dtype=None):
@@ -2101,6 +2102,64 @@ def seg_batch_aug(images, offsets, labels, hs, ws, index, oh, ow, top, left, fli
                                     int(out_w), float(max_shrink), _stream(images)), "afan_seg_batch_aug_u8")
     CALLS["seg_batch_aug"] += 1
     return out, labels_out
+
+
+def seg_batch_aug_jitter(images, offsets, labels, hs, ws, index, oh, ow, top, left, flip, order, brightness, contrast, saturation,
+                         out_h, out_w, max_shrink=3.0, workspace=None):
+    """seg_batch_aug with the reference's ExtColorJitter(brightness, contrast, saturation) between the crop and the flip
+    (afan_seg_batch_aug_jitter_u8; seg_data._augment_jitter_numpy restates it).  order: int64 [m] codes 0..5 into
+    seg_data.JITTER_ORDERS (clamped by the kernel); brightness / contrast / saturation: fp32 [m] factors.  workspace: int64 [>= m]
+    for the gray sums (allocated when None; a graph-captured caller passes its own).  Factors given on the host (numpy arrays, lists,
+    CPU tensors) are checked by `jitter_factors` — a NaN or an infinity raises ValueError — and uploaded; device vectors are taken as
+    they are, without a read-back (SegDeviceLoader's draws go through `jitter_factors` before their one upload)."""
+    host = [not (isinstance(t, torch.Tensor) and t.is_cuda) for t in (brightness, contrast, saturation)]
+    if any(host):
+        fac = [torch.from_numpy(jitter_factors(t.numpy() if isinstance(t, torch.Tensor) else t)) if h else t
+               for t, h in zip((brightness, contrast, saturation), host)]
+        _need(images, "images", torch.uint8)
+        brightness, contrast, saturation = (t.to(images.device) if h else t for t, h in zip(fac, host))
+    lib = _lib.load()
+    _need(images, "images", torch.uint8)
+    _need(labels, "labels", torch.uint8)
+    _need(offsets, "offsets", torch.int64)
+    _need(hs, "hs", torch.int32)
+    _need(ws, "ws", torch.int32)
+    per = (index, oh, ow, top, left, flip, order)
+    for t, name in zip(per, ("index", "oh", "ow", "top", "left", "flip", "order")):
+        _need(t, name, torch.int64)
+    fac = (brightness, contrast, saturation)
+    for t, name in zip(fac, ("brightness", "contrast", "saturation")):
+        _need(t, name, torch.float32)
+    m = index.shape[0]
+    if any(t.dim() != 1 or t.shape[0] != m for t in per + fac):
+        raise ValueError("seg_batch_aug_jitter: index, oh, ow, top, left, flip, order (int64) and the three factors (fp32) are vectors "
+                         "with one entry per sample")
+    n = offsets.shape[0]
+    if images.dim() != 1 or labels.dim() != 1 or images.shape[0] != 3 * labels.shape[0] or hs.shape != (n,) or ws.shape != (n,):
+        raise ValueError("seg_batch_aug_jitter: images is packed HWC uint8 (3 bytes per label byte), offsets / hs / ws have one entry per image")
+    if workspace is None:
+        workspace = torch.empty(max(m, 1), dtype=torch.int64, device=images.device)
+    _need(workspace, "workspace", torch.int64)
+    if workspace.dim() != 1 or workspace.shape[0] < m:
+        raise ValueError("seg_batch_aug_jitter: the workspace is an int64 vector of at least one entry per sample")
+    out = torch.empty((m, 3, int(out_h), int(out_w)), dtype=torch.float32, device=images.device)
+    labels_out = torch.empty((m, int(out_h), int(out_w)), dtype=torch.int64, device=images.device)
+    check(lib.afan_seg_batch_aug_jitter_u8(_ptr(images), _ptr(offsets), _ptr(labels), _ptr(hs), _ptr(ws), n, labels.shape[0], _ptr(index),
+                                           _ptr(oh), _ptr(ow), _ptr(top), _ptr(left), _ptr(flip), _ptr(order), _ptr(brightness),
+                                           _ptr(contrast), _ptr(saturation), _ptr(workspace), _ptr(out), _ptr(labels_out), m, int(out_h),
+                                           int(out_w), float(max_shrink), _stream(images)), "afan_seg_batch_aug_jitter_u8")
+    CALLS["seg_batch_aug_jitter"] += 1
+    return out, labels_out
+
+
+def jitter_factors(factors):
+    """Host-side colour-jitter factors -> a float32 numpy array of the same shape, refusing what the kernel must never see: a NaN or an
+    infinity (the blend d + f * (i - d) would not be finite).  What SegDeviceLoader uploads goes through here."""
+    import numpy as np
+    f = np.asarray(factors, dtype=np.float64)
+    if not np.isfinite(f).all():
+        raise ValueError("colour-jitter factors must be finite (got a NaN or an infinity)")
+    return f.astype(np.float32)
 
 
 # ------------------------------------------------------------------------------------- measurement

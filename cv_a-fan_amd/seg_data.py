@@ -9,6 +9,10 @@ The kernel is a pure function of per-sample parameters (index, resized size, cro
 host for a whole epoch at once from a seeded generator and uploads them in one pinned, non-blocking copy, so a batch costs one launch
 and no host synchronisation.  `_augment_numpy` restates the kernel in plain numpy: it is what the GPU tests hold the kernel to, and
 tests/golden/seg_aug_pillow.npz holds it to Pillow's own output, bit for bit.
+
+Cityscapes (args.py:142-151) is ExtRandomCrop -> ExtColorJitter(0.5, 0.5, 0.5) -> flip -> ToTensor: the same loader with
+scale_range=(1, 1) and jitter=(0.5, 0.5, 0.5), through ops.seg_batch_aug_jitter; `_jitter_numpy` / `_augment_jitter_numpy` restate it and
+tests/golden/seg_jitter_pillow.npz holds the restatement to Pillow's ImageEnhance.
 """
 import math
 import os
@@ -117,6 +121,75 @@ def _augment_numpy_batch(images, labels, index, oh, ow, top, left, flip, out_h, 
     return np.stack([o[0] for o in outs]), np.stack([o[1] for o in outs])
 
 
+# ------------------------------------------------------------------------------------ ExtColorJitter, restated
+# ExtColorJitter(brightness, contrast, saturation) is torchvision's PIL functional: PIL.ImageEnhance.{Brightness, Contrast, Color}
+# (img).enhance(f) = Image.blend(degenerate, img, f), in a shuffled order, each on the uint8 output of the one before.
+BRIGHTNESS, CONTRAST, SATURATION = 0, 1, 2
+# the order code the kernel takes: the permutations of (brightness, contrast, saturation) in lexicographic order
+JITTER_ORDERS = ((0, 1, 2), (0, 2, 1), (1, 0, 2), (1, 2, 0), (2, 0, 1), (2, 1, 0))
+
+
+def _gray(img):
+    """Pillow's RGB -> L on an HWC uint8 array, in integers."""
+    a = img.astype(np.int64)
+    return (19595 * a[..., 0] + 38470 * a[..., 1] + 7471 * a[..., 2] + 0x8000) >> 16
+
+
+def _blend(d, img, f):
+    """Image.blend(degenerate, image, f) on uint8 values: fp32, the product and the sum rounded separately (numpy does not fuse)."""
+    f32 = np.float32(f)
+    d32 = np.asarray(d).astype(np.float32)
+    with np.errstate(invalid="ignore", over="ignore"):
+        t = d32 + f32 * (img.astype(np.float32) - d32)
+        t = np.broadcast_to(t, img.shape)
+        if np.float32(0) <= f32 <= np.float32(1):
+            return t.astype(np.uint8)                                 # between d and the pixel: truncated
+        out = np.where(t >= np.float32(255), np.float32(255), t)
+        out = np.where(out > np.float32(0), out, np.float32(0))       # t <= 0 (and what is not a number) -> 0
+        return out.astype(np.uint8)
+
+
+def _jitter_numpy(img_u8, order, factors):
+    """The three operations on an HWC uint8 image.  order: code into JITTER_ORDERS (clamped into 0..5, as the kernel clamps it);
+    factors: (brightness, contrast, saturation), by operation — not by position in the order."""
+    img = np.ascontiguousarray(img_u8)
+    for op in JITTER_ORDERS[min(max(int(order), 0), 5)]:
+        f = factors[op]
+        if op == BRIGHTNESS:
+            d = np.zeros((), np.int64)
+        elif op == CONTRAST:
+            g = _gray(img)                                            # ImageStat.Stat(img.convert("L")).mean[0], int(mean + 0.5)
+            d = np.array(int(int(g.sum()) / g.size + 0.5), np.int64)
+        else:
+            d = _gray(img)[..., None]                                 # img.convert("L").convert("RGB")
+        img = _blend(d, img, f)
+    return img
+
+
+def _augment_jitter_numpy(img, lbl, oh, ow, top, left, flip, order, factors, out_h, out_w, max_shrink=MAX_SHRINK):
+    """One sample of ops.seg_batch_aug_jitter in numpy: _augment_numpy with the jitter between the crop and the flip (the padding's
+    pixels count in contrast's mean and are jittered, as Pillow would do)."""
+    h, w = lbl.shape
+    oh, ow, pad, top, left = _clamped(h, w, oh, ow, top, left, out_h, out_w, max_shrink)
+    ri = np.pad(_resize_bilinear(img, oh, ow), ((pad, pad), (pad, pad), (0, 0)))
+    rl = np.pad(_resize_nearest(lbl, oh, ow), ((pad, pad), (pad, pad)))
+    ri, rl = ri[top:top + out_h, left:left + out_w], rl[top:top + out_h, left:left + out_w]
+    ri = _jitter_numpy(ri, order, factors)
+    if flip:
+        ri, rl = ri[:, ::-1], rl[:, ::-1]
+    return np.ascontiguousarray(QUOT255[ri].transpose(2, 0, 1)), np.ascontiguousarray(rl.astype(np.int64))
+
+
+def _augment_jitter_numpy_batch(images, labels, index, oh, ow, top, left, flip, order, factors, out_h, out_w, max_shrink=MAX_SHRINK):
+    """factors: [3, m] (rows: brightness, contrast, saturation)."""
+    n = len(images)
+    fac = np.asarray(factors)
+    outs = [_augment_jitter_numpy(images[min(max(int(k), 0), n - 1)], labels[min(max(int(k), 0), n - 1)], a, b, t, l, f, o, fac[:, i],
+                                  out_h, out_w, max_shrink)
+            for i, (k, a, b, t, l, f, o) in enumerate(zip(index, oh, ow, top, left, flip, order))]
+    return np.stack([o[0] for o in outs]), np.stack([o[1] for o in outs])
+
+
 # ------------------------------------------------------------------------------------ parameters of the reference's transforms
 def val_resize_size(h, w, size):
     """ExtResize(size) with an int: the shorter side becomes `size` (torchvision's F.resize)."""
@@ -151,10 +224,16 @@ class SegDeviceLoader:
     permutation, scales, crop origins and flips are drawn on the host from one generator (seeded with (seed, epoch): every rank
     draws the same and takes its slice) and uploaded in one pinned non-blocking copy; per batch there is exactly one launch and no
     host synchronisation.  train=False gives the reference's validation transforms through the same kernel: crop_val (ExtResize +
-    ExtCenterCrop at crop_size, in batches) or the images as they are, one per batch."""
+    ExtCenterCrop at crop_size, in batches) or the images as they are, one per batch.
+
+    jitter=(b, c, s) (training only) adds the reference's ExtColorJitter(brightness=b, contrast=c, saturation=s) between the crop and
+    the flip (ops.seg_batch_aug_jitter): per sample and epoch an order of the three operations and three factors uniform in
+    [max(0, 1 - v), 1 + v], drawn AFTER the other draws from the same generator, so a loader without jitter draws what it always drew.
+    scale_range=(1, 1) is the Cityscapes transform: ExtRandomCrop without ExtRandomScale and without pad_if_needed — an image smaller
+    than the crop is refused at construction (the reference's random.randint(0, h - th) raises there)."""
 
     def __init__(self, images, labels, batch, device, train, crop_size, crop_val=False, scale_range=(0.5, 2.0), seed=None, rank=0,
-                 world=1):
+                 world=1, jitter=None):
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise ops.AfanLibraryError("SegDeviceLoader needs an MI355X: the batch is built by a HIP kernel and there is no CPU path")
@@ -163,6 +242,14 @@ class SegDeviceLoader:
         self.hs, self.ws = hs.astype(np.int64), ws.astype(np.int64)
         self.train, self.crop_val, self.crop = bool(train), bool(crop_val), int(crop_size)
         self.scale_range = (float(scale_range[0]), float(scale_range[1]))
+        self.jitter = None
+        if jitter is not None and self.train:
+            self.jitter = tuple(float(v) for v in jitter)
+            if len(self.jitter) != 3 or not all(math.isfinite(v) and v >= 0 for v in self.jitter):
+                raise ValueError("jitter takes (brightness, contrast, saturation), three finite values >= 0")
+        if self.train and self.scale_range == (1.0, 1.0) and (int(hs.min()) < self.crop or int(ws.min()) < self.crop):
+            raise ValueError(f"scale_range=(1, 1) crops without padding: an image of {int(hs.min())} x {int(ws.min())} (smallest height x "
+                             f"smallest width) is smaller than the crop of {self.crop}")
         self.rank, self.world, self.seed, self.epoch = int(rank), int(world), seed, 0
         if world > 1 and seed is None:
             raise RuntimeError("a data-parallel SegDeviceLoader needs a seed shared by all ranks")
@@ -192,6 +279,7 @@ class SegDeviceLoader:
         self.offsets = torch.from_numpy(off).to(dev)
         self.d_hs = torch.from_numpy(hs).to(dev)
         self.d_ws = torch.from_numpy(ws).to(dev)
+        self._gray_sums = self._jitter_draw = None
 
     def __len__(self):
         return self.n_batches
@@ -213,6 +301,10 @@ class SegDeviceLoader:
             left = rng.integers(0, ow + 2 * pad - self.crop + 1)
             flip = (rng.random(idx.shape[0]) < 0.5).astype(np.int64)
             sizes = [(self.crop, self.crop)] * self.n_batches
+            self._jitter_draw = None
+            if self.jitter is not None:                               # ExtColorJitter.get_params: three factors, then the shuffle
+                fac = np.stack([rng.uniform(max(0.0, 1.0 - v), 1.0 + v, idx.shape[0]) for v in self.jitter])
+                self._jitter_draw = (rng.integers(0, 6, idx.shape[0]).astype(np.int64), ops.jitter_factors(fac))
         elif self.crop_val:
             idx = np.arange(self.n)
             s = np.array([val_resize_size(int(h), int(w), self.crop) for h, w in zip(self.hs, self.ws)], np.int64)
@@ -231,6 +323,13 @@ class SegDeviceLoader:
         params, sizes = self._draw()
         self.last_params = params                                       # (host copy: what tests compare the batches against)
         dev_params = torch.from_numpy(params).pin_memory().to(self.device, non_blocking=True)       # one upload per epoch
+        jit = self._jitter_draw if self.train else None
+        self.last_jitter = jit                                          # (order int64 [n_used], factors fp32 [3, n_used]) or None
+        if jit is not None:
+            dev_order = torch.from_numpy(jit[0]).pin_memory().to(self.device, non_blocking=True)
+            dev_fac = torch.from_numpy(jit[1]).pin_memory().to(self.device, non_blocking=True)
+            if self._gray_sums is None:
+                self._gray_sums = torch.empty(max(self.batch // self.world, 1), dtype=torch.int64, device=self.device)
         per = self.batch // self.world
         for b in range(self.n_batches):
             lo = b * self.batch + self.rank * per
@@ -238,6 +337,12 @@ class SegDeviceLoader:
             if hi <= lo:
                 continue
             p = dev_params[:, lo:hi]
+            if jit is not None:
+                f = dev_fac[:, lo:hi]
+                yield ops.seg_batch_aug_jitter(self.images, self.offsets, self.labels, self.d_hs, self.d_ws, p[0], p[1], p[2], p[3], p[4],
+                                               p[5], dev_order[lo:hi], f[0], f[1], f[2], sizes[b][0], sizes[b][1], self.max_shrink,
+                                               workspace=self._gray_sums)
+                continue
             yield ops.seg_batch_aug(self.images, self.offsets, self.labels, self.d_hs, self.d_ws, p[0], p[1], p[2], p[3], p[4], p[5],
                                     sizes[b][0], sizes[b][1], self.max_shrink)
 
@@ -269,6 +374,59 @@ def load_voc(root, year="2012", image_set="train"):
     for x in names:
         images.append(np.asarray(Image.open(os.path.join(voc_root, "JPEGImages", x + ".jpg")).convert("RGB"), dtype=np.uint8))
         labels.append(np.asarray(Image.open(os.path.join(mask_dir, x + ".png")), dtype=np.uint8))
+    return images, labels
+
+
+# datasets/cityscapes.py:25-66: id_to_train_id, the 35 entries (ids 0..33 and the license plate's -1, which numpy indexing puts last)
+CITYSCAPES_TRAIN_IDS = (255, 255, 255, 255, 255, 255, 255, 0, 1, 255, 255, 2, 3, 4, 255, 255, 255, 5, 255, 6, 7, 8, 9, 10, 11, 12, 13, 14,
+                        15, 255, 255, 16, 17, 18, 255)
+
+
+def _train_id_table():
+    """256 entries: label id -> train id; ids past the reference's 35 map to -1 here and are refused by load_cityscapes."""
+    t = np.full(256, -1, np.int16)
+    t[:len(CITYSCAPES_TRAIN_IDS)] = CITYSCAPES_TRAIN_IDS
+    return t
+
+
+def encode_cityscapes(label_ids):
+    """Cityscapes.encode_target on an HW uint8 array of label ids -> HW uint8 train ids (0..18, 255 = ignore).  An id of 35 or more
+    raises ValueError (the reference's table lookup raises IndexError there)."""
+    out = _train_id_table()[np.asarray(label_ids, dtype=np.uint8)]
+    if (out < 0).any():
+        raise ValueError(f"a Cityscapes label id of {int(np.asarray(label_ids)[out < 0].max())}: the table has {len(CITYSCAPES_TRAIN_IDS)} ids")
+    return out.astype(np.uint8)
+
+
+def load_cityscapes(root, split="train"):
+    """datasets/cityscapes.py:73-102: leftImg8bit/<split>/<city>/*_leftImg8bit.png with gtFine/<split>/<city>/*_gtFine_labelIds.png,
+    decoded ONCE on the host with Pillow into (list of HWC uint8, list of HW uint8).  Cities and files are read in SORTED order (the
+    reference takes os.listdir's, which is the file system's).  id_to_train_id is applied here, through a 256-entry table, so the
+    resident labels are train ids: the mapping is pointwise and commutes with the crop and the flip, which the reference applies first.
+    There is no download here."""
+    try:
+        from PIL import Image
+    except ImportError as e:
+        raise ImportError("load_cityscapes decodes PNG files with Pillow, which is not installed; --synthetic N needs no files") from e
+    if split not in ("train", "test", "val"):
+        raise ValueError('Invalid split! Please use split="train", split="test" or split="val"')
+    images_dir, targets_dir = os.path.join(root, "leftImg8bit", split), os.path.join(root, "gtFine", split)
+    if not os.path.isdir(images_dir) or not os.path.isdir(targets_dir):
+        raise FileNotFoundError(f"Cityscapes '{split}' not found under {root} (expected {images_dir} and {targets_dir}); "
+                                "there is no download in this build")
+    images, labels = [], []
+    for city in sorted(os.listdir(images_dir)):
+        img_dir = os.path.join(images_dir, city)
+        if not os.path.isdir(img_dir):
+            continue
+        for name in sorted(os.listdir(img_dir)):
+            if not name.endswith("_leftImg8bit.png"):
+                continue
+            target = os.path.join(targets_dir, city, name.split("_leftImg8bit")[0] + "_gtFine_labelIds.png")
+            images.append(np.asarray(Image.open(os.path.join(img_dir, name)).convert("RGB"), dtype=np.uint8))
+            labels.append(encode_cityscapes(np.asarray(Image.open(target), dtype=np.uint8)))
+    if not images:
+        raise FileNotFoundError(f"Cityscapes '{split}' under {root} holds no *_leftImg8bit.png; there is no download in this build")
     return images, labels
 
 

@@ -15,7 +15,7 @@ from . import ops, resnet_s
 from .arena import ArenaSGD, ParamArena
 from .deeplab import PolyLR, set_bn_momentum
 from .grid_guard import GuardedTrainer
-from .seg_attack_algo import seg_train_phases, seg_train_step
+from .seg_attack_algo import _f32_logits, seg_train_phases, seg_train_step
 
 
 class SegTrainer(GuardedTrainer):
@@ -80,6 +80,10 @@ class SegTrainer(GuardedTrainer):
     def _body(self, images, labels):
         return seg_train_step(self.model, self.optimizer, self.criterion, images, labels, **self.kw)
 
+    def _phases(self, images, labels, out):
+        """The iteration as a generator that yields where a part of the gradients is final (what a subclass replaces with _body)."""
+        return seg_train_phases(self.model, self.optimizer, self.criterion, images, labels, out, **self.kw)
+
     # ---- data parallel: the tail's gradients (everything behind the SE point: layer4, ASPP, decoder — 53 % of DeepLabv3+
     # ResNet-101's 58.7 M parameters, the LAST contiguous range of the arena) are final when seg_train_phases yields "tail";
     # their all-reduce starts there, on the side stream, and runs under the head's backward.  The rest follows at finish().
@@ -101,7 +105,7 @@ class SegTrainer(GuardedTrainer):
         out, rng = {}, self._tail_range()
         if self.reducer is not None:
             self.reducer.begin(explicit=True)
-        for ph in seg_train_phases(self.model, self.optimizer, self.criterion, images, labels, out, **self.kw):
+        for ph in self._phases(images, labels, out):
             if ph == "tail" and self.reducer is not None and rng is not None:
                 self.reducer.launch_params(*rng)
         return out
@@ -138,7 +142,7 @@ class SegTrainer(GuardedTrainer):
             return out
         # one hipGraph per phase (shared memory pool): between two replays the host starts the tail's all-reduce
         out, pieces, pool = {}, [], None
-        gen = seg_train_phases(self.model, self.optimizer, self.criterion, self._static[0], self._static[1], out, **self.kw)
+        gen = self._phases(self._static[0], self._static[1], out)
         done, fused = False, []
         try:
             while not done:
@@ -200,3 +204,53 @@ class SegTrainer(GuardedTrainer):
             out = self._run_phases(images, labels) if self._phased() else self._body(images, labels)
         self._exchange_and_step()
         return out
+
+
+def seg_base_phases(model, optimizer, criterion, images, labels, out, *, defer_step=False):
+    """The baseline iteration, Segmentation/main_ori.py:158-163, as a generator in seg_train_phases' form: one train-mode forward,
+    the cross-entropy on the upsampled logits (on the LOW-resolution logits where the one-pass kernel takes them), backward, step.
+    Nothing is final before the end of the backward, so it never yields."""
+    from .deeplab import seg_criterion
+    criterion = seg_criterion(criterion)
+    if images.is_cuda:
+        ops.acc_reset(images.device)            # BatchNorm accumulator arena: one memset per iteration
+    optimizer.zero_grad()
+    low = bool(getattr(criterion, "low_res", False))
+    o = model({"x": images, "adv": None, "out_idx": 0, "flag": "clean", "low_res": low})
+    if getattr(criterion, "fused", False) and _f32_logits(o):
+        loss = criterion(o, labels, grad_scale=1.0)
+        torch.autograd.backward([loss], [ops.one(images.device)])
+    else:
+        loss = criterion(o, labels)
+        loss.backward()
+    if not defer_step:
+        optimizer.step()
+    out.update({"loss": loss.detach()})
+    return
+    yield
+
+
+class SegBaseTrainer(SegTrainer):
+    """The segmentation baseline (Segmentation/main_ori.py): SegTrainer's arena, two-group SGD, schedule, BatchNorm momentum, graph
+    capture, grid guard and data-parallel exchange around the plain iteration — no PGD, no mixing.  step() returns {"loss": ...}."""
+
+    def __init__(self, model, criterion=None, *, lr=0.01, momentum=0.9, weight_decay=1e-4, total_itrs=30000, lr_policy="poly",
+                 step_size=10000, backbone_bn_momentum=0.01, use_graph=True, graph_warmup=2, group=None, allreduce_chunks=4,
+                 segmented=None, wgrad_stream=None):
+        super().__init__(model, criterion, lr=lr, momentum=momentum, weight_decay=weight_decay, total_itrs=total_itrs,
+                         lr_policy=lr_policy, step_size=step_size, backbone_bn_momentum=backbone_bn_momentum, use_graph=use_graph,
+                         graph_warmup=graph_warmup, group=group, allreduce_chunks=allreduce_chunks, segmented=segmented,
+                         wgrad_stream=wgrad_stream)
+        self.kw = {"defer_step": True} if self.kw.get("defer_step") else {}
+
+    def _phases(self, images, labels, out):
+        return seg_base_phases(self.model, self.optimizer, self.criterion, images, labels, out, **self.kw)
+
+    def _body(self, images, labels):
+        out = {}
+        for _ in self._phases(images, labels, out):
+            pass
+        return out
+
+    def _tail_range(self):
+        return None

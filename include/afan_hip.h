@@ -820,6 +820,25 @@ int afan_seg_batch_aug_u8(const uint8_t* images, const int64_t* img_off, const u
                           const int64_t* top, const int64_t* left, const int64_t* flip, float* out, int64_t* labels_out,
                           int64_t m, int64_t out_h, int64_t out_w, double max_shrink, afan_stream_t stream);
 
+/* afan_seg_batch_aug_u8 with ExtColorJitter(brightness, contrast, saturation) between the crop and the flip (the reference's
+ * Cityscapes training transform, Segmentation/args.py:143-148): torchvision's PIL functional, i.e. Pillow's ImageEnhance.Brightness /
+ * Contrast / Color, each Image.blend(degenerate, image, factor) on the uint8 output of the one before, bit for bit
+ * (seg_data._jitter_numpy restates it).  Per sample: order[b], int64 code 0..5 = the permutations of (brightness, contrast,
+ * saturation) in lexicographic order, CLAMPED into [0, 5]; brightness[b], contrast[b], saturation[b]: the fp32 factors.
+ * The blend is t = d + f * (i - d) in fp32 with the product and the sum rounded separately (no fma); 0 <= f <= 1: (uint8)t, else 0 for
+ * t <= 0, 255 for t >= 255.  d: 0 (brightness); int(S / n + 0.5) in double (contrast), S the integer sum of the gray values
+ * (19595 R + 38470 G + 7471 B + 0x8000) >> 16 over the whole out_h x out_w crop, padding included, as it is when contrast's turn comes;
+ * the pixel's own gray value (saturation).  A non-finite factor gives 0 where the blend is not finite (callers refuse it).
+ * gray_sum: caller's int64 [m] workspace for S.  The call enqueues a launch that clears it, a statistics launch (one 64-bit integer
+ * atomic add per workgroup: the sums do not depend on scheduling) and the batch launch, all on `stream`; no grid barrier, no host
+ * synchronisation, capturable into a graph.  Errors as afan_seg_batch_aug_u8 (brightness / contrast / saturation 4-byte, order and
+ * gray_sum 8-byte aligned). */
+int afan_seg_batch_aug_jitter_u8(const uint8_t* images, const int64_t* img_off, const uint8_t* labels, const int32_t* hs,
+                                 const int32_t* ws, int64_t n_src, int64_t total_pixels, const int64_t* index, const int64_t* oh,
+                                 const int64_t* ow, const int64_t* top, const int64_t* left, const int64_t* flip, const int64_t* order,
+                                 const float* brightness, const float* contrast, const float* saturation, int64_t* gray_sum, float* out,
+                                 int64_t* labels_out, int64_t m, int64_t out_h, int64_t out_w, double max_shrink, afan_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Measurement aid (no reference counterpart): per-launch HIP-event timing of the kernels above, recorded
  * on the launch stream.  afan_profile_enable(1) starts recording (launches are then not graph-capturable),
