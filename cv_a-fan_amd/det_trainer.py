@@ -13,7 +13,7 @@ import torch
 
 from .arena import ArenaSGD, ParamArena
 from .det_attack_algo import det_train_phases
-from .grid_guard import GuardedTrainer
+from .train_step import StepTrainer
 
 # everything behind the conv4 feature map: layer4 (= detection.hidden), the RPN and the two heads.  The backbone's unused ImageNet
 # classifier `features.fc` sits between them in the reference's parameter order and never receives a gradient: optim.SGD skips a
@@ -23,24 +23,16 @@ TAIL_PREFIXES = ("features.layer4.", "features.fc.", "rpn.", "detection.")
 UNUSED_PARAMS = ("features.fc.weight", "features.fc.bias")
 
 
-class DetTrainer(GuardedTrainer):      # (frozen BatchNorm: no grid barrier on this path; flush_guard() is the uniform no-op)
+class DetTrainer(StepTrainer):
+    """Of StepTrainer only the exchange set-up: frozen BatchNorm (no grid barrier on this path: flush_guard() is the uniform no-op),
+    no graph of its own, and a step of three inputs."""
+
     def __init__(self, model, *, lr=0.001, momentum=0.9, weight_decay=0.0005, loss_settings=1, group=None, allreduce_chunks=4,
                  segmented=None, arena=None, noise_ahead=False):
-        import torch.distributed as dist
-        self.model, self.loss_settings, self.group = model, int(loss_settings), group
+        self.loss_settings = int(loss_settings)
         self.arena = arena if arena is not None else ParamArena(model, skip=UNUSED_PARAMS)
         self.optimizer = ArenaSGD(self.arena, lr, momentum, weight_decay)
-        self.world = dist.get_world_size(group) if dist.is_initialized() else 1
-        self.reducer = None
-        if self.world > 1:
-            from .train_step import GradAllReducer
-            self.reducer = GradAllReducer(self.arena, allreduce_chunks, group)
-            self.optimizer.grad_scale = 1.0 / self.world
-            for t in (self.arena.param, self.arena.momentum_buf):      # replicas start from rank 0's state
-                dist.broadcast(t, src=0, group=group)
-            for b in model.buffers():
-                dist.broadcast(b, src=0, group=group)
-            self.arena.refresh_shadow()
+        self._init_exchange(model, group, allreduce_chunks)
         # the next iteration's image-PGD noise drawn behind this iteration's backward (det_attack_algo.NoiseAhead): same generator
         # stream provided the caller draws nothing from the host generator between iterations
         from .det_attack_algo import NoiseAhead

@@ -223,11 +223,6 @@ class GuardedTrainer:
     def _drop_graphs(self):
         pass
 
-    def _guard_sync_ranks(self, group=None):
-        """Data parallel, between the gradient exchange and the optimizer launch."""
-        if self._guard is not None:
-            self._guard.sync_ranks(group)
-
     def _guarded(self, inputs, run):
         g = self._guard
         if g is None or not any(torch.is_tensor(t) and t.is_cuda for t in inputs):

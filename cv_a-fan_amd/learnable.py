@@ -10,13 +10,12 @@ blend and its d/dw reduction (`afan_mix_w*`), the whole-arena SGD.  The nine-ele
 own momentum SGD, the projection) stays on torch ops, as in the reference."""
 import torch
 
-from .grid_guard import GuardedTrainer
-
 from . import ops
 from .arena import ArenaSGD, ParamArena
 from .attack_algo import PGD
 from . import resnet_s
 from .resnet_s import _like_layout
+from .train_step import StepTrainer
 
 LEARNABLE_IDX = (4, 8, 11, 14, 18, 21, 24, 28, 31)   # main_learnable.py:59
 
@@ -43,8 +42,13 @@ class _MixW(torch.autograd.Function):
         return dw, None, None, None, None
 
 
-class LearnableTrainer(GuardedTrainer):
-    """Owns the backbone arena + SGD (sequential_model parameters only, :82-84) and the optimizer of `w` (:86-90)."""
+class LearnableTrainer(StepTrainer):
+    """Owns the backbone arena + SGD (sequential_model parameters only, :82-84) and the optimizer of `w` (:86-90).
+
+    step(inp, target) returns device tensors (loss, loss_clean, loss_adv, l1, l2[9,N], linf[9,N], prec1, w, out_clean);
+    `flush_guard()` at every logging interval (grid_guard.py)."""
+    _what = "the learnable A-FAN step"
+    _small = ("loss", "loss_clean", "loss_adv", "l1", "l2", "linf", "prec1", "w")      # everything but out_clean
 
     def __init__(self, model, criterion, *, steps=3, gamma=1.0, eps=2.0, idx_list=LEARNABLE_IDX, layer_number=None,
                  randinit=False, clip=False, lr=0.1, w_lr=0.01, l1_coef=1.0, momentum=0.9, weight_decay=5e-4,
@@ -63,11 +67,7 @@ class LearnableTrainer(GuardedTrainer):
                                            momentum=momentum, weight_decay=0)
         # hipGraph replay of the whole iteration (~2 500 launches on ResNet-56s), as AfanTrainer does; randinit draws on
         # the host generator every step and therefore stays eager
-        self.use_graph = bool(use_graph) and not randinit
-        self.graph_warmup = graph_warmup
-        self._graph = self._graph_failed = self._static = self._out = self._key = None
-        self._eager_steps = 0
-        self._guard_init(model, self.arena.param.device)      # a grid barrier that gives up: grid_guard.py
+        self._init_schedule(bool(use_graph) and not randinit, graph_warmup)
 
     # `w` and its optimizer are torch's own (nine floats): the device guard does not cover them, the ring keeps their clones
     def _guard_state(self):
@@ -85,58 +85,6 @@ class LearnableTrainer(GuardedTrainer):
                 st.pop("momentum_buffer", None)
             else:
                 st["momentum_buffer"].copy_(mb)
-
-    def _drop_graphs(self):
-        self._graph = self._graph_failed = self._static = self._out = self._key = None
-
-    def step(self, inp, target):
-        """One iteration; returns device tensors (loss, loss_clean, loss_adv, l1, l2[9,N], linf[9,N], prec1, w).
-        `flush_guard()` at every logging interval (grid_guard.py)."""
-        return self._guarded((inp, target), self._step_once)
-
-    def _step_once(self, inp, target):
-        key = (tuple(inp.shape), inp.dtype, tuple(target.shape))
-        if self._graph is not None and self._key == key:
-            return self._replay(inp, target)
-        if (self.use_graph and self._graph is None and self._graph_failed is None and inp.is_cuda
-                and self._eager_steps >= self.graph_warmup and self.model.training and self._graph_safe()):
-            try:
-                self._capture(inp, target, key)
-                return self._replay(inp, target)
-            except Exception as e:  # noqa: BLE001 — stay correct: fall back to eager launches, loudly
-                import warnings
-                self._graph, self._graph_failed = None, e
-                warnings.warn(f"hipGraph capture of the learnable A-FAN step failed ({type(e).__name__}: {e}); running eagerly")
-                torch.cuda.synchronize()
-        self._eager_steps += 1
-        self.optimizer._sync_lr()
-        return self._body(inp, target)
-
-    def _graph_safe(self):
-        """As AfanTrainer._graph_safe (every configuration runs on the library's own kernels: nothing to exclude)."""
-        if resnet_s.vendor_convs(self.model):
-            self.use_graph = False
-        return self.use_graph
-
-    def _capture(self, inp, target, key):
-        dev = inp.device
-        self._static = (torch.empty_like(inp), torch.empty_like(target))
-        self._static[0].copy_(inp)
-        self._static[1].copy_(target)
-        stream = torch.cuda.Stream(device=dev)
-        stream.wait_stream(torch.cuda.current_stream(dev))
-        torch.cuda.synchronize(dev)
-        g = torch.cuda.CUDAGraph()
-        with ops.no_gc_during_capture(), torch.cuda.graph(g, stream=stream, capture_error_mode="thread_local"):
-            out = self._body(self._static[0], self._static[1])
-        self._graph, self._out, self._key = g, out, key
-
-    def _replay(self, inp, target):
-        self._static[0].copy_(inp, non_blocking=True)
-        self._static[1].copy_(target, non_blocking=True)
-        self.optimizer._sync_lr()          # lr lives in device memory: the graph reads it, the host only writes it here
-        self._graph.replay()
-        return {k: v.clone() for k, v in self._out.items() if k != "out_clean"} | {"out_clean": self._out["out_clean"]}
 
     def _body(self, inp, target):
         m, ln = self.model, self.layer_number

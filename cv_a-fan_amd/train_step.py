@@ -11,6 +11,9 @@ everything that is not a convolution, one fused SGD launch over the parameter ar
 world_size > 1 — a chunked RCCL all-reduce of the flat gradient arena that overlaps the rest of the
 backward (data parallel: the PGD loop itself needs no communication).
 """
+import contextlib
+import time
+
 import torch
 import torch.distributed as dist
 
@@ -234,38 +237,44 @@ def _out_shape(mod, c, h, w):
 
 
 class StepTrainer(GuardedTrainer):
-    """What the trainers of one rank share, whatever their iteration body: the parameter arena and its fused SGD (learning rate in
-    device memory), the gradient exchange (GradAllReducer, or NullReducer for the data-parallel program on one GPU), the grid-barrier
-    guard, and the eager-then-captured schedule — `graph_warmup` eager iterations, then one capture per input shape, replayed from
-    then on; a failed capture falls back to eager launches with a warning.  A subclass provides _step_eager, _capture and
-    _step_graph."""
-    _what = "the step"
+    """What the trainers of one rank share, whatever their iteration: the gradient exchange set-up (_init_exchange), the grid-barrier
+    guard, and the eager-then-captured schedule — `graph_warmup` eager iterations, then ONE hipGraph capture, of the first input shape
+    seen after them, replayed from then on for that shape; every other shape runs eagerly, and so does everything after a failed
+    capture (with a warning).  _drop_graphs (a grid barrier gave up) forgets the graphs and the failure but not the eager count: the
+    next step captures again.
 
-    def _init_state(self, model, criterion, lr, momentum, weight_decay, allreduce_chunks, group, emulate_dp):
-        self.model, self.criterion = model, criterion
-        self.arena = ParamArena(model)
-        self.optimizer = ArenaSGD(self.arena, lr, momentum, weight_decay)
-        self.group = group
+    A subclass says what one iteration is — `_body(inp, target)`, the whole eager iteration, returning the observables; `_graph_body`
+    (what of it one graph holds; default: all of it) and `_after_replay` (the rest) — or, where parameter ranges become final during
+    the backward, `_use_phases` / `_phases(inp, target, out)`: a generator that yields a label at each such point, captured as one
+    graph per next() with the range `_range_of(label)` announced to the reducer between two replays, and followed by `_update`.
+    `_small` names the outputs that are cloned on replay (the others are views of graph-owned buffers, valid until the next step),
+    `_around(inp)` is a context around capture and eager execution (not replay), `_what` the iteration's name in the warning."""
+    _what = "the step"
+    _small = ()
+    reducer, group, world = None, None, 1
+
+    def _init_exchange(self, model, group=None, allreduce_chunks=4, emulate_dp=False):
+        """After self.arena and self.optimizer exist: the reducer (GradAllReducer between ranks; NullReducer for the data-parallel
+        program on one GPU; else none), 1/world in the SGD kernel (the all-reduce is a plain SUM), replicas equal to rank 0."""
+        self.model, self.group = model, group
         self.world = dist.get_world_size(group) if dist.is_initialized() else 1
-        self.reducer = GradAllReducer(self.arena, allreduce_chunks, group) if self.world > 1 else None
-        if self.world <= 1 and emulate_dp:
-            self.reducer = NullReducer(self.arena)      # one GPU, the data-parallel program (see NullReducer)
+        self.reducer = None
+        if self.world > 1:
+            self.reducer = GradAllReducer(self.arena, allreduce_chunks, group)
+        elif emulate_dp:
+            self.reducer = NullReducer(self.arena)
+        self.optimizer.grad_scale = 1.0 / self.world
+        self.sync_replicas()
+
+    def _init_schedule(self, use_graph, graph_warmup):
         # a grid barrier of the in-launch BatchNorm that gives up: detected every step without a host synchronisation, no update
         # applied meanwhile (the optimizer's device-side guard), the lost steps run again on the two-launch forms (grid_guard.py)
-        self._guard_init(model, self.arena.param.device)
-
-    def _init_graph(self, use_graph, graph_warmup):
+        self._guard_init(self.model, self.arena.param.device)
         self.use_graph = bool(use_graph)
         self.graph_warmup = graph_warmup
-        self._pieces = None
-        self._graph = None
-        self._graph_failed = None
-        self._graph_unsafe = None
         self._eager_steps = 0
-        self._static_in = None
-        self._static_out = None
-        self._shape_key = None
         self._stream = None
+        self._drop_graphs()
 
     def sync_replicas(self, src=0):
         """Every rank starts from rank `src`'s parameters, momentum and BatchNorm buffers (the reference's nn.DataParallel
@@ -274,22 +283,9 @@ class StepTrainer(GuardedTrainer):
         if not dist.is_initialized() or self.world <= 1:
             return
         a = self.arena
-        for t in (a.param, a.momentum_buf):
+        for t in (a.param, a.momentum_buf, *self.model.buffers()):
             dist.broadcast(t, src=src, group=self.group)
-        for b in self.model.buffers():
-            dist.broadcast(b, src=src, group=self.group)
         a.refresh_shadow()
-
-    def _graph_safe(self):
-        """Every configuration runs on the library's own kernels (tuned bf16 or general f32 MFMA) and is capturable; a
-        convolution that left the library would be listed by resnet_s.vendor_convs (empty by construction) and keep the
-        step eager: rounds 1-2 measured a captured vendor input-gradient pass reading memory the graph did not own."""
-        if self._graph_unsafe is None:
-            from . import resnet_s
-            self._graph_unsafe = resnet_s.vendor_convs(self.model) if hasattr(self.model, "sequential_model") else []
-            if self._graph_unsafe:
-                self.use_graph = False
-        return not self._graph_unsafe
 
     def _pre_sgd(self):
         """Data parallel: the grid barrier's error word becomes the maximum over the ranks before the (device-guarded) optimizer
@@ -297,23 +293,52 @@ class StepTrainer(GuardedTrainer):
         if self._guard is not None and self.world > 1:
             self._guard.sync_ranks(self.group)
 
+    def _update(self):
+        """What follows the last phase or piece: the end of the exchange, the ranks' agreement, the SGD launch."""
+        if self.reducer is not None:
+            self.reducer.finish()          # whatever no launch_params() announced is reduced here
+        self._pre_sgd()
+        self.optimizer.step()
+
     def _drop_graphs(self):
         """After a grid barrier gave up: the captured graphs hold in-launch-BatchNorm launches; capture again (two-launch forms)."""
-        self._graph = self._pieces = self._static_in = self._static_out = self._shape_key = None
+        self._graph = self._pieces = self._pieces_fused = self._static_in = self._static_out = self._shape_key = None
         self._graph_failed = None
 
+    # ---- what a subclass says
+    def _use_phases(self, inp):
+        return False
+
+    def _piece_count(self):
+        """How many next() of _phases make the iteration (None: until the generator ends; that piece's label is None)."""
+        return None
+
+    def _range_of(self, label):
+        return label
+
+    def _graph_body(self, inp, target):
+        return self._body(inp, target)
+
+    def _after_replay(self):
+        pass
+
+    def _around(self, inp):
+        return contextlib.nullcontext()
+
+    # ---- the schedule
     def step(self, inp, target):
         """One iteration.  Returns device tensors only (see the subclass); no host synchronisation."""
         return self._guarded((inp, target), self._step_once)
 
     def _step_once(self, inp, target):
-        if self._graph is not None and self._shape_key == (tuple(inp.shape), inp.dtype, tuple(target.shape)):
+        key = (tuple(inp.shape), inp.dtype, tuple(target.shape))
+        if self._graph is not None and self._shape_key == key:
             return self._step_graph(inp, target)
         if (self.use_graph and self._graph is None and self._graph_failed is None
-                and self._eager_steps >= self.graph_warmup and inp.is_cuda and self.model.training
-                and self._graph_safe()):
+                and self._eager_steps >= self.graph_warmup and inp.is_cuda and self.model.training):
             try:
                 self._capture(inp, target)
+                self._shape_key = key
                 return self._step_graph(inp, target)
             except Exception as e:  # noqa: BLE001 — stay correct: fall back to eager launches, loudly
                 import warnings
@@ -322,6 +347,92 @@ class StepTrainer(GuardedTrainer):
                 torch.cuda.synchronize()
         self._eager_steps += 1
         return self._step_eager(inp, target)
+
+    def _announce(self, label):
+        rng = self._range_of(label)
+        if self.reducer is not None and rng is not None:
+            self.reducer.launch_params(*rng)
+
+    def _step_eager(self, inp, target):
+        self.optimizer._sync_lr()
+        with self._around(inp):
+            if not self._use_phases(inp):
+                return self._body(inp, target)
+            out = {}
+            if self.reducer is not None:
+                self.reducer.begin(explicit=True)
+            for label in self._phases(inp, target, out):
+                self._announce(label)
+        self._update()
+        return out
+
+    def _capture(self, inp, target):
+        """One hipGraph of _graph_body — or, in phases, one per next() of the generator (one memory pool): between two replays the
+        host starts the all-reduce of the range the finished piece completed (RCCL on the side stream), under the rest of the
+        backward.  Once per trainer lifetime (and after _drop_graphs), outside any timed region: a device synchronisation and the
+        learning rate's upload come first, never inside a capture."""
+        dev = inp.device
+        self._stream = stream = torch.cuda.Stream(device=dev)
+        static = (inp.clone(), target.clone())
+        stream.wait_stream(torch.cuda.current_stream(dev))
+        torch.cuda.synchronize(dev)
+        self.optimizer._sync_lr()
+        with self._around(inp):
+            if not self._use_phases(inp):
+                g = torch.cuda.CUDAGraph()
+                with _capturing(g, stream):
+                    out = self._graph_body(*static)
+                self._graph, self._static_in, self._static_out = g, static, out
+                return
+            out, pieces, fused, count = {}, [], [], self._piece_count()
+            gen = self._phases(*static, out)
+            try:
+                while True:
+                    n0 = ops.CALLS["conv_bn_fused"]
+                    g = torch.cuda.CUDAGraph()
+                    with _capturing(g, stream, pool=pieces[0][0].pool() if pieces else None):
+                        label = next(gen, None)
+                    pieces.append((g, label))
+                    fused.append(ops.CALLS["conv_bn_fused"] - n0)      # convolution + BatchNorm launches in this piece
+                    if label is None or len(pieces) == count:
+                        break
+                    if self.reducer is not None:
+                        # the replay starts an exchange HERE: whatever is captured from now on runs beside RCCL's resident kernels and
+                        # must not contain a grid barrier (the eager path gets the same switch from the reducer's own launches)
+                        ops.exchange_in_flight(True)
+            finally:
+                ops.exchange_in_flight(False)
+                gen.close()                # (no generator outlives the capture)
+        self._pieces, self._pieces_fused = pieces, fused
+        self._graph, self._static_in, self._static_out = pieces[0][0], static, out
+
+    def _step_graph(self, inp, target):
+        self._static_in[0].copy_(inp, non_blocking=True)
+        self._static_in[1].copy_(target, non_blocking=True)
+        self.optimizer._sync_lr()          # lr lives in device memory: the graph reads it, the host only writes it here
+        if self._pieces is None:
+            self._graph.replay()
+            self._after_replay()
+        else:
+            if self.reducer is not None:
+                self.reducer.begin(explicit=True)
+            for g, label in self._pieces:
+                g.replay()
+                t_ = time.perf_counter()
+                self._announce(label)
+                if self.reducer is not None:
+                    self.reducer.note_host_gap(time.perf_counter() - t_)
+            self._update()
+        # graph-owned outputs are overwritten by the next replay: hand out copies of the small ones
+        return {k: (v.clone() if k in self._small else v) for k, v in self._static_out.items()}
+
+
+@contextlib.contextmanager
+def _capturing(graph, stream, pool=None):
+    """torch.cuda.graph with what every capture here needs: no garbage collection meanwhile (freeing another trainer's graph or
+    stream in the middle of a capture aborts the process), errors confined to this thread."""
+    with ops.no_gc_during_capture(), torch.cuda.graph(graph, pool=pool, stream=stream, capture_error_mode="thread_local"):
+        yield
 
 
 class AfanTrainer(StepTrainer):
@@ -332,14 +443,18 @@ class AfanTrainer(StepTrainer):
     hipGraph and replayed from then on: static shapes, the learning rate in device memory and on-device metrics make
     the step capturable, and replay removes the host launch cost that otherwise bounds the step (PyTorch's eager
     dispatch + autograd tape is ~15 us per launch).  With world_size > 1 the graph stops after the backward and the
-    gradient all-reduce + SGD run eagerly.  randinit draws on the host generator every step, so it stays eager."""
+    gradient all-reduce + SGD run eagerly.  randinit draws on the host generator every step, so it stays eager.
+
+    step(inp, target) returns device tensors only: loss, loss_adv, loss_clean, prec1, l2[N], linf[N] (+ x_adv, feature_map,
+    out_clean — in graph mode these three are views of graph-owned buffers, valid until the next step)."""
     _what = "the A-FAN step"
+    _small = ("loss", "loss_adv", "loss_clean", "prec1", "l2", "linf")
 
     def __init__(self, model, criterion, *, steps=5, gamma=0.5, eps=2.0, perturb_idx=13, layer_number=None,
                  randinit=False, clip=False, lr=0.1, momentum=0.9, weight_decay=5e-4, allreduce_chunks=4,
                  group=None, use_graph=True, graph_warmup=3, batch_final=True,
                  share_head=True, fold_clean=None, segmented=None, dual_bn=False, emulate_dp=False):
-        self.model, self.criterion = model, criterion
+        self.criterion = criterion
         # dual-BN option (off = the reference's single BatchNorm set): adversarial features — every PGD pass and the
         # adversarial final pass — are normalised by an auxiliary BatchNorm set.  The first PGD pass is then no longer the
         # clean pass and the two final passes no longer share their affine parameters: no fold, no grouped final pass.
@@ -352,10 +467,9 @@ class AfanTrainer(StepTrainer):
         self.perturb_idx = perturb_idx
         self.layer_number = layer_number if layer_number is not None else model.layer_number
         self.randinit, self.clip = randinit, clip
-        self._init_state(model, criterion, lr, momentum, weight_decay, allreduce_chunks, group, emulate_dp)
-        if self.world > 1:
-            self.optimizer.grad_scale = 1.0 / self.world
-            self.sync_replicas()
+        self.arena = ParamArena(model)
+        self.optimizer = ArenaSGD(self.arena, lr, momentum, weight_decay)
+        self._init_exchange(model, group, allreduce_chunks, emulate_dp)
         import os
         # exchange the tail's gradients stage by stage while the rest of the backward runs (folded schedule); 0: one
         # blocking all-reduce after the backward (A/B, and the fallback if a piece-wise capture fails)
@@ -366,7 +480,7 @@ class AfanTrainer(StepTrainer):
         self.share_head = bool(share_head)
         self.fold_clean = fold_clean if fold_clean is None else bool(fold_clean)
         self._fold_auto = {}
-        self._init_graph(bool(use_graph) and not randinit, graph_warmup)
+        self._init_schedule(bool(use_graph) and not randinit, graph_warmup)
 
     # ------------------------------------------------------------------------------------------------ body
     FOLD_MIN_ELEMS = 0            # feature-map elements (batch x C x H x W) from which fold_clean=None folds (0: always)
@@ -464,7 +578,7 @@ class AfanTrainer(StepTrainer):
         idxs = [i for i, n in enumerate(self.arena.names) if n.startswith(pre)]
         return (idxs[0], idxs[-1] + 1) if idxs else (0, 0)
 
-    def _phases_folded(self, inp, target, out):
+    def _phases(self, inp, target, out):
         """The folded iteration (see _forward_backward_folded) as a generator for data-parallel runs: it yields the arena
         parameter range whose gradients have just become final — the tail stage by stage from the last one (the tail is
         run in segments, detached at the stage transitions, so that its backward can be issued piece by piece), then the
@@ -535,9 +649,12 @@ class AfanTrainer(StepTrainer):
                     "feature_map": feature_map, "out_clean": c_outs[-1].detach()})
         yield self._param_range(0, idx)
 
-    def _ddp_phases_ok(self, inp):
+    def _use_phases(self, inp):
         want = self.segmented or (self.ddp_overlap and self.reducer is not None)
         return bool(want and self._fold_ok(inp) and hasattr(self.model, "sequential_model"))
+
+    def _piece_count(self):
+        return len(self._tail_segments()) + 1      # one piece per tail segment + the head (nothing follows the last yield)
 
     def _forward_backward(self, inp, target, overlap_allreduce):
         if self._fold_ok(inp):
@@ -649,107 +766,22 @@ class AfanTrainer(StepTrainer):
         self._groupable_key, self._groupable = key, bool(ok)
         return self._groupable
 
-    def _step_eager(self, inp, target):
-        self.optimizer._sync_lr()
-        if self._ddp_phases_ok(inp):
-            out = {}
-            if self.reducer is not None:
-                self.reducer.begin(explicit=True)
-            for rng in self._phases_folded(inp, target, out):
-                if self.reducer is not None:
-                    self.reducer.launch_params(*rng)
-            if self.reducer is not None:
-                self.reducer.finish()
-            self._pre_sgd()
-            self.optimizer.step()
-            return out
+    def _body(self, inp, target):
         out = self._forward_backward(inp, target, overlap_allreduce=self.reducer is not None)
-        if self.reducer is not None:
-            self.reducer.finish()
-        self._pre_sgd()
-        self.optimizer.step()
+        self._update()
         return out
 
-    # ----------------------------------------------------------------------------------------------- graph
-    def _capture_pieces(self, inp, target):
-        """Data-parallel capture: one hipGraph per phase of _phases_folded; between two replays the host starts the
-        all-reduce of the range the finished piece completed (RCCL on the side stream), so the exchange of the last
-        stage's gradients — most of the bytes — runs under the rest of the backward.  The pieces share one memory pool."""
-        dev = inp.device
-        self._stream = torch.cuda.Stream(device=dev)
-        self._static_in = (inp.clone(), target.clone())
-        self._stream.wait_stream(torch.cuda.current_stream(dev))
-        torch.cuda.synchronize(dev)
-        out, pieces, pool, fused = {}, [], None, []
-        gen = self._phases_folded(self._static_in[0], self._static_in[1], out)
-        try:
-            for _ in range(len(self._tail_segments()) + 1):      # one piece per tail segment + the head (nothing follows the last)
-                n0 = ops.CALLS["conv_bn_fused"]
-                g = torch.cuda.CUDAGraph()
-                with ops.no_gc_during_capture(), torch.cuda.graph(g, pool=pool, stream=self._stream, capture_error_mode="thread_local"):
-                    rng = next(gen)
-                fused.append(ops.CALLS["conv_bn_fused"] - n0)
-                pieces.append((g, rng))
-                pool = pieces[0][0].pool()
-                if self.reducer is not None:
-                    # the replay starts an exchange HERE: whatever is captured from now on runs beside RCCL's resident kernels and
-                    # must not contain a grid barrier (the eager path gets the same switch from the reducer's own launches)
-                    ops.exchange_in_flight(True)
-        finally:
-            ops.exchange_in_flight(False)
-        gen.close()
-        self._pieces_fused = fused          # convolution + BatchNorm launches captured per piece (data parallel: 0 after the first)
-        self._pieces, self._static_out = pieces, out
-        self._graph = pieces[0][0]
-        self._shape_key = (tuple(inp.shape), inp.dtype, tuple(target.shape))
+    def _graph_body(self, inp, target):
+        out = self._forward_backward(inp, target, overlap_allreduce=False)
+        if self.world == 1:
+            self.optimizer.step()
+        return out
 
-    def _capture(self, inp, target):
-        if self._ddp_phases_ok(inp):
-            return self._capture_pieces(inp, target)
-        dev = inp.device
-        self._stream = torch.cuda.Stream(device=dev)
-        self._static_in = (inp.clone(), target.clone())
-        self._stream.wait_stream(torch.cuda.current_stream(dev))
-        g = torch.cuda.CUDAGraph()
-        with ops.no_gc_during_capture(), torch.cuda.graph(g, stream=self._stream, capture_error_mode="thread_local"):
-            out = self._forward_backward(self._static_in[0], self._static_in[1], overlap_allreduce=False)
-            if self.world == 1:
-                self.optimizer.step()
-        self._graph, self._static_out = g, out
-        self._shape_key = (tuple(inp.shape), inp.dtype, tuple(target.shape))
-
-    def _step_graph(self, inp, target):
-        self._static_in[0].copy_(inp, non_blocking=True)
-        self._static_in[1].copy_(target, non_blocking=True)
-        self.optimizer._sync_lr()          # lr lives in device memory: the graph reads it, the host only writes it here
-        if self._pieces is not None:
-            if self.reducer is not None:
-                self.reducer.begin(explicit=True)
-            import time as _time
-            for g, rng in self._pieces:
-                g.replay()
-                t_ = _time.perf_counter()
-                if self.reducer is not None:
-                    self.reducer.launch_params(*rng)
-                    self.reducer.note_host_gap(_time.perf_counter() - t_)
-            if self.reducer is not None:
-                self.reducer.finish()
+    def _after_replay(self):
+        if self.world > 1:
+            dist.all_reduce(self.arena.grad, op=dist.ReduceOp.SUM, group=self.group)
             self._pre_sgd()
             self.optimizer.step()
-        else:
-            self._graph.replay()
-            if self.world > 1:
-                dist.all_reduce(self.arena.grad, op=dist.ReduceOp.SUM, group=self.group)
-                self._pre_sgd()
-                self.optimizer.step()
-        small = ("loss", "loss_adv", "loss_clean", "prec1", "l2", "linf")
-        # graph-owned outputs are overwritten by the next replay: hand out copies of the small ones
-        return {k: (v.clone() if k in small else v) for k, v in self._static_out.items()}
-
-    def step(self, inp, target):
-        """One iteration. Returns device tensors only: loss, loss_adv, loss_clean, prec1, l2[N], linf[N] (+ x_adv,
-        feature_map, out_clean — in graph mode these three are views of graph-owned buffers, valid until the next step)."""
-        return self._guarded((inp, target), self._step_once)
 
 
 class BaseTrainer(StepTrainer):
@@ -757,7 +789,7 @@ class BaseTrainer(StepTrainer):
     network (every BatchNorm updates its running statistics once), the criterion, zero_grad, backward, one fused SGD launch.
     The in-launch convolution + BatchNorm forms and the block fusions apply as in AfanTrainer's passes — the layers are the same.
 
-    use_graph=True (default): after `graph_warmup` eager iterations the iteration is captured once per input shape and replayed.
+    use_graph=True (default): after `graph_warmup` eager iterations the iteration is captured once and replayed (StepTrainer).
     Data parallel (or emulate_dp=True, the same program on one GPU): the graph ends after the backward; one blocking all-reduce of the
     gradient arena, the ranks' agreement on the barrier error word and the guarded SGD launch follow eagerly.  Nothing is launched
     between the exchange's start and its end, so no grid barrier can meet it.
@@ -765,15 +797,16 @@ class BaseTrainer(StepTrainer):
     step(inp, target) returns device tensors only: loss, prec1, out_clean (in graph mode a view of a graph-owned buffer, valid
     until the next step)."""
     _what = "the baseline step"
+    _small = ("loss", "prec1")
 
     def __init__(self, model, criterion, *, lr=0.1, momentum=0.9, weight_decay=5e-4, allreduce_chunks=4, group=None,
                  use_graph=True, graph_warmup=3, emulate_dp=False):
-        self._init_state(model, criterion, lr, momentum, weight_decay, allreduce_chunks, group, emulate_dp)
-        if self.world > 1:
-            self.optimizer.grad_scale = 1.0 / self.world        # the all-reduce is a plain SUM
-            self.sync_replicas()
+        self.criterion = criterion
+        self.arena = ParamArena(model)
+        self.optimizer = ArenaSGD(self.arena, lr, momentum, weight_decay)
+        self._init_exchange(model, group, allreduce_chunks, emulate_dp)
         self.layer_number = model.layer_number
-        self._init_graph(use_graph, graph_warmup)
+        self._init_schedule(use_graph, graph_warmup)
 
     def _forward_backward(self, inp, target):
         from . import resnet_s
@@ -792,39 +825,19 @@ class BaseTrainer(StepTrainer):
             prec1 = (output_clean.argmax(dim=1) == target).float().sum() * (100.0 / target.shape[0])
         return {"loss": loss.detach(), "prec1": prec1, "out_clean": output_clean.detach()}
 
-    def _exchange_and_update(self):
+    def _graph_body(self, inp, target):
+        out = self._forward_backward(inp, target)
+        if self.reducer is None:
+            self.optimizer.step()
+        return out
+
+    def _after_replay(self):
         if self.reducer is not None:
             self.reducer.begin(explicit=True)
             self.reducer.launch_params(0, len(self.arena.params))        # the whole arena, one message
-            self.reducer.finish()
-        self._pre_sgd()
-        self.optimizer.step()
+            self._update()
 
-    def _step_eager(self, inp, target):
-        self.optimizer._sync_lr()
-        out = self._forward_backward(inp, target)
-        self._exchange_and_update()
+    def _body(self, inp, target):
+        out = self._graph_body(inp, target)
+        self._after_replay()
         return out
-
-    def _capture(self, inp, target):
-        dev = inp.device
-        self._stream = torch.cuda.Stream(device=dev)
-        self._static_in = (inp.clone(), target.clone())
-        self._stream.wait_stream(torch.cuda.current_stream(dev))
-        g = torch.cuda.CUDAGraph()
-        with ops.no_gc_during_capture(), torch.cuda.graph(g, stream=self._stream, capture_error_mode="thread_local"):
-            out = self._forward_backward(self._static_in[0], self._static_in[1])
-            if self.reducer is None:
-                self.optimizer.step()
-        self._graph, self._static_out = g, out
-        self._shape_key = (tuple(inp.shape), inp.dtype, tuple(target.shape))
-
-    def _step_graph(self, inp, target):
-        self._static_in[0].copy_(inp, non_blocking=True)
-        self._static_in[1].copy_(target, non_blocking=True)
-        self.optimizer._sync_lr()          # lr lives in device memory: the graph reads it, the host only writes it here
-        self._graph.replay()
-        if self.reducer is not None:
-            self._exchange_and_update()
-        # graph-owned outputs are overwritten by the next replay: hand out copies of the small ones
-        return {k: (v.clone() if k in ("loss", "prec1") else v) for k, v in self._static_out.items()}

@@ -139,7 +139,18 @@ def test_trainers_tail_ranges_are_arena_suffixes(pkg):
 
 
 def test_trainer_sets_grad_scale_from_world(pkg):
-    """1/world lives in the fused SGD kernel's grad_scale (the all-reduce is a plain SUM)."""
+    """1/world lives in the fused SGD kernel's grad_scale (the all-reduce is a plain SUM): set in the one exchange set-up,
+    StepTrainer._init_exchange, which every data-parallel trainer's constructor reaches (its own, or the one it hands over to)."""
     import inspect
-    src = inspect.getsource(pkg.train_step.AfanTrainer.__init__)
-    assert "grad_scale = 1.0 / self.world" in src
+    ts = pkg.train_step
+    assert "grad_scale = 1.0 / self.world" in inspect.getsource(ts.StepTrainer._init_exchange)
+
+    def reaches(cls):
+        if "__init__" not in vars(cls):
+            return reaches(cls.__mro__[1])
+        src = inspect.getsource(cls.__init__)
+        return "self._init_exchange(" in src or ("super().__init__(" in src and reaches(cls.__mro__[1]))
+
+    for cls in (ts.AfanTrainer, ts.BaseTrainer, pkg.seg_trainer.SegTrainer, pkg.seg_trainer.SegBaseTrainer, pkg.det_trainer.DetTrainer):
+        assert issubclass(cls, ts.StepTrainer) and reaches(cls), cls
+        assert "_init_exchange" not in vars(cls), cls

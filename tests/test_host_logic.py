@@ -329,6 +329,18 @@ def test_buffer_arena_keeps_the_state_dict_contract(pkg):
     assert bn.running_mean.data_ptr() >= ba.f32.data_ptr() and torch.equal(bn.running_mean, sd2[[k for k in sd2 if k.endswith("running_mean")][0]])
 
 
+def test_every_graph_capable_trainer_runs_the_one_schedule(pkg):
+    """The eager-then-captured schedule is written once (train_step.StepTrainer): no trainer carries a copy of it, and the dead
+    capture condition `_graph_safe` (resnet_s.vendor_convs is empty by construction) is gone from all of them."""
+    ts = pkg.train_step
+    capable = (ts.AfanTrainer, ts.BaseTrainer, pkg.seg_trainer.SegTrainer, pkg.seg_trainer.SegBaseTrainer, pkg.learnable.LearnableTrainer)
+    for cls in capable:
+        assert issubclass(cls, ts.StepTrainer)
+        assert cls._step_once is ts.StepTrainer._step_once, cls
+    for cls in capable + (pkg.det_trainer.DetTrainer, ts.StepTrainer):
+        assert not hasattr(cls, "_graph_safe"), cls
+
+
 def test_trainer_and_guard_form_no_reference_cycle(pkg):
     """A trainer must die by reference count (its hipGraphs, streams and events with it): grid_guard.GridGuard keeps only a WEAK
     reference to the trainer's `_drop_graphs` — a strong one made every trainer wait for a cyclic garbage collection, which once ran
