@@ -4,9 +4,11 @@ The directory name carries a hyphen (it is fixed by the build contract), so impo
     import importlib; afan = importlib.import_module("cv_a-fan_amd")
 Sub-modules: attack_algo (PGD & friends, reference signatures), resnet_s (slice-protocol models),
 arena (flat parameter arena + fused SGD), train_step (the joint step, data parallel), ops (tensor
-wrappers over the C-ABI in include/afan_hip.h), main_perturb (entry point for cmd/run_perturb.sh; DeviceLoader: one-launch batches), main_base (the baseline trainer, cmd/run_base.sh), infer (the fused, graph-replayed eval forward; main_inference evaluates a checkpoint), deeplab (the
+wrappers over the C-ABI in include/afan_hip.h), cls_data (DeviceLoader: one-launch CIFAR batches), cls_entry (what the Classification entry points share: flags, set-up, the train / evaluation / epoch loops, the
+checkpoint files; main_perturb for cmd/run_perturb.sh, main_base for cmd/run_base.sh, main_learnable, main_inference), infer (the fused, graph-replayed eval forward; main_inference evaluates a checkpoint), deeplab (the
 DeepLabv3+ split-forward network), seg_attack_algo / seg_trainer (the Segmentation A-FAN operators and iteration), seg_data (SegDeviceLoader: one-launch
-segmentation batches; main_aug_final is the entry point for cmd/run_seg.sh), seg_eval (StreamSegMetrics with a one-launch confusion
+segmentation batches; main_aug_final is the entry point for cmd/run_seg.sh, main_ori for cmd/run_seg_base.sh), seg_entry (what the Segmentation entry
+points share: the parser, set-up, checkpoint and restore, the iteration loop), seg_eval (StreamSegMetrics with a one-launch confusion
 matrix, validate; main_seg_val scores a checkpoint, cmd/run_seg_val.sh), det_ops / det_attack_algo / det_model / det_trainer
 (the Detection operators, iteration, the Faster-RCNN / ResNet-101 model and its data-parallel trainer).
 """

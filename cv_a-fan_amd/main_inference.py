@@ -6,7 +6,7 @@ through the eval-mode model, infer.Attacker; `Robust:` lines in the format of th
 clean evaluation alone, its output unchanged.
 
 The checkpoint's `state_dict` is a main_perturb.py checkpoint's or one in the reference's layout (the same keys).  The
-CIFAR-10 test split is evaluated in file order with its last partial batch; the evaluation is main_perturb.validate
+CIFAR-10 test split is evaluated in file order with its last partial batch; the evaluation is cls_entry.validate
 (infer.Evaluator: one fused launch per convolution, per-batch results read back at --print_freq batches)."""
 import argparse
 import os
@@ -19,9 +19,10 @@ if __package__ in (None, ""):  # executed as a script (cmd/run_test.sh): import 
     import importlib
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     _pkg = importlib.import_module("cv_a-fan_amd")
-    resnet_s, infer, main_perturb = _pkg.resnet_s, _pkg.infer, importlib.import_module("cv_a-fan_amd.main_perturb")
+    resnet_s, infer = _pkg.resnet_s, _pkg.infer
+    cls_data, cls_entry = importlib.import_module("cv_a-fan_amd.cls_data"), importlib.import_module("cv_a-fan_amd.cls_entry")
 else:
-    from . import infer, main_perturb, resnet_s
+    from . import cls_data, cls_entry, infer, resnet_s
 
 parser = argparse.ArgumentParser(description="A-FAN CIFAR-10 checkpoint evaluation on MI355X")
 # ---- base setting (main_inference.py:28-32)
@@ -30,12 +31,7 @@ parser.add_argument("--print_freq", default=50, type=int, help="print frequency"
 parser.add_argument("--gpu", type=int, default=0, help="gpu device id")
 parser.add_argument("--pretrained", help="pretrained_model", default="res56s_cifar10_baseline", type=str)
 parser.add_argument("--batch_size", type=int, default=128, help="batch size")
-# ---- additions
-parser.add_argument("--arch", default="resnet56s", choices=sorted(resnet_s.ARCHS))
-parser.add_argument("--dtype", default="bf16", choices=["bf16", "fp32"], help="backbone compute dtype")
-parser.add_argument("--layout", default="nhwc", choices=["nhwc", "nchw"],
-                    help="internal activation / weight layout (nhwc: the library's MFMA convolutions; nchw: the general fp32-arithmetic kernels)")
-parser.add_argument("--synthetic", type=int, default=0, help="evaluate on N synthetic images instead of the CIFAR-10 test split")
+cls_entry.add_addition_flags(parser, max_iters=False, synthetic_help="evaluate on N synthetic images instead of the CIFAR-10 test split")
 # ---- robust accuracy (image-space L-inf PGD on the eval-mode model)
 parser.add_argument("--attack_steps", type=int, default=0, help="PGD steps of the robust-accuracy pass (0: clean evaluation only)")
 parser.add_argument("--attack_eps", type=float, default=8.0, help="L-inf radius of the attack, in /255 pixel units")
@@ -44,31 +40,12 @@ parser.add_argument("--attack_randinit", action="store_true", help="start the at
 
 
 def robust_validate(val_loader, model, criterion, args, log):
-    """The robust counterpart of main_perturb.validate: every batch attacked (infer.Attacker), the adversarial loss and precision
+    """The robust counterpart of cls_entry.validate: every batch attacked (infer.Attacker), the adversarial loss and precision
     kept on the device and read back at --print_freq batches and at the end, in batch order."""
-    losses, top1 = main_perturb.AverageMeter(), main_perturb.AverageMeter()
     model.eval()
     at = infer.Attacker(model, criterion, args.attack_eps / 255.0, args.attack_gamma / 255.0, args.attack_steps, args.attack_randinit)
     at.refresh()
-    pending = []
-
-    def flush():
-        for loss_t, prec_t, n in pending:
-            losses.update(loss_t.item(), n)
-            top1.update(prec_t.item(), n)
-        pending.clear()
-
-    for i, (inp, target) in enumerate(val_loader):
-        _, loss, prec = at.attack(inp, target)
-        pending.append((loss, prec, inp.size(0)))
-        if i % args.print_freq == 0:
-            flush()
-            log("Robust: [{0}/{1}]\t"
-                "Loss {loss.val:.4f} ({loss.avg:.4f})\t"
-                "Accuracy {top1.val:.3f} ({top1.avg:.3f})".format(i, len(val_loader), loss=losses, top1=top1))
-    flush()
-    log("robust_accuracy {top1.avg:.3f}".format(top1=top1))
-    return top1.avg, losses.avg
+    return cls_entry.evaluate(val_loader, lambda inp, target: at.attack(inp, target)[1:], "Robust", "robust_accuracy", args, log)
 
 
 def main(argv=None):
@@ -78,16 +55,10 @@ def main(argv=None):
     # (without an attack the printed namespace is the clean evaluation's own: the attack flags are not part of it)
     shown = args if args.attack_steps else argparse.Namespace(**{k: v for k, v in vars(args).items() if not k.startswith("attack_")})
     print(shown, flush=True)
-    if not torch.cuda.is_available():
-        raise RuntimeError("main_inference.py needs an MI355X: this build has no CPU path (oracle/ is test infrastructure)")
-    torch.cuda.set_device(int(args.gpu))
-    dev = torch.device("cuda", int(args.gpu))
-    if args.arch == "resnet50" and not args.synthetic:
-        raise SystemExit("--arch resnet50 is the ImageNet-shape synthetic configuration: pass --synthetic N")
+    dev, _, _, _, log = cls_entry.setup("main_inference.py", args.gpu, place=False)
+    cls_entry.check_arch(args)
     ctor, _ = resnet_s.ARCHS[args.arch]
-    model = ctor()
-    model.set_compute_dtype(torch.bfloat16 if args.dtype == "bf16" else torch.float32)
-    model.set_channels_last(args.layout == "nhwc").to(dev)
+    model = cls_entry.prepare_model(ctor(), args, dev)
     criterion = nn.CrossEntropyLoss()
 
     checkpoint = torch.load(args.pretrained, map_location=dev, weights_only=False)
@@ -97,16 +68,13 @@ def main(argv=None):
     model.load_state_dict(state)
 
     if args.synthetic:
-        side, classes = (224, 1000) if args.arch == "resnet50" else (32, 10)
-        loader = main_perturb.SyntheticLoader(args.synthetic, args.batch_size, dev, side=side, classes=classes)
+        side, classes = cls_entry.synthetic_shape(args)
+        loader = cls_data.SyntheticLoader(args.synthetic, args.batch_size, dev, side=side, classes=classes)
     else:
-        xt, yt = main_perturb._load_cifar10_test(args.data)
-        loader = main_perturb.DeviceLoader(xt, yt, args.batch_size, dev, False, drop_last=False)
+        xt, yt = cls_data._load_cifar10_test(args.data)
+        loader = cls_data.DeviceLoader(xt, yt, args.batch_size, dev, False, drop_last=False)
 
-    def log(*a):
-        print(*a, flush=True)
-
-    main_perturb.validate(loader, model, criterion, args, log)
+    cls_entry.validate(loader, model, criterion, args, log)
     if args.attack_steps:
         robust_validate(loader, model, criterion, args, log)
 

@@ -7,21 +7,16 @@ Per batch: SegDeviceLoader's one launch, the model's eval-mode forward up to the
 launch (seg_eval.validate); the confusion matrix is read back once, for the printed scores."""
 import argparse
 import os
-import random
 import sys
-
-import numpy as np
-import torch
 
 if __package__ in (None, ""):  # executed as a script (cmd/run_seg_val.sh): import the hyphenated package by path
     import importlib
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     _pkg = importlib.import_module("cv_a-fan_amd")
-    deeplab, seg_data, seg_eval = _pkg.deeplab, _pkg.seg_data, _pkg.seg_eval
+    seg_data, seg_eval, seg_entry = _pkg.seg_data, _pkg.seg_eval, importlib.import_module("cv_a-fan_amd.seg_entry")
 else:
-    from . import deeplab, seg_data, seg_eval
+    from . import seg_data, seg_entry, seg_eval
 
-MODEL_MAP = deeplab.MODELS
 DATASET, NUM_CLASSES = "voc", 21                                     # (main_aug_final.py:29-30)
 ADDITIONS = ("dtype", "layout", "synthetic", "max_side")
 
@@ -50,42 +45,19 @@ def get_argparser():
     return parser
 
 
-def synthetic_split(opts):
-    """The split --synthetic N scores on (main_aug_final.py draws its training split the same way)."""
-    hi = opts.max_side or 500
-    return seg_data.SyntheticSegSplit(opts.synthetic, seed=opts.random_seed, min_side=max(3 * hi // 4, 1), max_side=hi,
-                                      classes=NUM_CLASSES)
+synthetic_split = seg_entry.synthetic_split          # (main_aug_final.py draws its training split the same way)
 
 
 def main(argv=None):
     opts = get_argparser().parse_args(argv)
-    for arg, val in opts.__dict__.items():                              # (args.py:259-262)
-        print(arg + '.' * (80 - len(arg) - len(str(val))) + str(val))
-    print()
-    if opts.model not in MODEL_MAP:
-        raise NotImplementedError(f"--model {opts.model}: the mobilenet backbones are not built (no kernels for depthwise convolutions)")
+    seg_entry.print_args(opts)
+    seg_entry.check_model(opts)
     opts.save_val_results = False
-    local = int(opts.gpu_id.split(",")[0])
-    if not torch.cuda.is_available():
-        raise RuntimeError("main_seg_val.py needs an MI355X: this build has no CPU path (oracle/ is test infrastructure)")
-    torch.cuda.set_device(local)
-    device = torch.device("cuda", local)
-    print("Device: %s" % device)
+    device, _ = seg_entry.setup_device("main_seg_val.py", opts.gpu_id, place=False)
+    seg_entry.seed_all(opts.random_seed)
 
-    torch.manual_seed(opts.random_seed)
-    np.random.seed(opts.random_seed)
-    random.seed(opts.random_seed)
-
-    model = MODEL_MAP[opts.model](num_classes=NUM_CLASSES, output_stride=opts.output_stride)
-    model.set_compute_dtype(torch.bfloat16 if opts.dtype == "bf16" else torch.float32)
-    model.set_channels_last(opts.layout == "nhwc")
-    if opts.ckpt is not None and os.path.isfile(opts.ckpt):
-        checkpoint = torch.load(opts.ckpt, map_location=torch.device('cpu'))
-        model.load_state_dict(checkpoint["model_state"])
-        print("Model restored from %s" % opts.ckpt)
-        del checkpoint
-    else:
-        print("[!] Retrain")
+    model = seg_entry.build_model(opts, NUM_CLASSES)
+    seg_entry.restore(opts, model)
     model.to(device)
 
     if opts.synthetic:
@@ -96,11 +68,7 @@ def main(argv=None):
     loader = seg_data.SegDeviceLoader(images, labels, opts.val_batch_size, device, False, opts.crop_size, crop_val=opts.crop_val)
     print("Dataset: %s, Val set: %d" % (DATASET, len(images)))
 
-    metrics = seg_eval.StreamSegMetrics(NUM_CLASSES, device)
-    model.eval()
-    val_score, _ = seg_eval.validate(opts=opts, model=model, loader=loader, device=device, metrics=metrics)
-    print(metrics.to_str(val_score))
-    return val_score
+    return seg_entry.validation(opts, model, loader, device, seg_eval.StreamSegMetrics(NUM_CLASSES, device))
 
 
 if __name__ == '__main__':

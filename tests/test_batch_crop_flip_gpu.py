@@ -1,5 +1,5 @@
 """ops.batch_crop_flip (afan_batch_crop_flip_u8: gather + random crop + flip + /255 in one launch) against the torch chain it
-replaces, main_perturb._augment_torch, bit for bit, labels included."""
+replaces, cls_data._augment_torch, bit for bit, labels included."""
 import importlib
 
 import pytest
@@ -9,7 +9,7 @@ pytestmark = pytest.mark.gpu
 
 
 def _mp():
-    return importlib.import_module("cv_a-fan_amd.main_perturb")
+    return importlib.import_module("cv_a-fan_amd.cls_data")
 
 
 def _split(n, c, h, w, gpu, seed=0):

@@ -1,4 +1,4 @@
-"""main_perturb.DeviceLoader on the one-launch kernel: the same batches, bit for bit, as the torch chain (_augment_torch) fed with the
+"""cls_data.DeviceLoader on the one-launch kernel: the same batches, bit for bit, as the torch chain (_augment_torch) fed with the
 same seeds and the same permutation."""
 import importlib
 
@@ -10,7 +10,7 @@ pytestmark = pytest.mark.gpu
 
 
 def _mp():
-    return importlib.import_module("cv_a-fan_amd.main_perturb")
+    return importlib.import_module("cv_a-fan_amd.cls_data")
 
 
 def _fake(n):

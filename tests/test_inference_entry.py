@@ -16,7 +16,7 @@ def test_parser_matches_the_reference():
 
 
 def test_test_split_reader_keeps_file_order(tmp_path):
-    mp = __import__(load_pkg().__name__ + ".main_perturb", fromlist=["_load_cifar10_test"])
+    mp = __import__(load_pkg().__name__ + ".cls_data", fromlist=["_load_cifar10_test"])
     d = tmp_path / "cifar-10-batches-py"
     d.mkdir()
     data = np.arange(5 * 3072, dtype=np.int64).reshape(5, 3072) % 251

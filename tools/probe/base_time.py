@@ -2,7 +2,7 @@
 
   kind "step":   ms per iteration of train_step.BaseTrainer (bf16 channels-last, replayed hipGraph) beside AfanTrainer's K = 5 step at
                  the same shape — device events around `iters` iterations, `repeats` times after warm-up; median, min and max reported.
-  kind "loader": ms per batch of main_perturb.DeviceLoader iteration ALONE (a fake 45 000-image split), kernel path
+  kind "loader": ms per batch of cls_data.DeviceLoader iteration ALONE (a fake 45 000-image split), kernel path
                  (ops.batch_crop_flip) against the torch chain it replaced (_augment_torch, what the loader ran before) — host wall
                  clock with a final synchronise, and device time from events around the epoch; median, min and max over the repeats.
 
@@ -22,7 +22,7 @@ import torch.nn as nn
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 afan = importlib.import_module("cv_a-fan_amd")
-mp = importlib.import_module("cv_a-fan_amd.main_perturb")
+mp = importlib.import_module("cv_a-fan_amd.cls_data")
 
 STEP_CONFIGS = [("resnet20s", 128), ("resnet56s", 128), ("resnet18", 256)]
 

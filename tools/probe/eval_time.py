@@ -1,4 +1,4 @@
-"""Eval forward time: the eager eval pass (model forward + criterion + accuracy, as main_perturb.validate ran it) against
+"""Eval forward time: the eager eval pass (model forward + criterion + accuracy, as validate ran it before infer.Evaluator) against
 infer.Evaluator's graph replay, device events around N batches after warm-up.  One JSON line per configuration.
 Usage: python tools/probe/eval_time.py [--iters N] [--out FILE]"""
 import argparse
