@@ -27,10 +27,20 @@ int afan_frozen_bottleneck_fwd(const void* x, int64_t n, int64_t h, int64_t w, i
                                const void* w1, const void* w2, const void* w3, const void* wd, const float* k1, const float* k2,
                                const float* k3, const float* kd, void* scratch, void* a1, void* a2, void* out,
                                afan_stream_t stream) {
+    return afan_frozen_bottleneck_fwd_dil(x, n, h, w, cin, planes, stride, 1, w1, w2, w3, wd, k1, k2, k3, kd, scratch, a1, a2, out, stream);
+}
+
+// The same with the dilation of the 3x3 convolution (padding = dilation; dilation > 1: stride 1 — the atrous bottlenecks of
+// Segmentation/network/backbone/resnet.py:29-32 in eval mode).  Dilation 1 issues exactly the launches it always did.
+int afan_frozen_bottleneck_fwd_dil(const void* x, int64_t n, int64_t h, int64_t w, int64_t cin, int64_t planes, int stride, int dilation,
+                                   const void* w1, const void* w2, const void* w3, const void* wd, const float* k1, const float* k2,
+                                   const float* k3, const float* kd, void* scratch, void* a1, void* a2, void* out,
+                                   afan_stream_t stream) {
     if (!x || !w1 || !w2 || !w3 || !k1 || !k2 || !k3 || !scratch || !a1 || !a2 || !out) return AFAN_ENULL;
     if (wd && !kd) return AFAN_ENULL;
     if (n <= 0 || h <= 0 || w <= 0 || cin <= 0 || planes <= 0 || !(stride == 1 || stride == 2)) return AFAN_ESHAPE;
     if (!wd && (cin != 4 * planes || stride != 1)) return AFAN_ESHAPE;
+    if (dilation < 1 || (dilation > 1 && stride != 1)) return AFAN_ESHAPE;
     const int64_t ho = (h - 1) / stride + 1, wo = (w - 1) / stride + 1, co = 4 * planes;
     uint16_t* r1 = (uint16_t*)scratch;                       // [n, planes, h, w] (then [n, planes, ho, wo])
     uint16_t* r3 = r1 + n * planes * h * w;                  // [n, co, ho, wo]
@@ -39,15 +49,17 @@ int afan_frozen_bottleneck_fwd(const void* x, int64_t n, int64_t h, int64_t w, i
     // a convolution and its frozen BatchNorm (+ residual) (+ ReLU) as ONE launch where the tiled kernel takes the shape
     // (afan_conv_fwd_affine_nhwc_bf16: the same bits), else the two launches
     auto conv_bn = [&](const void* in, const void* wt, void* raw, void* dst, int64_t hi_, int64_t wi_, int64_t ci_, int64_t co_, int k, int st_,
-                       const float* kc, const void* res, int relu) -> int {
-        int rc = fuse_affine() ? afan_conv_fwd_affine_nhwc_bf16(in, wt, dst, n, hi_, wi_, ci_, co_, k, st_, kc, res, relu, stream) : AFAN_ESHAPE;
+                       const float* kc, const void* res, int relu, int dil = 1) -> int {
+        int rc = !fuse_affine() ? AFAN_ESHAPE
+                 : dil > 1 ? afan_conv_fwd_affine_dil_nhwc_bf16(in, wt, dst, n, hi_, wi_, ci_, co_, k, st_, dil, kc, res, relu, stream)
+                           : afan_conv_fwd_affine_nhwc_bf16(in, wt, dst, n, hi_, wi_, ci_, co_, k, st_, kc, res, relu, stream);
         if (rc != AFAN_ESHAPE) return rc;
-        if ((rc = afan_conv_fwd_nhwc_bf16(in, wt, raw, n, hi_, wi_, ci_, co_, k, st_, 1, nullptr, nullptr, nullptr, 1, stream))) return rc;
+        if ((rc = afan_conv_fwd_nhwc_bf16(in, wt, raw, n, hi_, wi_, ci_, co_, k, st_, dil, nullptr, nullptr, nullptr, 1, stream))) return rc;
         const int64_t ho_ = (hi_ - 1) / st_ + 1, wo_ = (wi_ - 1) / st_ + 1;
         return afan_affine_apply(raw, res, dst, AFAN_BF16, n, co_, ho_ * wo_, kc, relu, stream);
     };
     if ((e = conv_bn(x, w1, r1, a1, h, w, cin, planes, 1, 1, k1, nullptr, 1))) return e;
-    if ((e = conv_bn(a1, w2, r1, a2, h, w, planes, planes, 3, stride, k2, nullptr, 1))) return e;
+    if ((e = conv_bn(a1, w2, r1, a2, h, w, planes, planes, 3, stride, k2, nullptr, 1, dilation))) return e;
     const void* res = x;
     if (wd) {
         if ((e = conv_bn(x, wd, rd, rd, h, w, cin, co, 1, stride, kd, nullptr, 0))) return e;      // (raw == dst: the apply is elementwise)
@@ -89,6 +101,18 @@ int afan_frozen_bottleneck_bwd_chain(const void* g, void* pre_d3, void* pre_dres
                                      const void* wt1, const void* wt2, const void* wt3, const void* wtd, const float* al1, const float* al2,
                                      const float* al3, const float* ald, float* gw1, float* gw2, float* gw3, float* gwd, float* wgrad_ws,
                                      void* scratch, void* dx, const float* prev_al3, void* prev_d3, void* prev_dres, afan_stream_t stream) {
+    return afan_frozen_bottleneck_bwd_chain_dil(g, pre_d3, pre_dres, x, a1, a2, out, n, h, w, cin, planes, stride, 1, wt1, wt2, wt3, wtd, al1, al2,
+                                                al3, ald, gw1, gw2, gw3, gwd, wgrad_ws, scratch, dx, prev_al3, prev_d3, prev_dres, stream);
+}
+
+// The same with the dilation of the 3x3 convolution (see afan_frozen_bottleneck_fwd_dil).  Dilation 1 issues exactly the launches it
+// always did; the weight gradients, where asked for, take the dilation too (one by one: the multi launch's plan knows dilation 1).
+int afan_frozen_bottleneck_bwd_chain_dil(const void* g, void* pre_d3, void* pre_dres, const void* x, const void* a1, const void* a2,
+                                         const void* out, int64_t n, int64_t h, int64_t w, int64_t cin, int64_t planes, int stride,
+                                         int dilation, const void* wt1, const void* wt2, const void* wt3, const void* wtd,
+                                         const float* al1, const float* al2, const float* al3, const float* ald, float* gw1, float* gw2,
+                                         float* gw3, float* gwd, float* wgrad_ws, void* scratch, void* dx, const float* prev_al3,
+                                         void* prev_d3, void* prev_dres, afan_stream_t stream) {
     if (!x || !a1 || !a2 || !out || !wt1 || !wt2 || !wt3 || !al1 || !al2 || !al3 || !scratch) return AFAN_ENULL;
     if (!g && (!pre_d3 || !pre_dres)) return AFAN_ENULL;
     if (prev_al3 && (dx || !prev_d3 || !prev_dres)) return AFAN_ENULL;
@@ -96,6 +120,7 @@ int afan_frozen_bottleneck_bwd_chain(const void* g, void* pre_d3, void* pre_dres
     if ((gw1 || gw2 || gw3 || gwd) && !wgrad_ws) return AFAN_ENULL;
     if (n <= 0 || h <= 0 || w <= 0 || cin <= 0 || planes <= 0 || !(stride == 1 || stride == 2)) return AFAN_ESHAPE;
     if (!wtd && (cin != 4 * planes || stride != 1)) return AFAN_ESHAPE;
+    if (dilation < 1 || (dilation > 1 && stride != 1)) return AFAN_ESHAPE;
     const int64_t ho = (h - 1) / stride + 1, wo = (w - 1) / stride + 1, co = 4 * planes;
     uint16_t* d3 = (uint16_t*)scratch;                       // [n, co, ho, wo]
     uint16_t* dres = d3 + n * co * ho * wo;                  // [n, co, ho, wo]
@@ -110,15 +135,17 @@ int afan_frozen_bottleneck_bwd_chain(const void* g, void* pre_d3, void* pre_dres
     // an input gradient and the backward of the frozen BatchNorm + ReLU it runs into as ONE launch where the tiled kernel takes the
     // shape (afan_conv_dgrad_affine_nhwc_bf16: the same bits), else the two launches
     auto dgrad_bn = [&](const void* dyp, const void* wt, void* raw, void* dst, int64_t hi_, int64_t wi_, int64_t ci_, int64_t co_, int k, int st_,
-                        const float* al, const void* act) -> int {
-        int rc = fuse_affine() ? afan_conv_dgrad_affine_nhwc_bf16(dyp, wt, dst, n, hi_, wi_, ci_, co_, k, st_, al, act, stream) : AFAN_ESHAPE;
+                        const float* al, const void* act, int dil = 1) -> int {
+        int rc = !fuse_affine() ? AFAN_ESHAPE
+                 : dil > 1 ? afan_conv_dgrad_affine_dil_nhwc_bf16(dyp, wt, dst, n, hi_, wi_, ci_, co_, k, st_, dil, al, act, stream)
+                           : afan_conv_dgrad_affine_nhwc_bf16(dyp, wt, dst, n, hi_, wi_, ci_, co_, k, st_, al, act, stream);
         if (rc != AFAN_ESHAPE) return rc;
-        if ((rc = afan_conv_dgrad_nhwc_bf16(dyp, wt, raw, n, hi_, wi_, ci_, co_, k, st_, 1, nullptr, nullptr, nullptr, 0, nullptr, nullptr,
+        if ((rc = afan_conv_dgrad_nhwc_bf16(dyp, wt, raw, n, hi_, wi_, ci_, co_, k, st_, dil, nullptr, nullptr, nullptr, 0, nullptr, nullptr,
                                             nullptr, 1, stream))) return rc;
         return afan_affine_relu_bwd(raw, act, al, dst, nullptr, AFAN_BF16, AFAN_NHWC, n, ci_, hi_ * wi_, 1, stream);
     };
     if ((e = dgrad_bn(d3, wt3, t2, d2, ho, wo, planes, co, 1, 1, al2, a2))) return e;
-    if ((e = dgrad_bn(d2, wt2, t1, d1, h, w, planes, planes, 3, stride, al1, a1))) return e;
+    if ((e = dgrad_bn(d2, wt2, t1, d1, h, w, planes, planes, 3, stride, al1, a1, dilation))) return e;
     const void* addend = dres;
     const bool want_dx = dx || prev_al3;
     if (wtd) {
@@ -144,22 +171,22 @@ int afan_frozen_bottleneck_bwd_chain(const void* g, void* pre_d3, void* pre_dres
     const void* xs[4]; const void* dys[4]; float* gws[4];
     int64_t ns[4], hs[4], ws_[4], cis[4], cos[4];
     int ks[4], sts[4], dils[4], codes[4], m = 0;
-    auto add = [&](float* gw, const void* xin, const void* dy, int64_t hh, int64_t ww, int64_t ci, int64_t co_, int k, int st) {
+    auto add = [&](float* gw, const void* xin, const void* dy, int64_t hh, int64_t ww, int64_t ci, int64_t co_, int k, int st, int dil = 1) {
         if (!gw) return;
         xs[m] = xin; dys[m] = dy; gws[m] = gw; ns[m] = n; hs[m] = hh; ws_[m] = ww; cis[m] = ci; cos[m] = co_; ks[m] = k; sts[m] = st;
-        dils[m] = 1;
+        dils[m] = dil;
         codes[m] = afan_conv_wgrad_plan(n, hh, ww, ci, co_, k, st);
         ++m;
     };
     add(gw3, a2, d3, ho, wo, planes, co, 1, 1);
-    add(gw2, a1, d2, h, w, planes, planes, 3, stride);
+    add(gw2, a1, d2, h, w, planes, planes, 3, stride, dilation);
     add(gw1, x, d1, h, w, cin, planes, 1, 1);
     if (wtd) add(gwd, x, dres, h, w, cin, co, 1, stride);
-    bool same = m >= 2;
+    bool same = m >= 2 && dilation == 1;
     for (int i = 0; i < m; ++i) same = same && codes[i] != 0 && codes[i] == codes[0];
     if (same) return afan_conv_wgrad_multi_nhwc_bf16(m, xs, dys, gws, ns, hs, ws_, cis, cos, ks, sts, dils, wgrad_ws, 1, stream);
     for (int i = 0; i < m; ++i)
-        if ((e = afan_conv_wgrad_nhwc_bf16(xs[i], dys[i], gws[i], ns[i], hs[i], ws_[i], cis[i], cos[i], ks[i], sts[i], 1, wgrad_ws, 1,
+        if ((e = afan_conv_wgrad_nhwc_bf16(xs[i], dys[i], gws[i], ns[i], hs[i], ws_[i], cis[i], cos[i], ks[i], sts[i], dils[i], wgrad_ws, 1,
                                            stream))) return e;
     return AFAN_OK;
 }

@@ -1734,7 +1734,7 @@ static int dgrad_impl(const void* dy, const void* dy_sc, const void* wt, void* d
             }
         if (bnf) return small_eligible(p) ? AFAN_ESHAPE : dispatch_bnf(p, st, true);
         if (small_eligible(p)) {
-            if ((p.aff && !any_family) || !small_groups_ok(p)) return AFAN_ESHAPE;
+            if ((p.aff && (!any_family || dilation > 1)) || !small_groups_ok(p)) return AFAN_ESHAPE;   // (atrous affine form: the tiled kernel only)
             if (p.aff && !aligned(aff_alpha, 16)) return AFAN_EALIGN;              // (small_dgrad_aff reads its alpha row as 16-byte vectors)
             return small_launch(p, st);
         }
@@ -1873,8 +1873,9 @@ int afan_conv_fwd_nhwc_bf16(const void* x, const void* w, void* y, int64_t n, in
 // image stem (afan_conv_stem.hip; no residual there), each in an instantiation of its own (the training kernels are not touched).
 // The 7x7 stem (afan_conv_stem7.hip) has no such form.
 static int fwd_affine_impl(const void* x, const void* w, void* y, int64_t n, int64_t hi, int64_t wi, int64_t ci, int64_t co, int k,
-                           int stride, const float* coefs, const void* residual, int relu, afan_stream_t stream, bool any_family) {
-    if (any_family && ci == 3) {                                // the image stem: affine + ReLU at its staged store
+                           int stride, const float* coefs, const void* residual, int relu, afan_stream_t stream, bool any_family,
+                           int dilation = 1) {
+    if (any_family && ci == 3 && dilation == 1) {                                // the image stem: affine + ReLU at its staged store
         AFAN_TRACE_PROBLEM(0, afan::trace::FWD, n, hi, wi, ci, co, k, stride, 1);
         if (!afan_stem::eligible(n, hi, wi, ci, co, k, stride) || residual) return AFAN_ESHAPE;
         if (!x || !w || !y || !coefs) return AFAN_ENULL;
@@ -1884,14 +1885,14 @@ static int fwd_affine_impl(const void* x, const void* w, void* y, int64_t n, int
         AFAN_PROF_FLOPS("conv_stem_fwd_kernel", 2.0 * (M * co + M * 3 + 27.0 * co), 2.0 * M * co * 27, st);
         return afan_stem::fwd_aff_launch(x, w, y, n, hi, wi, co, coefs, relu, st);
     }
-    int e = check_dims(n, hi, wi, ci, co, k, stride, 1);
+    int e = check_dims(n, hi, wi, ci, co, k, stride, dilation);
     if (e) return e;
-    AFAN_TRACE_PROBLEM(0, afan::trace::FWD, n, hi, wi, ci, co, k, stride, 1);
+    AFAN_TRACE_PROBLEM(0, afan::trace::FWD, n, hi, wi, ci, co, k, stride, dilation);
     if (!x || !w || !y || !coefs) return AFAN_ENULL;
     if (!aligned(x, 16) || !aligned(w, 16) || !aligned(y, 16) || (residual && !aligned(residual, 16))) return AFAN_EALIGN;
-    const int pad = k / 2;
+    const int pad = k / 2;     // (a dilated 3x3 at stride 1 keeps the spatial size, like the plain one)
     ConvP p{};
-    p.max_pad = 1;
+    p.max_pad = dilation;      // (atrous: never the LDS-resident halo form, halo_ok())
     p.x = (const uint16_t*)x; p.w = (const uint16_t*)w; p.y = (uint16_t*)y;
     p.N = (int)n; p.Hi = (int)hi; p.Wi = (int)wi; p.Ci = (int)ci;
     p.Ho = (int)((hi + 2 * pad - k) / stride + 1); p.Wo = (int)((wi + 2 * pad - k) / stride + 1); p.Co = (int)co;
@@ -1904,9 +1905,10 @@ static int fwd_affine_impl(const void* x, const void* w, void* y, int64_t n, int
     for (int r = 0; r < k; ++r)
         for (int s = 0; s < k; ++s) {
             const int t = r * k + s;
-            c0.dh[t] = r - pad; c0.dw[t] = s - pad; c0.wofs[t] = (int)(t * ci);
+            c0.dh[t] = (r - pad) * dilation; c0.dw[t] = (s - pad) * dilation; c0.wofs[t] = (int)(t * ci);
         }
-    const bool small = small_eligible(p), c64 = !small && afan_c64::eligible(n, hi, wi, ci, co, k, stride);
+    if (dilation > 1 && small_eligible(p)) return AFAN_ESHAPE;     // (atrous: the tiled kernel only, as afan_conv_fwd_nhwc_bf16's callers ask)
+    const bool small = small_eligible(p), c64 = !small && dilation == 1 && afan_c64::eligible(n, hi, wi, ci, co, k, stride);
     if (!any_family && (small || c64)) return AFAN_ESHAPE;
     if (!small && (ci % 8 != 0 || co % 8 != 0 || ci < 40 || co < 40)) return AFAN_ESHAPE;
     if ((small || c64) && !aligned(coefs, 16)) return AFAN_EALIGN;   // (those two read the coefficient rows as 16-byte vectors)
@@ -1933,6 +1935,19 @@ int afan_conv_fwd_affine_any_nhwc_bf16(const void* x, const void* w, void* y, in
                                        int64_t co, int k, int stride, const float* coefs, const void* residual, int relu,
                                        afan_stream_t stream) {
     return fwd_affine_impl(x, w, y, n, hi, wi, ci, co, k, stride, coefs, residual, relu, stream, true);
+}
+
+// The same with a dilation (Segmentation's eval-mode DeepLab, deeplab.py: the atrous 3x3 convolutions of layer3 / layer4 and of ASPP with
+// their BatchNorms): y = [relu](bf16(conv(x, w; padding = dilation * (k / 2), dilation)) * alpha + beta [+ residual]), bit for bit
+// afan_conv_fwd_nhwc_bf16(dilation) followed by afan_affine_apply.  dilation == 1: afan_conv_fwd_affine_any_nhwc_bf16.  dilation > 1:
+// 3x3 at stride 1 on the tiled kernel, whose epilogue carries the affine in every instantiation — the launch is the one
+// afan_conv_fwd_nhwc_bf16 would choose (max_pad = dilation: never the LDS-resident halo form), so no kernel is added and the training
+// kernels are not touched.  AFAN_ESHAPE where no kernel takes the problem (the caller issues the two launches).
+int afan_conv_fwd_affine_dil_nhwc_bf16(const void* x, const void* w, void* y, int64_t n, int64_t hi, int64_t wi, int64_t ci, int64_t co,
+                                       int k, int stride, int dilation, const float* coefs, const void* residual, int relu,
+                                       afan_stream_t stream) {
+    if (dilation == 1) return fwd_affine_impl(x, w, y, n, hi, wi, ci, co, k, stride, coefs, residual, relu, stream, true);
+    return fwd_affine_impl(x, w, y, n, hi, wi, ci, co, k, stride, coefs, residual, relu, stream, true, dilation);
 }
 
 // nb <= 4 forward problems on the SAME input with the SAME output shape in one launch (grid.z = problem): ASPP's atrous 3x3
@@ -2097,6 +2112,18 @@ int afan_conv_dgrad_affine_any_nhwc_bf16(const void* dy, const void* wt, void* d
     if (!alpha) return AFAN_ENULL;
     return dgrad_impl(dy, nullptr, wt, dx, n, hi, wi, ci, co, k, stride, 1, nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr, 1, stream,
                       alpha, act, nullptr, nullptr, true);
+}
+
+// The same with a dilation (the eval-mode DeepLab's backward): dx = bf16((act > 0 ? bf16(dgrad(dy, wt; dilation)) : 0) * alpha[c]), bit for
+// bit afan_conv_dgrad_nhwc_bf16(dilation) followed by afan_affine_relu_bwd.  dilation == 1: afan_conv_dgrad_affine_any_nhwc_bf16.
+// dilation > 1: 3x3 at stride 1 on the tiled kernel (the launch afan_conv_dgrad_nhwc_bf16 would choose), whose backward epilogue
+// always masks: act == NULL answers AFAN_ESHAPE there, like every problem no kernel takes (the caller issues the two launches).
+int afan_conv_dgrad_affine_dil_nhwc_bf16(const void* dy, const void* wt, void* dx, int64_t n, int64_t hi, int64_t wi, int64_t ci,
+                                         int64_t co, int k, int stride, int dilation, const float* alpha, const void* act,
+                                         afan_stream_t stream) {
+    if (!alpha) return AFAN_ENULL;
+    return dgrad_impl(dy, nullptr, wt, dx, n, hi, wi, ci, co, k, stride, dilation, nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr, 1,
+                      stream, alpha, act, nullptr, nullptr, true);
 }
 
 // The input gradient that arrives at the OUTPUT of a frozen-BatchNorm residual block (Detection's bottlenecks: out = relu(bn3(conv3) +

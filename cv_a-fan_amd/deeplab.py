@@ -20,8 +20,8 @@ import torch
 import torch.nn as nn
 
 from . import ops
-from .resnet_s import (BatchNorm2d, Conv2d, NormalizeByChannelMeanStd, _BlockFn, _ConvFn, _Flags, _WgradStream, _accumulates_in_place,
-                       _block_fast_path_ok, _block_params, _dense, _like_layout, _to_compute)
+from .resnet_s import (BatchNorm2d, Conv2d, NormalizeByChannelMeanStd, _BlockFn, _ConvFn, _Flags, _FrozenBlockFn, _WgradStream,
+                       _accumulates_in_place, _block_fast_path_ok, _block_params, _dense, _like_layout, _own_conv_ok, _to_compute)
 
 __all__ = ["deeplabv3plus_resnet50", "deeplabv3plus_resnet101", "deeplabv3_resnet50", "deeplabv3_resnet101", "DeepLabV3",
            "seg_criterion", "set_bn_momentum", "PolyLR", "MODELS"]
@@ -404,16 +404,147 @@ def _enter(x, dtype, channels_last):
     return _to_compute(x, dtype)
 
 
+# ---------------------------------------------------------------------------- eval mode on the frozen-BatchNorm forms
+# An eval-mode DeepLab (validation, and the steps_pgd + 1 forward / backward passes per batch of seg_eval.pgd_validate) is bound by
+# launches and Python dispatch: every convolution and every BatchNorm is its own autograd node.  With the switch on, on the bf16
+# channels-last path, a Bottleneck is ONE node over ops.frozen_bottleneck_fwd_plan / _bwd_plan (the block's dilation included) and a
+# conv -> BatchNorm (-> ReLU) pair ONE node whose forward is one launch (ops.conv_fwd_affine) — the same kernels, the same bits.  Read
+# at call time (tests flip it); training mode, fp32, NCHW and BatchNorms with their auxiliary (--dual_bn) set swapped in never come here.
+FROZEN_EVAL = os.environ.get("AFAN_SEG_FROZEN_EVAL", "1") != "0"
+# The BatchNorms are not frozen for good (training continues between validations): coefficient blocks and block plans are kept per
+# module and rebuilt when a tensor behind them changed (_version, address), the weights moved (_Flags.weight_epoch) or any BatchNorm
+# was in training mode in between (_Flags.bn_epoch).  0: rebuilt at every call (A/B, tools/probe/seg_pgd_val_time.py).
+COEF_CACHE = os.environ.get("AFAN_SEG_COEF_CACHE", "1") != "0"
+
+
+def _bn_frozen(bn):
+    return (not bn.training) and bn.track_running_stats and getattr(bn, "_branch", "main") == "main" and bn.weight is not None \
+        and bn.weight.dtype == torch.float32
+
+
+def _bn_key(bn):
+    ts = (bn.running_mean, bn.running_var, bn.weight, bn.bias)
+    return tuple(t._version for t in ts) + tuple(t.data_ptr() for t in ts) + (_Flags.bn_epoch,)
+
+
+def _bn_coefs(bn):
+    """The afan_affine_coefs block [4, C] of an eval-mode BatchNorm, by BatchNorm2d.fused's expressions (the same values)."""
+    key = _bn_key(bn) if COEF_CACHE else None
+    hit = bn.__dict__.get("_frozen_coefs")
+    if key is not None and hit is not None and hit[0] == key:
+        return hit[1]
+    with torch.no_grad():
+        coefs = ops.affine_coefs(bn.running_mean, torch.rsqrt(bn.running_var + bn.eps), bn.weight.detach(), bn.bias.detach())
+    bn.__dict__["_frozen_coefs"] = (key, coefs)
+    return coefs
+
+
+def _frozen_conv_ok(conv, x):
+    k = conv.kernel_size[0]
+    return (conv.bias is None and conv.compute_dtype == torch.bfloat16 and conv.kernel_size[0] == conv.kernel_size[1]
+            and tuple(conv.padding) == (conv.dilation[0] * (k // 2),) * 2 and conv.in_channels != 3 and conv.groups == 1
+            and _own_conv_ok(x, conv.lp_weight(), conv.stride, conv.padding, conv.dilation))
+
+
+def _frozen_input_ok(x):
+    return (FROZEN_EVAL and x.is_cuda and x.dtype == torch.bfloat16 and x.dim() == 4 and x.shape[2] * x.shape[3] > 1
+            and x.is_contiguous(memory_format=torch.channels_last))
+
+
+class _FrozenCbrFn(torch.autograd.Function):
+    """conv -> eval-mode BatchNorm (-> ReLU) as ONE node: the forward is one launch where a kernel has the epilogue form
+    (ops.conv_fwd_affine, atrous 3x3 included), else the two launches; the backward is the affine's (afan_affine_relu_bwd) and the
+    convolution's input gradient.  Input gradient only: eval-mode parameters get no gradient here."""
+
+    @staticmethod
+    def forward(ctx, x, conv, coefs, relu):
+        w = conv.lp_weight().detach()
+        st, dil = conv.stride[0], conv.dilation[0]
+        y = ops.conv_fwd_affine(x, w, st, coefs, None, relu, any_kernel=True, dilation=dil)
+        if y is None:      # (AFAN_ESHAPE: no epilogue form for this layer)
+            y = ops.affine_apply(ops.conv_fwd(x, w, st, dilation=dil), coefs, None, relu)
+        if ctx.needs_input_grad[0]:
+            ctx.conv, ctx.alpha, ctx.relu, ctx.in_hw = conv, coefs[2], bool(relu), tuple(x.shape[2:])
+            ctx.save_for_backward(y)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        (y,) = ctx.saved_tensors
+        gy = _like_layout(gy, y)
+        if gy.dtype != y.dtype:
+            gy = gy.to(y.dtype)
+        conv = ctx.conv
+        d, _ = ops.affine_relu_backward(gy, y, ctx.alpha, ctx.relu, want_dx=True)
+        return ops.conv_dgrad(d, conv.lp_weight_t(), ctx.in_hw, conv.stride[0], dilation=conv.dilation[0]), None, None, None
+
+
 def _cbr(conv, bn, x, relu=True):
     """conv -> BatchNorm (moments from the convolution's epilogue where the kernels take the shape) -> ReLU."""
+    if FROZEN_EVAL and _bn_frozen(bn) and conv.compute_dtype == torch.bfloat16:
+        xc = _to_compute(x, conv.compute_dtype)
+        if _frozen_input_ok(xc) and _frozen_conv_ok(conv, xc):
+            return _FrozenCbrFn.apply(xc, conv, _bn_coefs(bn), relu)
     out, st = conv.forward_with_stats(x, bn)
     return bn.fused(out, None, relu, st)
+
+
+def _frozen_block_plan(blk, x):
+    """The eval-mode Bottleneck's ops.FrozenBlockPlan for this input (dilation of its 3x3 included, no weight gradients), or None
+    where the one-node form does not apply — then the layers run as they always did."""
+    convs = [blk.conv1, blk.conv2, blk.conv3] + ([blk.downsample[0]] if blk.downsample is not None else [None])
+    bns = [blk.bn1, blk.bn2, blk.bn3] + ([blk.downsample[1]] if blk.downsample is not None else [])
+    if not all(_bn_frozen(b) for b in bns):
+        return None
+    key = None
+    if COEF_CACHE:
+        key = (tuple(x.shape), x.device.index, _Flags.weight_epoch) + tuple(v for b in bns for v in _bn_key(b)) + \
+            tuple(v for c in convs if c is not None for v in (c.weight._version, c.lp_weight().data_ptr()))
+        hit = blk.__dict__.get("_frozen_plan")
+        if hit is not None and hit[0] == key:
+            return hit[1]
+    plan = None
+    c2 = blk.conv2
+    ok = all(c is None or (c.bias is None and c.compute_dtype == torch.bfloat16) for c in convs) and \
+        tuple(c2.padding) == tuple(c2.dilation) and (c2.dilation[0] == 1 or c2.stride[0] == 1)
+    if ok:
+        n, _, h, w = x.shape
+        ho, wo = (h - 1) // c2.stride[0] + 1, (w - 1) // c2.stride[0] + 1
+        probes = [x, _Probe((n, c2.in_channels, h, w), x), _Probe((n, blk.conv3.in_channels, ho, wo), x), x]
+        ok = all(c is None or _own_conv_ok(t, c.lp_weight(), c.stride, c.padding, c.dilation) for c, t in zip(convs, probes))
+    if ok:
+        ks = tuple(_bn_coefs(b) for b in bns) + ((None,) if convs[3] is None else ())
+        plan = ops.frozen_bottleneck_plan(x, blk.conv1.out_channels, c2.stride[0],
+                                          tuple(None if c is None else c.lp_weight().detach() for c in convs), ks,
+                                          tuple(None if c is None else c.lp_weight_t() for c in convs),
+                                          tuple(None if k is None else k[2] for k in ks), (None, None, None, None), dilation=c2.dilation[0])
+    blk.__dict__["_frozen_plan"] = (key, plan)
+    return plan
+
+
+class _Probe:
+    """What _own_conv_ok looks at of a map that does not exist yet (a block's inner activations)."""
+    __slots__ = ("shape", "device", "dtype", "is_cuda")
+
+    def __init__(self, shape, like):
+        self.shape, self.device, self.dtype, self.is_cuda = torch.Size(shape), like.device, like.dtype, like.is_cuda
+
+    def dim(self):
+        return len(self.shape)
+
+    def is_contiguous(self, memory_format=None):
+        return True
 
 
 class Bottleneck(nn.Module):
     """backbone/resnet.py:76-119: 1x1 -> 3x3 (stride, dilation) -> 1x1 x4, `downsample` = 1x1 conv + BN when the shape
     changes.  One autograd node on the bf16 channels-last path (resnet_s._BlockFn)."""
     expansion = 4
+    # True: the block's input is read outside the block too (ResNet sets it on layer2's first block: the decoder reads the low-level
+    # feature).  The one-node eval form adds the block's own two input gradients inside a launch, a + b, before autograd adds the
+    # other reader's c; the layer-by-layer nodes hand them over one by one, (c + b) + a.  bf16 sums of three do not reorder, so such
+    # a block keeps its layer nodes (each conv -> BatchNorm pair still one node) and the image gradient keeps its bits.
+    shared_input = False
 
     def __init__(self, inplanes, planes, stride=1, downsample=None, dilation=1):
         super().__init__()
@@ -435,10 +566,20 @@ class Bottleneck(nn.Module):
     def _chain(self):
         return [(self.conv1, self.bn1), (self.conv2, self.bn2), (self.conv3, self.bn3)]
 
+    def __getstate__(self):
+        # (the eval-mode launch plan holds ctypes pointer objects: a deepcopy / torch.save of the module starts without it)
+        d = dict(self.__dict__)
+        d.pop("_frozen_plan", None)
+        return d
+
     def forward(self, x):
         x = _to_compute(x, self.conv1.compute_dtype)
         if _Flags.block_fusion and _block_fast_path_ok(self, x):
             return _BlockFn.apply(x, self, _Flags.param_grads, *_block_params(self))
+        if not self.bn1.training and not self.shared_input and _frozen_input_ok(x):
+            plan = _frozen_block_plan(self, x)
+            if plan is not None:
+                return _FrozenBlockFn.apply(x, self, plan)
         out = _cbr(self.conv1, self.bn1, x)
         out = _cbr(self.conv2, self.bn2, out)
         out, st = self.conv3.forward_with_stats(out, self.bn3)
@@ -461,6 +602,7 @@ class ResNet(nn.Module):
         self.layer2 = self._make_layer(128, layers[1], stride=2, dilate=replace_stride_with_dilation[0])
         self.layer3 = self._make_layer(256, layers[2], stride=2, dilate=replace_stride_with_dilation[1])
         self.layer4 = self._make_layer(512, layers[3], stride=2, dilate=replace_stride_with_dilation[2])
+        self.layer2[0].shared_input = True                     # (`low_level`, forward(): layer1's output goes to the decoder as well)
         for m in self.modules():                               # backbone/resnet.py:160-165
             if isinstance(m, nn.Conv2d):
                 nn.init.kaiming_normal_(m.weight, mode="fan_out", nonlinearity="relu")

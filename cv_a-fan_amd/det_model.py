@@ -26,8 +26,8 @@ from . import ops
 from .deeplab import MaxPool2d, StemConv, _MaxPoolFn, _enter
 from .det_ops import (box_assign, box_decode_clip, fg_bg_draw, fg_bg_sample, labels_limit_, nms, per_image_losses, proposal_rows,
                       roi_align, sample_lists)
-from .resnet_s import (Conv2d, NormalizeByChannelMeanStd, _accumulates_in_place, _ConvFn, _dense, _Flags, _like_layout, _linear, dgrad_only,
-                       _own_conv_ok, _to_compute, _WgradStream)
+from .resnet_s import (Conv2d, NormalizeByChannelMeanStd, _accumulates_in_place, _ConvFn, _dense, _Flags, _FrozenBlockFn, _like_layout, _linear,
+                       dgrad_only, _own_conv_ok, _to_compute, _WgradStream)
 
 __all__ = ["Model", "ResNet101", "RegionProposalNetwork", "FrozenBatchNorm2d", "fasterrcnn_resnet101"]
 
@@ -178,31 +178,6 @@ class _GlobalMaxFn(torch.autograd.Function):
 
 
 # ------------------------------------------------------------------------------------------------------------- backbone
-class _FrozenBlockFn(torch.autograd.Function):
-    """A frozen-BatchNorm bottleneck (backbone/resnet101_ori.py:78-127) as ONE autograd node on the bf16 channels-last path:
-    the same launches as the layer-by-layer form — three (four) tuned convolutions, three (four) fused affine(+residual)
-    (+ReLU) launches forward; affine backward, input gradient and weight gradient per layer backward, the identity shortcut's
-    gradient added in the first convolution's dgrad epilogue — but one `Function.apply`, one backward node and ONE native call
-    each way (afan_frozen_bottleneck_fwd / _bwd issue the launches from C++) instead of seven of each: the Detection
-    iteration is bound by Python dispatch (2 600 applies per iteration before this node)."""
-
-    @staticmethod
-    def forward(ctx, x, blk, plan, *params):
-        out, a1, a2 = ops.frozen_bottleneck_fwd_plan(x, plan)
-        ctx.plan = plan
-        ctx.save_for_backward(x, a1, a2, out)
-        return out
-
-    @staticmethod
-    def backward(ctx, g):
-        x, a1, a2, out = ctx.saved_tensors
-        g = _like_layout(g, out)
-        if g.dtype != out.dtype:
-            g = g.to(out.dtype)
-        dx = ops.frozen_bottleneck_bwd_plan(g, x, a1, a2, out, ctx.plan, ctx.needs_input_grad[0])
-        return (dx, None, None) + (None,) * (len(ctx.needs_input_grad) - 3)
-
-
 def _block_plan(blk, x):
     """The block's cached ops.FrozenBlockPlan for this input shape and autograd mode, or False where the one-node form does not
     apply (then the layer-by-layer modules run).  Valid for one weight epoch (an optimizer step or a shadow refresh bumps

@@ -8,7 +8,8 @@ hipGraph), the batch is built on the device by seg_data.SegDeviceLoader in one l
 
 Validation (seg_eval.validate: one eager low-resolution forward and one scoring launch per batch) runs at every --val_interval on the
 `val` image set and keeps best_*; a --synthetic run has no validation split and skips it.  Scoring a checkpoint on its own
-(the reference's --test_only) is main_seg_val.py.  Not built here: --test_only, --eval_pgd, --save_val_results (they raise),
+(the reference's --test_only) is main_seg_val.py, under an image-space PGD attack (main_advtrain.py's --eval_pgd) main_seg_rob.py.
+Not built here: --test_only, --eval_pgd, --save_val_results (they raise),
 --dataset cityscapes (its ExtColorJitter has no kernel), visdom and tensorboard (accepted, ignored)."""
 import functools
 import os
@@ -28,7 +29,7 @@ else:
 get_argparser, get_full_argparser, print_args, ADDITIONS = (seg_entry.get_argparser, seg_entry.get_full_argparser, seg_entry.print_args,
                                                             seg_entry.ADDITIONS)
 UNBUILT_VALIDATION = {"test_only": "validation of a checkpoint on its own is main_seg_val.py (cmd/run_seg_val.sh), not a flag of this program",
-                      "eval_pgd": "validation under an image-space PGD attack (args.pgd_validate) is not built; main_seg_val.py scores clean images",
+                      "eval_pgd": "validation under an image-space PGD attack (args.pgd_validate) is main_seg_rob.py (cmd/run_seg_rob.sh), not a flag of this program",
                       "save_val_results": "writing validation images is not built; validation itself runs at --val_interval and in main_seg_val.py"}
 NO_VAL_SPLIT = "a --synthetic run has no validation split (main_seg_val.py --synthetic N scores a checkpoint on a synthetic one)"
 

@@ -659,12 +659,17 @@ class FrozenBlockPlan:
     Detection iteration runs 388 block forwards and ~250 block backwards, and at ~100 us of Python per call (eligibility
     checks, 20 pointer wrappers, four workspace-size queries) the host, not the GPU, set its pace."""
     __slots__ = ("n", "cin", "h", "w", "ho", "wo", "planes", "co", "stride", "fwd_scratch", "bwd_scratch", "wgrad_ws", "w_ptrs", "k_ptrs",
-                 "wt_ptrs", "al_ptrs", "gw_ptrs", "n_fwd", "n_wgrad", "has_ds", "keep", "sig")
+                 "wt_ptrs", "al_ptrs", "gw_ptrs", "n_fwd", "n_wgrad", "has_ds", "keep", "sig", "dilation")
 
 
-def frozen_bottleneck_plan(x, planes, stride, ws, ks, wts, als, gws):
+def frozen_bottleneck_plan(x, planes, stride, ws, ks, wts, als, gws, dilation=1):
+    """dilation: of the block's 3x3 convolution (padding = dilation; > 1 needs stride 1: DeepLab's atrous bottlenecks in eval mode,
+    afan_frozen_bottleneck_*_dil).  dilation = 1 issues the calls it always did."""
     lib = _lib.load()
     p = FrozenBlockPlan()
+    p.dilation = int(dilation)
+    if p.dilation < 1 or (p.dilation > 1 and int(stride) != 1):
+        raise ValueError("frozen_bottleneck_plan: an atrous 3x3 (dilation > 1) has stride 1")
     p.n, p.cin, p.h, p.w = (int(v) for v in x.shape)
     p.ho, p.wo = (p.h - 1) // stride + 1, (p.w - 1) // stride + 1
     p.planes, p.co, p.stride = int(planes), 4 * int(planes), int(stride)
@@ -679,7 +684,7 @@ def frozen_bottleneck_plan(x, planes, stride, ws, ks, wts, als, gws):
     p.n_fwd, p.n_wgrad = 3 + int(p.has_ds), sum(gw is not None for gw in gws)
     p.keep = (ws, ks, wts, als, gws)              # the tensors behind the pointers
     # every address a launch of this plan bakes in: two plans with equal signatures issue identical launches (hipGraph reuse)
-    p.sig = (p.n, p.cin, p.h, p.w, p.planes, p.stride) + tuple(None if t is None else t.data_ptr() for grp in p.keep for t in grp)
+    p.sig = (p.n, p.cin, p.h, p.w, p.planes, p.stride) + ((p.dilation,) if p.dilation != 1 else ()) + tuple(None if t is None else t.data_ptr() for grp in p.keep for t in grp)
     return p
 
 
@@ -692,6 +697,12 @@ def frozen_bottleneck_fwd_plan(x, p):
     scratch = _workspace(x, p.fwd_scratch, "fbk_fwd")
     CALLS["conv_fwd"] += p.n_fwd
     w, k = p.w_ptrs, p.k_ptrs
+    if p.dilation != 1:
+        check(lib.afan_frozen_bottleneck_fwd_dil(C.c_void_p(x.data_ptr()), p.n, p.h, p.w, p.cin, p.planes, p.stride, p.dilation, w[0], w[1], w[2], w[3],
+                                                 k[0], k[1], k[2], k[3], C.c_void_p(scratch.data_ptr()), C.c_void_p(a1.data_ptr()),
+                                                 C.c_void_p(a2.data_ptr()), C.c_void_p(out.data_ptr()), C.c_void_p(_raw_stream(dev.index))),
+              "afan_frozen_bottleneck_fwd_dil")
+        return out, a1, a2
     check(lib.afan_frozen_bottleneck_fwd(C.c_void_p(x.data_ptr()), p.n, p.h, p.w, p.cin, p.planes, p.stride, w[0], w[1], w[2], w[3], k[0], k[1], k[2], k[3],
                                          C.c_void_p(scratch.data_ptr()), C.c_void_p(a1.data_ptr()), C.c_void_p(a2.data_ptr()),
                                          C.c_void_p(out.data_ptr()), C.c_void_p(_raw_stream(dev.index))), "afan_frozen_bottleneck_fwd")
@@ -714,6 +725,14 @@ def frozen_bottleneck_bwd_plan(g, x, a1, a2, out, p, want_dx, pre=None, prev=Non
         nd3, ndres = torch.empty_like(x), torch.empty_like(x)
     elif want_dx:
         dx = torch.empty_like(x)
+    if p.dilation != 1:
+        check(lib.afan_frozen_bottleneck_bwd_chain_dil(_ptr(g), _ptr(pre[0]) if pre else None, _ptr(pre[1]) if pre else None, C.c_void_p(x.data_ptr()),
+                                                       C.c_void_p(a1.data_ptr()), C.c_void_p(a2.data_ptr()), C.c_void_p(out.data_ptr()), p.n, p.h, p.w,
+                                                       p.cin, p.planes, p.stride, p.dilation, wt[0], wt[1], wt[2], wt[3], al[0], al[1], al[2], al[3],
+                                                       gw[0], gw[1], gw[2], gw[3], _ptr(wws), C.c_void_p(scratch.data_ptr()), _ptr(dx),
+                                                       prev.al_ptrs[2] if prev is not None else None, _ptr(nd3), _ptr(ndres),
+                                                       C.c_void_p(_raw_stream(x.device.index))), "afan_frozen_bottleneck_bwd_chain_dil")
+        return (nd3, ndres) if prev is not None else dx
     check(lib.afan_frozen_bottleneck_bwd_chain(_ptr(g), _ptr(pre[0]) if pre else None, _ptr(pre[1]) if pre else None, C.c_void_p(x.data_ptr()),
                                                C.c_void_p(a1.data_ptr()), C.c_void_p(a2.data_ptr()), C.c_void_p(out.data_ptr()), p.n, p.h, p.w, p.cin,
                                                p.planes, p.stride, wt[0], wt[1], wt[2], wt[3], al[0], al[1], al[2], al[3], gw[0], gw[1], gw[2], gw[3],
@@ -1193,20 +1212,31 @@ def _conv_dgrad_bn_pair(dy, pair, in_hw, bn_x, bn_stats, relu, bn_y, want_dres, 
     return dx, dres
 
 
-def conv_fwd_affine(x, w, stride, coefs, residual=None, relu=False, any_kernel=False):
+def conv_fwd_affine(x, w, stride, coefs, residual=None, relu=False, any_kernel=False, dilation=1):
     """[relu](bf16(conv2d(x, w)) * alpha + beta [+ residual]) in ONE launch: a convolution with the frozen BatchNorm behind it in its
     epilogue.  any_kernel=False (afan_conv_fwd_affine_nhwc_bf16): the tiled kernel's shapes; None where the shape belongs to another
     kernel (the caller issues conv_fwd + affine_apply: the same bits).  any_kernel=True (afan_conv_fwd_affine_any_nhwc_bf16, the
     eval forward of infer.py): every forward kernel family of conv_fwd (tiled, small-channel, 64 -> 64 weights-in-registers,
     3-channel image stem — the stem without a residual), coefs a 16-byte aligned afan_affine_coefs block; None where no kernel takes
-    the shape."""
+    the shape.  dilation > 1 (afan_conv_fwd_affine_dil_nhwc_bf16, the eval-mode DeepLab's atrous 3x3 convolutions at stride 1, padding
+    = dilation): the tiled kernel; the same bits as conv_fwd(dilation=) + affine_apply."""
     lib = _lib.load()
     _cl4(x, "x"), _cl4(w, "w")
     n, ci, hi, wi = x.shape
     co, _, k, _ = w.shape
-    pad = k // 2
-    ho, wo = (hi + 2 * pad - k) // stride + 1, (wi + 2 * pad - k) // stride + 1
+    dilation = int(dilation)
+    pad = dilation * (k // 2)
+    ho, wo = (hi + 2 * pad - dilation * (k - 1) - 1) // stride + 1, (wi + 2 * pad - dilation * (k - 1) - 1) // stride + 1
     y = torch.empty((n, co, ho, wo), dtype=torch.bfloat16, device=x.device, memory_format=torch.channels_last)
+    if dilation != 1:
+        name = "afan_conv_fwd_affine_dil_nhwc_bf16"
+        rc = lib.afan_conv_fwd_affine_dil_nhwc_bf16(_ptr(x), _ptr(w), _ptr(y), n, hi, wi, ci, co, k, int(stride), dilation, _ptr(coefs),
+                                                    _ptr(residual), int(bool(relu)), _stream(x))
+        if rc == -3:
+            return None
+        check(rc, name)
+        CALLS["conv_fwd"] += 1
+        return y
     name = "afan_conv_fwd_affine_any_nhwc_bf16" if any_kernel else "afan_conv_fwd_affine_nhwc_bf16"
     rc = getattr(lib, name)(_ptr(x), _ptr(w), _ptr(y), n, hi, wi, ci, co, k, int(stride), _ptr(coefs), _ptr(residual),
                             int(bool(relu)), _stream(x))
@@ -1736,18 +1766,20 @@ def maxpool2d_backward(dy, idx, in_shape, k, stride, pad=0, x=None, channels_las
     return dx
 
 
-def conv_dgrad_affine(dy, wt, in_hw, stride, alpha, act, any_kernel=False):
+def conv_dgrad_affine(dy, wt, in_hw, stride, alpha, act, any_kernel=False, dilation=1):
     """dx = bf16((act > 0 ? bf16(dgrad(dy, wt)) : 0) * alpha[c]) in ONE launch: an input gradient with the backward of the frozen
     BatchNorm + ReLU it runs into.  any_kernel=False (afan_conv_dgrad_affine_nhwc_bf16): the tiled kernel's shapes; None where another
     kernel owns the shape (the caller issues conv_dgrad + affine_relu_backward: the same bits).  any_kernel=True
     (afan_conv_dgrad_affine_any_nhwc_bf16, the eval backward of infer.py): every input-gradient family of conv_dgrad (tiled,
     small-channel, 64 -> 64 weights-in-registers), alpha 16-byte aligned; act=None (no ReLU mask: bf16(bf16(dgrad) * alpha[c])) on
-    the latter two; None where no kernel takes the problem."""
+    the latter two; None where no kernel takes the problem.  dilation > 1 (afan_conv_dgrad_affine_dil_nhwc_bf16: atrous 3x3 at
+    stride 1): the tiled kernel, which always masks — None without `act`."""
     lib = _lib.load()
     _cl4(dy, "dy"), _cl4(wt, "wt")
+    dilation = int(dilation)
     if act is not None:
         _cl4(act, "act")
-    elif not any_kernel:
+    elif not any_kernel and dilation == 1:
         raise ValueError("conv_dgrad_affine: the ReLU mask `act` is optional only with any_kernel=True")
     _need(alpha, "alpha", torch.float32)
     n, co, ho, wo = dy.shape
@@ -1756,6 +1788,15 @@ def conv_dgrad_affine(dy, wt, in_hw, stride, alpha, act, any_kernel=False):
     if alpha.numel() != ci or (act is not None and tuple(act.shape) != (n, ci, hi, wi)):
         raise ValueError("conv_dgrad_affine: alpha [Ci] and act of dx's shape")
     dx = torch.empty((n, ci, hi, wi), dtype=torch.bfloat16, device=dy.device, memory_format=torch.channels_last)
+    if dilation != 1:
+        name = "afan_conv_dgrad_affine_dil_nhwc_bf16"
+        rc = lib.afan_conv_dgrad_affine_dil_nhwc_bf16(_ptr(dy), _ptr(wt), _ptr(dx), n, hi, wi, ci, co, k, int(stride), dilation, _ptr(alpha),
+                                                      _ptr(act), _stream(dy))
+        if rc == -3:
+            return None
+        check(rc, name)
+        CALLS["conv_dgrad"] += 1
+        return dx
     name = "afan_conv_dgrad_affine_any_nhwc_bf16" if any_kernel else "afan_conv_dgrad_affine_nhwc_bf16"
     rc = getattr(lib, name)(_ptr(dy), _ptr(wt), _ptr(dx), n, hi, wi, ci, co, k, int(stride), _ptr(alpha), _ptr(act), _stream(dy))
     if rc == -3:

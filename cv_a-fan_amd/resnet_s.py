@@ -31,6 +31,8 @@ class _Flags:
     wgrad_stash = False  # True: block weight gradients are not launched but their operands kept on the conv module (stash_wgrad)
     bn_groups = 1        # 2: the batch is [adv half | clean half]; BatchNorm statistics / running updates per half, in order
     bn_branch = "main"   # "adv" inside bn_branch(model, "adv"): BatchNorms with an auxiliary set use it (dual-BN option)
+    bn_epoch = 0         # bumped whenever a BatchNorm2d changes between training and eval mode (BatchNorm2d.train): the running
+                         # statistics move only in training mode, and there through the kernels' own pointers (no tensor version changes)
 
 
 @contextlib.contextmanager
@@ -828,6 +830,32 @@ class _BlockFn(torch.autograd.Function):
         return (dx, None, None) + (None,) * (len(ctx.needs_input_grad) - 3)
 
 
+class _FrozenBlockFn(torch.autograd.Function):
+    """A frozen-BatchNorm bottleneck (Detection: backbone/resnet101_ori.py:78-127; Segmentation: DeepLab's eval-mode bottlenecks,
+    atrous ones included, deeplab.Bottleneck) as ONE autograd node on the bf16 channels-last path:
+    the same launches as the layer-by-layer form — three (four) tuned convolutions, three (four) fused affine(+residual)
+    (+ReLU) launches forward; affine backward, input gradient and weight gradient per layer backward, the identity shortcut's
+    gradient added in the first convolution's dgrad epilogue — but one `Function.apply`, one backward node and ONE native call
+    each way (afan_frozen_bottleneck_fwd / _bwd issue the launches from C++) instead of seven of each: the Detection
+    iteration is bound by Python dispatch (2 600 applies per iteration before this node)."""
+
+    @staticmethod
+    def forward(ctx, x, blk, plan, *params):
+        out, a1, a2 = ops.frozen_bottleneck_fwd_plan(x, plan)
+        ctx.plan = plan
+        ctx.save_for_backward(x, a1, a2, out)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        x, a1, a2, out = ctx.saved_tensors
+        g = _like_layout(g, out)
+        if g.dtype != out.dtype:
+            g = g.to(out.dtype)
+        dx = ops.frozen_bottleneck_bwd_plan(g, x, a1, a2, out, ctx.plan, ctx.needs_input_grad[0])
+        return (dx, None, None) + (None,) * (len(ctx.needs_input_grad) - 3)
+
+
 def _block_fast_path_ok(blk, x):
     """bf16 channels-last training step with every convolution of the block on the library's MFMA kernels and every
     parameter's gradient buffer owned by the arena (or parameter gradients switched off, as inside PGD)."""
@@ -984,6 +1012,10 @@ class BatchNorm2d(nn.BatchNorm2d):
         for k in ("running_mean", "running_var", "num_batches_tracked"):
             self._buffers[k], a._buffers[k] = a._buffers[k], self._buffers[k]
         self._branch = branch
+
+    def train(self, mode=True):
+        _Flags.bn_epoch += 1         # (caches of this layer's frozen affine, deeplab._bn_coefs, end here)
+        return super().train(mode)
 
     def fused(self, x, residual=None, relu=False, conv_stats=None):
         if self.training:

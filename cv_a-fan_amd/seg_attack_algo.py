@@ -114,11 +114,12 @@ def decoder_PGD(input_dict, image_batch, criterion, y=None, model=None, steps=3,
 
 
 def adv_input(x=None, criterion=None, y=None, model=None, steps=3, eps=None, gamma=None, randinit=False, clip=False):
-    """Image-space PGD (:86-105), clamped to [0, 1] at the end."""
+    """Image-space PGD (:86-105), clamped to [0, 1] at the end.  With seg_criterion's fused callable the model hands back its
+    low-resolution logits and the criterion resizes inside its own kernel, as in PGD / decoder_PGD."""
     x, x_adv = _start(x, eps, randinit)
     for _ in range(steps):
-        _ascend(x_adv, lambda t: model({"x": t, "adv": None, "out_idx": 0, "flag": "clean", "low_level_feat": None}),
-                criterion, y, gamma, x, eps, clip)
+        _ascend(x_adv, lambda t: model({"x": t, "adv": None, "out_idx": 0, "flag": "clean", "low_level_feat": None,
+                                        "low_res": _low_res(criterion)}), criterion, y, gamma, x, eps, clip)
     lo, hi = torch.zeros_like(x_adv), torch.ones_like(x_adv)
     ops.tensor_clamp_(x_adv, lo, hi)
     return x_adv.requires_grad_(True)

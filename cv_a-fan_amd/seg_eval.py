@@ -1,5 +1,5 @@
-"""Segmentation validation: StreamSegMetrics (Segmentation/metrics/stream_metrics.py:25-83) and validate (Segmentation/args.py:168-220)
-with the reference's interfaces.
+"""Segmentation validation: StreamSegMetrics (Segmentation/metrics/stream_metrics.py:25-83), validate (Segmentation/args.py:168-220)
+and pgd_validate (args.py:223-255: the same pass on images attacked in image space) with the reference's interfaces.
 
 What differs is where the counting happens.  The reference resizes the logits to the image size, takes max(dim=1), copies the
 predictions and the labels to the host and counts there (np.bincount), once per batch.  Here `update_logits` hands the classifier's
@@ -10,7 +10,7 @@ reference's, in numpy float64 on the same float64 matrix."""
 import numpy as np
 import torch
 
-from . import deeplab, ops
+from . import deeplab, ops, seg_attack_algo
 
 
 def _fast_hist(n_classes, label_true, label_pred):
@@ -115,4 +115,26 @@ def validate(opts, model, loader, device, metrics, ret_samples_ids=None):
             out = model({"x": images, "adv": None, "out_idx": 0, "flag": "clean", "low_res": True})
             metrics.update_logits(out, labels)
         score = metrics.get_results()
+    return score, ret_samples
+
+
+def pgd_validate(opts, model, loader, device, metrics, criterion, ret_samples_ids=None):
+    """args.py:223-255: one pass over `loader` with every batch attacked by image-space sign-PGD first (seg_attack_algo.adv_input with
+    opts.steps_pgd / eps_pgd / gamma_pgd / randinit_pgd / clip_pgd, eps and gamma in 1/255 units), (score, ret_samples).  The caller
+    sets model.eval().  Per batch: steps_pgd forward + input-gradient passes (no parameter gradient is computed: adv_input runs them
+    under dgrad_only), then one forward under no_grad on the adversarial images that stops at the classifier's low-resolution
+    logits and one scoring launch, as validate().  Nothing is read back before get_results() — except that --randinit_pgd draws
+    its start on the host, as the reference does.  steps_pgd = 0 scores what validate() scores.  ret_samples is []."""
+    metrics.reset()
+    ret_samples = []
+    criterion = deeplab.seg_criterion(criterion)
+    for images, labels in loader:
+        images, labels = images.to(device), labels.to(device)
+        adv_images = seg_attack_algo.adv_input(x=images, criterion=criterion, y=labels, model=model, steps=opts.steps_pgd,
+                                               eps=(opts.eps_pgd / 255), gamma=(opts.gamma_pgd / 255), randinit=opts.randinit_pgd,
+                                               clip=opts.clip_pgd)
+        with torch.no_grad():
+            out = model({"x": adv_images.detach(), "adv": None, "out_idx": 0, "flag": "clean", "low_res": True})
+            metrics.update_logits(out, labels)
+    score = metrics.get_results()
     return score, ret_samples

@@ -271,6 +271,13 @@ int afan_conv_fwd_affine_nhwc_bf16(const void* x, const void* w, void* y, int64_
 int afan_conv_fwd_affine_any_nhwc_bf16(const void* x, const void* w, void* y, int64_t n, int64_t hi, int64_t wi, int64_t ci,
                                        int64_t co, int k, int stride, const float* coefs, const void* residual, int relu,
                                        afan_stream_t stream);
+/* afan_conv_fwd_affine_dil_nhwc_bf16 — the same with a dilation (Segmentation's eval-mode DeepLab: the atrous 3x3 convolutions of
+ * backbone/resnet.py:29-32 and _deeplab.py:146-153 with their BatchNorms): padding = dilation * (k / 2).  dilation == 1:
+ * afan_conv_fwd_affine_any_nhwc_bf16.  dilation > 1: 3x3 at stride 1 on the tiled kernel, bit for bit
+ * afan_conv_fwd_nhwc_bf16(dilation) followed by afan_affine_apply.  AFAN_ESHAPE where no kernel takes the problem. */
+int afan_conv_fwd_affine_dil_nhwc_bf16(const void* x, const void* w, void* y, int64_t n, int64_t hi, int64_t wi, int64_t ci, int64_t co,
+                                       int k, int stride, int dilation, const float* coefs, const void* residual, int relu,
+                                       afan_stream_t stream);
 /* nb (1..4) forward convolutions on the SAME input x with the SAME output shape in ONE launch: w[b] / y[b] / ksize[b] (1 or 3)
  * / dilation[b] per problem (host arrays; device pointers inside), BatchNorm moments of y[b] around stats_shift[b] into the
  * f64 accumulator block stats_acc[b] (both arrays NULL: no moments).  (1) The atrous branches of ASPP,
@@ -309,6 +316,13 @@ int afan_conv_dgrad_affine_nhwc_bf16(const void* dy, const void* wt, void* dx, i
  * input-gradient kernel takes the shape. */
 int afan_conv_dgrad_affine_any_nhwc_bf16(const void* dy, const void* wt, void* dx, int64_t n, int64_t hi, int64_t wi, int64_t ci,
                                          int64_t co, int k, int stride, const float* alpha, const void* act, afan_stream_t stream);
+/* afan_conv_dgrad_affine_dil_nhwc_bf16 — the same with a dilation (the eval-mode DeepLab's backward).  dilation == 1:
+ * afan_conv_dgrad_affine_any_nhwc_bf16.  dilation > 1: 3x3 at stride 1 on the tiled kernel, bit for bit
+ * afan_conv_dgrad_nhwc_bf16(dilation) followed by afan_affine_relu_bwd(relu = 1); AFAN_ESHAPE without act (that kernel's backward
+ * epilogue always masks) and where no kernel takes the problem. */
+int afan_conv_dgrad_affine_dil_nhwc_bf16(const void* dy, const void* wt, void* dx, int64_t n, int64_t hi, int64_t wi, int64_t ci,
+                                         int64_t co, int k, int stride, int dilation, const float* alpha, const void* act,
+                                         afan_stream_t stream);
 /* The gradient arriving at the OUTPUT of a frozen-BatchNorm residual block with that block's first backward step applied on the way
  * out: g = bf16(bf16(dgrad(dy)) + addend) (addend optional), m = act > 0 ? g : 0, dres = m, d3 = bf16(m * alpha[c]) — bit for bit
  * afan_conv_dgrad_nhwc_bf16(addend) followed by afan_affine_relu_bwd(relu = 1) with both outputs (Detection/backbone/
@@ -585,6 +599,19 @@ int afan_frozen_bottleneck_bwd_chain(const void* g, void* pre_d3, void* pre_dres
                                      const void* wt1, const void* wt2, const void* wt3, const void* wtd, const float* al1, const float* al2,
                                      const float* al3, const float* ald, float* gw1, float* gw2, float* gw3, float* gwd, float* wgrad_ws,
                                      void* scratch, void* dx, const float* prev_al3, void* prev_d3, void* prev_dres, afan_stream_t stream);
+/* The two sequencers with the dilation of the 3x3 convolution (padding = dilation; stride 1 whenever dilation > 1: the atrous
+ * bottlenecks of Segmentation/network/backbone/resnet.py:29-32 in eval mode).  The 3x3 goes through
+ * afan_conv_fwd_affine_dil_nhwc_bf16 / afan_conv_dgrad_affine_dil_nhwc_bf16; dilation 1 = the functions above. */
+int afan_frozen_bottleneck_fwd_dil(const void* x, int64_t n, int64_t h, int64_t w, int64_t cin, int64_t planes, int stride, int dilation,
+                                   const void* w1, const void* w2, const void* w3, const void* wd, const float* k1, const float* k2,
+                                   const float* k3, const float* kd, void* scratch, void* a1, void* a2, void* out,
+                                   afan_stream_t stream);
+int afan_frozen_bottleneck_bwd_chain_dil(const void* g, void* pre_d3, void* pre_dres, const void* x, const void* a1, const void* a2,
+                                         const void* out, int64_t n, int64_t h, int64_t w, int64_t cin, int64_t planes, int stride,
+                                         int dilation, const void* wt1, const void* wt2, const void* wt3, const void* wtd,
+                                         const float* al1, const float* al2, const float* al3, const float* ald, float* gw1, float* gw2,
+                                         float* gw3, float* gwd, float* wgrad_ws, void* scratch, void* dx, const float* prev_al3,
+                                         void* prev_d3, void* prev_dres, afan_stream_t stream);
 /* nn.AdaptiveAvgPool2d(1) (_deeplab.py:133): y[n,c] = mean over hw (fp32 accumulate); dx = dy / hw broadcast.
  * pooled_f32 != 0: the pooled side (y / dy) is fp32 whatever `dtype` the map has. */
 int afan_avgpool_fwd(const void* x, void* y, int dtype, int layout, int64_t n, int64_t c, int64_t hw, int pooled_f32,
