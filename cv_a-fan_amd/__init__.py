@@ -2,7 +2,7 @@
 
 The directory name carries a hyphen (it is fixed by the build contract), so import it with
     import importlib; afan = importlib.import_module("cv_a-fan_amd")
-Sub-modules: attack_algo (PGD & friends, reference signatures), resnet_s (slice-protocol models),
+Sub-modules: attack_algo (PGD & friends, reference signatures), pgd (the sign-PGD core every attack path is built from), resnet_s (slice-protocol models),
 arena (flat parameter arena + fused SGD), train_step (the joint step, data parallel), ops (tensor
 wrappers over the C-ABI in include/afan_hip.h), cls_data (DeviceLoader: one-launch CIFAR batches), cls_entry (what the Classification entry points share: flags, set-up, the train / evaluation / epoch loops, the
 checkpoint files; main_perturb for cmd/run_perturb.sh, main_base for cmd/run_base.sh, main_learnable, main_inference), infer (the fused, graph-replayed eval forward; main_inference evaluates a checkpoint), deeplab (the
@@ -14,7 +14,7 @@ matrix, validate; main_seg_val scores a checkpoint, cmd/run_seg_val.sh), det_ops
 """
 from . import _lib, ops  # noqa: F401
 from ._lib import AfanLibraryError, LIB_PATH  # noqa: F401
-from . import resnet_s, attack_algo, arena, grid_guard, train_step, learnable, seg_attack_algo, deeplab, seg_trainer, seg_data, seg_eval, det_ops, det_attack_algo, det_model, det_trainer, host, infer  # noqa: F401
+from . import resnet_s, pgd, attack_algo, arena, grid_guard, train_step, learnable, seg_attack_algo, deeplab, seg_trainer, seg_data, seg_eval, det_ops, det_attack_algo, det_model, det_trainer, host, infer  # noqa: F401
 from .attack_algo import PGD, get_sample_points, linfball_proj, mix_feature, tensor_clamp  # noqa: F401
 
 __version__ = "0.1.0"

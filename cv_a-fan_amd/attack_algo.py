@@ -5,14 +5,13 @@ Same names, argument meaning and return contract as
   Segmentation/attack_algo.py:108-130  get_sample_points, mix_feature   (== Detection/attack_algo.py:236-265)
 but every arithmetic step is a hand-written HIP kernel from libafan_hip.so (sign-step + projection +
 per-sample norms fused in one pass; channel-moment re-normalisation in one pass).  `model` may be any
-nn.Module on the GPU that follows the slice protocol `model(t, end_point=, start_point=)`; for the
-models of `resnet_s.py` the tail additionally runs its fused BN kernels with parameter gradients
-switched off (the reference asks autograd for the feature gradient only, attack_algo.py:52).
+nn.Module on the GPU that follows the slice protocol `model(t, end_point=, start_point=)`.  The loop
+itself (input gradient, sign step) is pgd.py's; PGD keeps its one-launch start and the bf16 shadow.
 """
 import torch
 
-from . import ops
-from .resnet_s import _dense, _like_layout, dgrad_only, fused_criterion
+from . import ops, pgd
+from .resnet_s import _dense, _like_layout, fused_criterion
 
 __all__ = ["PGD", "tensor_clamp", "linfball_proj", "mix_feature", "get_sample_points", "last_norms"]
 
@@ -63,26 +62,20 @@ def PGD(x, loss_fn, y=None, model=None, steps=3, gamma=None, start_idx=1, layer_
         shadow = torch.empty_like(x, dtype=torch.bfloat16)
     if randinit:
         # the reference draws the noise on the CPU default generator (attack_algo.py:44); same stream here
-        u = _like_layout(torch.rand(x_adv.shape).to(x.device, non_blocking=True), x_adv)
-        ops.axpy_noise_(x_adv, u, eps, shadow)
+        ops.axpy_noise_(x_adv, torch.rand(x_adv.shape).to(x.device, non_blocking=True), eps, shadow)
     l2 = linf = None
     loss_fn = fused_criterion(loss_fn, model)
     for t in range(steps):
         if t == 0 and grad0 is not None:
-            grad = grad0.detach()
+            grad = grad0
         else:
             # the tail consumes the bf16 shadow written by the previous step's kernel (no separate cast)
             xin = (shadow if lp else x_adv).detach().requires_grad_(True)
-            with dgrad_only():
-                out = model(xin, end_point=layer_number, start_point=start_idx)
-                loss = loss_fn(out, y)
-                root = ops.one(loss.device) if (loss.dim() == 0 and loss.dtype == torch.float32) else None
-                grad = torch.autograd.grad(loss, xin, grad_outputs=root, only_inputs=True)[0]
-        grad = _like_layout(grad, x_adv)
+            grad = pgd.input_gradient(lambda t: loss_fn(model(t, end_point=layer_number, start_point=start_idx), y), xin)
         if with_norms and t == steps - 1:
-            l2, linf = ops.pgd_step_norms_(x_adv, grad, gamma, x, eps, clip, shadow)
+            l2, linf = pgd.step(x_adv, grad, gamma, x, eps, clip, shadow, norms=True)
         else:
-            ops.pgd_step_(x_adv, grad, gamma, x, eps, clip, shadow)
+            pgd.step(x_adv, grad, gamma, x, eps, clip, shadow)
     if with_norms:
         if l2 is None:
             l2, linf = ops.perturb_norms(x_adv, x)

@@ -11,17 +11,15 @@ behaviour of the reference's `Detection/attack_algo.py`, and the loop body of `D
 
 `model` is anything that follows the reference's protocol (`Detection/model.py:40-185`):
 `model.train().forward({'x', 'adv', 'out_idx', 'flag'}, bboxes, labels)` -> four per-image loss tensors, a feature map
-(flag 'head') or the ROI dict ('roi_head').  The sign step / projection / noise / clamp / mix / sample-point arithmetic runs in
-libafan_hip.so; NMS and ROIAlign for the model's own layers are in det_ops.py.  The Faster-RCNN model itself is out of
-scope; the Faster-RCNN model is det_model.py."""
+(flag 'head') or the ROI dict ('roi_head').  The attacks are pgd.py's loop around that protocol; the mix / sample-point arithmetic
+runs in libafan_hip.so; NMS and ROIAlign for the model's own layers are in det_ops.py; the Faster-RCNN model is det_model.py."""
 import os
 
 import torch
 
-from . import ops
+from . import ops, pgd
 from .attack_algo import get_sample_points, linfball_proj, mix_feature, sample_points_mixed, tensor_clamp  # noqa: F401
 from .det_ops import PGD, sum_of_means  # noqa: F401  (Detection/attack_algo.py:48-74)
-from .resnet_s import dgrad_only
 
 
 def compute_loss(loss1, loss2, loss3, loss4):
@@ -53,30 +51,6 @@ class NoiseAhead:
         return u if (u is not None and tuple(u.shape) == tuple(shape)) else None
 
 
-def _start(x, eps, randinit, ahead=None):
-    if x.device.type != "cuda":
-        raise ops.AfanLibraryError("x must live on the MI355X (no CPU path in this build)")
-    x = x.detach().float()
-    x = x if (x.is_contiguous() or (x.dim() == 4 and x.is_contiguous(memory_format=torch.channels_last))) else x.contiguous()
-    x_adv = x.clone()
-    if randinit:   # noise from the CPU default generator, then host -> device, like the reference (:52, :159)
-        u = ahead.take(x_adv.shape) if ahead is not None else None
-        u = (u if u is not None else torch.rand(x_adv.shape)).to(x.device, non_blocking=True)
-        if u.stride() != x_adv.stride():
-            u = u.contiguous(memory_format=torch.channels_last)
-        ops.axpy_noise_(x_adv, u, eps)
-    return x, x_adv
-
-
-def _ascend(x_adv, loss_of, gamma, x, eps, clip):
-    xin = x_adv.detach().requires_grad_(True)
-    with dgrad_only():          # only_inputs=True (:66,:103,:170): no parameter gradient is computed, none is touched
-        grad = torch.autograd.grad(loss_of(xin), xin, only_inputs=True)[0]
-    if grad.stride() != x_adv.stride():
-        grad = grad.contiguous(memory_format=torch.channels_last) if (x_adv.dim() == 4 and not x_adv.is_contiguous()) else grad.contiguous()
-    ops.pgd_step_(x_adv, grad, gamma, x, eps if eps is not None else 0.0, clip)     # one launch: sign step (+ projection)
-
-
 def _pgd1_from_clean(model, col, idx, image_batch, y, eps, gamma):
     """`PGD(fm[idx - 1], ..., steps=1, idx=idx)` without a random start (:84-86) when the clean pass's own activations are at hand:
     its one forward runs the backbone's remaining stages on the CLEAN feature map — the numbers the clean ROI-head pass already
@@ -89,19 +63,12 @@ def _pgd1_from_clean(model, col, idx, image_batch, y, eps, gamma):
     outs = [col.get(("out", i)) for i in (1, 2, 3)]
     if not all(det_model.stage_input_gradient(stages[i - 1], outs[i - 1]) for i in range(idx + 1, 4)):
         return None                  # (decided before anything is drawn from the host generator)
-    x = col[idx].detach().float()
-    x = x if (x.is_contiguous() or (x.dim() == 4 and x.is_contiguous(memory_format=torch.channels_last))) else x.contiguous()
-    x_adv = x.clone()
-    xin = col[3].detach().requires_grad_(True)
-    with dgrad_only():
-        l1, l2, l3, l4 = model.train().forward({"x": image_batch, "adv": xin, "out_idx": 3, "flag": "tail"}, y["bb"], y["lb"])
-        g = torch.autograd.grad(sum_of_means(l1, l2, l3, l4), xin, only_inputs=True)[0]
+    x, x_adv = pgd.start(col[idx], eps, False)
+    g = pgd.input_gradient(lambda t: sum_of_means(*model.train().forward({"x": image_batch, "adv": t, "out_idx": 3, "flag": "tail"}, y["bb"], y["lb"])),
+                           col[3].detach().requires_grad_(True))
     for i in range(3, idx, -1):
         g = det_model.stage_input_gradient(stages[i - 1], outs[i - 1], g)
-    grad = g.float()
-    if grad.stride() != x_adv.stride():
-        grad = grad.contiguous(memory_format=torch.channels_last) if (x_adv.dim() == 4 and not x_adv.is_contiguous()) else grad.contiguous()
-    ops.pgd_step_(x_adv, grad, gamma, x, eps, False)
+    pgd.step(x_adv, g, gamma, x, eps, False)
     return x_adv.requires_grad_(True)
 
 
@@ -120,26 +87,21 @@ def _pgd_three_from_clean(model, col, image_batch, y, specs, share=None):
     outs = [col.get(("out", i)) for i in (1, 2, 3)]
     if not all(det_model.stage_input_gradient(stages[i - 1], outs[i - 1]) for i in (2, 3)):
         return None                  # (decided before anything is drawn from the host generator)
-    xins = [col[3].detach().requires_grad_(True) for _ in specs]
-    with dgrad_only():
+    def loss_of(xins):
         res = model.train().forward_heads_many([{"x": image_batch, "adv": xi, "out_idx": 3, "flag": "tail"} for xi in xins], y["bb"], y["lb"],
                                                share=share)
         losses = [sum_of_means(*r) for r in res]
         total = losses[0]
         for l in losses[1:]:
             total = total + l
-        grads = torch.autograd.grad(total, xins, only_inputs=True)
+        return total
+    grads = pgd.input_gradient(loss_of, [col[3].detach().requires_grad_(True) for _ in specs])
     advs = []
     for (idx, eps, gamma), g in zip(specs, grads):
         for i in range(3, idx, -1):
             g = det_model.stage_input_gradient(stages[i - 1], outs[i - 1], g)
-        x = col[idx].detach().float()
-        x = x if (x.is_contiguous() or (x.dim() == 4 and x.is_contiguous(memory_format=torch.channels_last))) else x.contiguous()
-        x_adv = x.clone()
-        grad = g.float()
-        if grad.stride() != x_adv.stride():
-            grad = grad.contiguous(memory_format=torch.channels_last) if (x_adv.dim() == 4 and not x_adv.is_contiguous()) else grad.contiguous()
-        ops.pgd_step_(x_adv, grad, gamma, x, eps, False)
+        x, x_adv = pgd.start(col[idx], eps, False)
+        pgd.step(x_adv, g, gamma, x, eps, False)
         advs.append(x_adv.requires_grad_(True))
     return advs
 
@@ -152,20 +114,21 @@ def rpn_roi_PGD(layer="roi", rpn_roi_output_dict=None, y=None, model=None, steps
     feature (:129-146: the update is commented out) — the dict comes back with an unperturbed requires_grad copy."""
     d = rpn_roi_output_dict
     if layer == "roi":
-        _, x_adv = _start(d["roi_output_dict"]["roi_feature_map"], eps, randinit)
+        _, x_adv = pgd.start(d["roi_output_dict"]["roi_feature_map"], eps, randinit)
         d["roi_output_dict"]["roi_feature_map"] = x_adv
+
+        def loss_of(t):
+            d["roi_output_dict"]["roi_feature_map"] = t
+            ao, at, pc, pt = model.train().forward({"adv": d, "out_idx": "roi_tail", "flag": "clean"}, y["bb"], y["lb"])
+            return sum_of_means(pc, pt) if only_roi_loss else sum_of_means(ao, at, pc, pt)
         for _ in range(steps):
-            def loss_of(t):
-                d["roi_output_dict"]["roi_feature_map"] = t
-                ao, at, pc, pt = model.train().forward({"adv": d, "out_idx": "roi_tail", "flag": "clean"}, y["bb"], y["lb"])
-                return sum_of_means(pc, pt) if only_roi_loss else sum_of_means(ao, at, pc, pt)
-            _ascend(x_adv, loss_of, gamma, None, 0.0, False)
+            pgd.ascend(x_adv, loss_of, gamma, None, None, False)
             if clip:
                 raise NameError("name 'rpn_feature1' is not defined")
         d["roi_output_dict"]["roi_feature_map"] = x_adv.requires_grad_(True)
         return d
     if layer == "rpn":
-        _, x_adv = _start(d["rpn_feature_map_dict"]["rpn_feature"], eps, randinit)
+        _, x_adv = pgd.start(d["rpn_feature_map_dict"]["rpn_feature"], eps, randinit)
         x_adv.requires_grad_(True)
         d["rpn_feature_map_dict"]["rpn_feature"] = x_adv
         for _ in range(steps):
@@ -176,12 +139,12 @@ def rpn_roi_PGD(layer="roi", rpn_roi_output_dict=None, y=None, model=None, steps
 
 def adv_input(x=None, y=None, model=None, steps=3, eps=None, gamma=None, randinit=False, clip=False, noise_ahead=None):
     """:153-178: image-space PGD under the sum of the four losses, clamped to [0, 1] at the end."""
-    x, x_adv = _start(x, eps, randinit, noise_ahead)
+    # (the random start's draw may have been made ahead of time: NoiseAhead)
+    x, x_adv = pgd.start(x, eps, randinit, noise_ahead.take(x.shape) if (randinit and noise_ahead is not None) else None)
+    loss_of = lambda t: compute_loss(*model.train().forward({"x": t, "adv": None, "out_idx": -1, "flag": "clean"}, y["bb"], y["lb"]))
     for _ in range(steps):
-        _ascend(x_adv, lambda t: compute_loss(*model.train().forward({"x": t, "adv": None, "out_idx": -1, "flag": "clean"},
-                                                                     y["bb"], y["lb"])), gamma, x, eps, clip)
-    ops.tensor_clamp_(x_adv, torch.zeros_like(x_adv), torch.ones_like(x_adv))
-    return x_adv.requires_grad_(True)
+        pgd.ascend(x_adv, loss_of, gamma, x, eps, clip)
+    return pgd.clamp01_(x_adv).requires_grad_(True)
 
 
 def det_train_step(model, optimizer, image_batch, bboxes_batch, labels_batch, loss_settings=1):

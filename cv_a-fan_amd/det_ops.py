@@ -8,7 +8,7 @@ and return contract as the reference's extension layer:
     PGD(x, image_batch, y, model, steps, eps, gamma, idx, randinit, clip)        Detection/attack_algo.py:48-74
 
 The kernels live in libafan_hip.so (afan_det.hip); there is no CPU fallback.  The Faster-RCNN model itself (model.py, rpn/,
-roi/) is not part of this slice: `PGD` drives any module that follows the reference's protocol
+roi/) is not part of this slice: `PGD` (pgd.py's loop) drives any module that follows the reference's protocol
 `model.train().forward({'x','adv','out_idx','flag'}, bboxes, labels) -> 4 loss tensors`."""
 import ctypes as C
 import os
@@ -17,10 +17,9 @@ import torch
 import torch.nn as nn
 from torch.nn.modules.utils import _pair
 
-from . import _lib, ops
+from . import _lib, ops, pgd
 from ._lib import check
 from .attack_algo import get_sample_points, linfball_proj, mix_feature, tensor_clamp  # noqa: F401 (Detection/attack_algo.py:236-265)
-from .resnet_s import dgrad_only
 
 _ws = {}
 
@@ -352,24 +351,8 @@ class Pooler(object):
 def PGD(x, image_batch, y=None, model=None, steps=3, eps=None, gamma=None, idx=1, randinit=False, clip=False):
     """Detection/attack_algo.py:48-74: K-step sign-gradient ascent on the backbone feature map `x` under the SUM of the four
     detection losses (each a mean).  Returns a new fp32 leaf with requires_grad=True; `x` is not modified."""
-    if x.device.type != "cuda":
-        raise ops.AfanLibraryError("PGD: x must live on the MI355X (no CPU path in this build)")
-    x = x.detach().float()
-    x = x if (x.is_contiguous() or (x.dim() == 4 and x.is_contiguous(memory_format=torch.channels_last))) else x.contiguous()
-    x_adv = x.clone()
-    if randinit:
-        u = torch.rand(x_adv.shape).to(x.device, non_blocking=True)
-        if u.stride() != x_adv.stride():
-            u = u.contiguous(memory_format=torch.channels_last)
-        ops.axpy_noise_(x_adv, u, eps)
+    x, x_adv = pgd.start(x, eps, randinit)
+    loss_of = lambda t: sum_of_means(*model.train().forward({"x": image_batch, "adv": t, "out_idx": idx, "flag": "tail"}, y["bb"], y["lb"]))
     for _ in range(steps):
-        xin = x_adv.detach().requires_grad_(True)
-        inputs = {"x": image_batch, "adv": xin, "out_idx": idx, "flag": "tail"}
-        with dgrad_only():      # only_inputs=True (:66): the library's layers skip (and must not add into) parameter gradients
-            l1, l2, l3, l4 = model.train().forward(inputs, y["bb"], y["lb"])
-            loss = sum_of_means(l1, l2, l3, l4)
-            grad = torch.autograd.grad(loss, xin, only_inputs=True)[0]
-        if grad.stride() != x_adv.stride():
-            grad = grad.contiguous(memory_format=torch.channels_last) if (x_adv.dim() == 4 and not x_adv.is_contiguous()) else grad.contiguous()
-        ops.pgd_step_(x_adv, grad, gamma, x, eps if eps is not None else 0.0, clip)
+        pgd.ascend(x_adv, loss_of, gamma, x, eps, clip)
     return x_adv.requires_grad_(True)

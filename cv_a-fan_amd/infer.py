@@ -10,8 +10,8 @@ a fused 1x1 convolution (the eager path's own decomposition); under AFAN_STEM7_D
 by one afan_affine_apply.
 
 The forward reads only buffers the Evaluator owns (bf16 weight copies, [4][C] coefficient blocks, the head's parameters),
-rewritten in place by refresh() at the start of every evaluation pass, so one hipGraph per batch shape — captured on the
-shape's second pass, forward + criterion + accuracy — serves every epoch.  fp32, NCHW, or a criterion other than a default
+rewritten in place by refresh() at the start of every evaluation pass, so one hipGraph per batch shape (_ShapeGraphs: forward +
+criterion + accuracy) serves every epoch.  fp32, NCHW, or a criterion other than a default
 nn.CrossEntropyLoss: the model's own eager forward.
 
 Attacker (below) is its counterpart for robust accuracy: image-space PGD on the eval-mode model, forward and backward one launch per
@@ -19,7 +19,7 @@ convolution, the whole attack one hipGraph per batch shape."""
 import torch
 import torch.nn as nn
 
-from . import ops, resnet_s
+from . import ops, pgd, resnet_s
 from .deeplab import StemConv, _Stem7Fn
 
 
@@ -30,6 +30,53 @@ def accuracy(output, target):
 
 class _Unfused(Exception):
     """A layer of this batch shape is not on the library's bf16 MFMA kernels in the eager path: evaluate eagerly."""
+
+
+class _ShapeGraphs:
+    """The per-batch-shape schedule of Evaluator and Attacker: eager on a key's first sight, captured into a hipGraph on its second (a
+    shape that recurs every epoch gets its graph; its first pass was the warm-up), replayed from then on.  fused_fn(*statics) -> tuple
+    of outputs is what gets captured (a static input may be None); where it raises _Unfused the shape is remembered and eager_fn
+    runs, now and ever after.  A replay hands out clones of the outputs — except the first `borrow` of them, which stay the graph's
+    own static tensors (overwritten by the next replay)."""
+
+    def __init__(self, fused_fn, eager_fn, borrow=0):
+        self.fused_fn, self.eager_fn, self.borrow = fused_fn, eager_fn, borrow
+        self._graphs, self._seen, self._eager_shapes = {}, {}, set()
+        self._pool = None               # one memory pool for the instance's graphs
+
+    def __call__(self, key, shape, *inputs):
+        g = self._graphs.get(key)
+        if g is not None:
+            graph, statics, outs = g
+            for s, t in zip(statics, inputs):
+                if s is not None:
+                    s.copy_(t)
+            graph.replay()
+            return outs[:self.borrow] + tuple(o.clone() for o in outs[self.borrow:])
+        if shape in self._eager_shapes:
+            return self.eager_fn(*inputs)
+        try:
+            r = self.fused_fn(*inputs)
+        except _Unfused:
+            self._eager_shapes.add(shape)
+            return self.eager_fn(*inputs)
+        self._seen[key] = self._seen.get(key, 0) + 1
+        if self._seen[key] >= 2:
+            self._capture(key, inputs)
+        return r
+
+    def _capture(self, key, inputs):
+        dev = inputs[0].device
+        statics = tuple(None if t is None else t.clone() for t in inputs)
+        stream = torch.cuda.Stream(device=dev)
+        stream.wait_stream(torch.cuda.current_stream(dev))
+        graph = torch.cuda.CUDAGraph()
+        with ops.capturing(graph, stream, self._pool):
+            outs = tuple(self.fused_fn(*statics))
+        torch.cuda.current_stream(dev).wait_stream(stream)
+        if self._pool is None:
+            self._pool = graph.pool()
+        self._graphs[key] = (graph, statics, outs)
 
 
 def _default_ce(criterion):
@@ -100,8 +147,7 @@ class Evaluator:
         self.fused = (isinstance(model, resnet_s.ResNet) and type(model).forward is resnet_s.ResNet.forward
                       and model.compute_dtype == torch.bfloat16 and model.channels_last and _default_ce(criterion)
                       and next(model.parameters()).is_cuda)
-        self._graphs, self._seen, self._eager_shapes = {}, {}, set()
-        self._pool = None
+        self._shapes = _ShapeGraphs(self._fused_step, self._eager, borrow=1)
         self.last_logits = None          # logits of the last evaluate() (a graph's static output after a replay)
         if self.fused:
             self._plan()
@@ -190,65 +236,31 @@ class Evaluator:
                 try:
                     return self._forward(inp)
                 except _Unfused:
-                    self._eager_shapes.add(tuple(inp.shape))
+                    self._shapes._eager_shapes.add(tuple(inp.shape))
             m = self.model
             return m(inp, end_point=m.layer_number, start_point=0)
 
     def _shape_fused(self, inp):
-        return tuple(inp.shape) not in self._eager_shapes
+        return tuple(inp.shape) not in self._shapes._eager_shapes
 
     def evaluate(self, inp, target):
         """(loss, prec1) of one batch as device scalars; nothing is read back here."""
         with torch.no_grad():
             if not self.fused:
-                return self._run(self._eager, inp, target)
-            key = (tuple(inp.shape), inp.dtype, tuple(target.shape), target.dtype)
-            g = self._graphs.get(key)
-            if g is not None:
-                graph, sx, sy, out, loss, prec = g
-                sx.copy_(inp)
-                sy.copy_(target)
-                graph.replay()
-                self.last_logits = out
-                return loss.clone(), prec.clone()
-            if not self._shape_fused(inp):
-                return self._run(self._eager, inp, target)
-            try:
-                r = self._run(self._fused_step, inp, target)
-            except _Unfused:
-                self._eager_shapes.add(tuple(inp.shape))
-                return self._run(self._eager, inp, target)
-            self._seen[key] = self._seen.get(key, 0) + 1
-            if self._seen[key] >= 2:            # a shape that recurs (every epoch) gets its graph; its first pass was the warm-up
-                self._capture(key, inp, target)
-            return r
-
-    def _run(self, fn, inp, target):
-        out, loss, prec = fn(inp, target)
-        self.last_logits = out
-        return loss, prec
-
-    def _capture(self, key, inp, target):
-        dev = inp.device
-        sx, sy = inp.clone(), target.clone()
-        stream = torch.cuda.Stream(device=dev)
-        stream.wait_stream(torch.cuda.current_stream(dev))
-        graph = torch.cuda.CUDAGraph()
-        with ops.no_gc_during_capture(), torch.cuda.graph(graph, pool=self._pool, stream=stream, capture_error_mode="thread_local"):
-            out, loss, prec = self._fused_step(sx, sy)
-        torch.cuda.current_stream(dev).wait_stream(stream)
-        if self._pool is None:
-            self._pool = graph.pool()
-        self._graphs[key] = (graph, sx, sy, out, loss, prec)
+                out, loss, prec = self._eager(inp, target)
+            else:
+                key = (tuple(inp.shape), inp.dtype, tuple(target.shape), target.dtype)
+                out, loss, prec = self._shapes(key, tuple(inp.shape), inp, target)
+            self.last_logits = out
+            return loss, prec
 
 
 class Attacker:
     """Image-space L-inf PGD on the model in eval mode — the robust-accuracy counterpart of Evaluator, whose private weight
     copies and coefficient blocks it shares (refresh() rewrites both).  attack(inp, target) -> (x_adv, loss_adv, prec_adv) on the
-    device.  The schedule is seg_attack_algo.adv_input's (Segmentation/attack_algo.py:86-105): start at the clean image (plus
-    (2u - 1) * eps with u drawn by the HOST's default generator when randinit), `steps` times x_adv += gamma * sign(d loss / d x_adv)
-    projected onto the eps-ball around the clean image (ops.pgd_step_(clip=True)), then one clamp to [0, 1]; loss_adv / prec_adv are
-    the criterion and top-1 precision of the model on x_adv.  eps and gamma are in pixel units ([0, 1] images).
+    device.  The schedule is seg_attack_algo.adv_input's (Segmentation/attack_algo.py:86-105), built from pgd.py like it: pgd.start
+    (the HOST draws the random start), `steps` projected sign steps, one clamp to [0, 1]; loss_adv / prec_adv are the criterion and
+    top-1 precision of the model on x_adv.  eps and gamma are in pixel units ([0, 1] images).
 
     bf16 channels-last BasicBlock ResNets (ResNet-20s / -56s / -18) run fused: the forward is Evaluator's (one launch per convolution)
     with its activations kept, the backward one launch per convolution where a kernel has the form — the input gradient with the
@@ -266,8 +278,7 @@ class Attacker:
         ev = self.ev
         self.fused = bool(ev.fused and not ev.pre and not ev.stem.stem7 and ev.stem.relu
                           and all(isinstance(blk, resnet_s.BasicBlock) for blk, _, _ in ev.blocks))
-        self._graphs, self._seen, self._eager_shapes = {}, {}, set()
-        self._pool = None
+        self._shapes = _ShapeGraphs(self._fused_attack, self.attack_eager)
         self.inv_std = None
 
     def refresh(self):
@@ -343,22 +354,13 @@ class Attacker:
         gx = ops.conv_general_dgrad(pend[0], st.w, xn.shape[2:], st.stride, int(st.conv.padding[0]), 1)
         return ops.affine_relu_backward(gx.float().contiguous(), None, self.inv_std, False)[0]
 
-    def _start(self, x, u):
-        x_adv = x.clone()
-        if self.randinit:
-            ops.axpy_noise_(x_adv, u, self.eps)
-        return x_adv
-
-    def _finish(self, x_adv):
-        ops.tensor_clamp_(x_adv, torch.zeros_like(x_adv), torch.ones_like(x_adv))
-
     def _fused_attack(self, x, target, u):
-        x_adv = self._start(x, u)
+        x, x_adv = pgd.start(x, self.eps, self.randinit, u)
         for _ in range(self.steps):
             logits, saved = self._forward(x_adv)
             _, dlogits = ops.cross_entropy(logits, target)
-            ops.pgd_step_(x_adv, self._backward(dlogits, saved), self.gamma, x, self.eps, True)
-        self._finish(x_adv)
+            pgd.step(x_adv, self._backward(dlogits, saved), self.gamma, x, self.eps, True)
+        pgd.clamp01_(x_adv)
         out = self.ev._forward(x_adv)
         return x_adv, self.criterion(out, target).float(), accuracy(out.float(), target)
 
@@ -366,19 +368,12 @@ class Attacker:
     def attack_eager(self, inp, target, u=None):
         """The same schedule through the model's own eval-mode forward and autograd (any dtype, layout and criterion)."""
         m = self.model
-        x = inp.detach().float().contiguous()
-        if self.randinit and u is None:
-            u = torch.rand(x.shape).to(x.device, non_blocking=True)
-        x_adv = self._start(x, u)
+        x, x_adv = pgd.start(inp.detach().float().contiguous(), self.eps, self.randinit, u)
         crit = resnet_s.fused_criterion(self.criterion, m)
+        loss_of = lambda t: crit(m(t, end_point=m.layer_number, start_point=0), target)
         for _ in range(self.steps):
-            xin = x_adv.detach().requires_grad_(True)
-            with torch.enable_grad(), resnet_s.dgrad_only():
-                loss = crit(m(xin, end_point=m.layer_number, start_point=0), target)
-                root = ops.one(loss.device) if (loss.dim() == 0 and loss.dtype == torch.float32) else None
-                grad = torch.autograd.grad(loss, xin, grad_outputs=root, only_inputs=True)[0]
-            ops.pgd_step_(x_adv, grad.float().contiguous(), self.gamma, x, self.eps, True)
-        self._finish(x_adv)
+            pgd.ascend(x_adv, loss_of, self.gamma, x, self.eps, True)
+        pgd.clamp01_(x_adv)
         with torch.no_grad():
             out = m(x_adv, end_point=m.layer_number, start_point=0)
             return x_adv, self.criterion(out, target).float(), accuracy(out.float(), target)
@@ -392,41 +387,10 @@ class Attacker:
         x = inp.detach().float().contiguous()
         # the host draws the random start (the reference's attack_algo.py:44), whichever path runs
         u = torch.rand(x.shape).to(x.device, non_blocking=True) if self.randinit else None
-        if not self.fused or tuple(x.shape) in self._eager_shapes:
+        if not self.fused:
             return self.attack_eager(x, target, u)
         with torch.no_grad():
-            key = (tuple(x.shape), tuple(target.shape), target.dtype)
-            g = self._graphs.get(key)
-            if g is not None:
-                graph, sx, sy, su, x_adv, loss, prec = g
-                sx.copy_(x)
-                sy.copy_(target)
-                if su is not None:
-                    su.copy_(u)
-                graph.replay()
-                return x_adv.clone(), loss.clone(), prec.clone()
-            try:
-                r = self._fused_attack(x, target, u)
-            except _Unfused:
-                self._eager_shapes.add(tuple(x.shape))
-                return self.attack_eager(x, target, u)
-            self._seen[key] = self._seen.get(key, 0) + 1
-            if self._seen[key] >= 2:            # (as Evaluator: a shape that recurs gets its graph, its first pass was the warm-up)
-                self._capture(key, x, target, u)
-            return r
-
-    def _capture(self, key, x, target, u):
-        dev = x.device
-        sx, sy, su = x.clone(), target.clone(), (u.clone() if u is not None else None)
-        stream = torch.cuda.Stream(device=dev)
-        stream.wait_stream(torch.cuda.current_stream(dev))
-        graph = torch.cuda.CUDAGraph()
-        with ops.no_gc_during_capture(), torch.cuda.graph(graph, pool=self._pool, stream=stream, capture_error_mode="thread_local"):
-            x_adv, loss, prec = self._fused_attack(sx, sy, su)
-        torch.cuda.current_stream(dev).wait_stream(stream)
-        if self._pool is None:
-            self._pool = graph.pool()
-        self._graphs[key] = (graph, sx, sy, su, x_adv, loss, prec)
+            return self._shapes((tuple(x.shape), tuple(target.shape), target.dtype), tuple(x.shape), x, target, u)
 
 
 def evaluator_for(model, criterion):

@@ -2,6 +2,7 @@
 device memory and the stream; every arithmetic op below runs in libafan_hip.so.  No fallbacks: a CPU
 tensor, a non-contiguous tensor or a missing library raises.
 """
+import contextlib
 import ctypes as C
 import os
 import threading
@@ -1023,6 +1024,14 @@ class no_gc_during_capture:
             import gc
             gc.enable()
         return False
+
+
+@contextlib.contextmanager
+def capturing(graph, stream=None, pool=None):
+    """torch.cuda.graph with what every capture here needs: no garbage collection meanwhile (freeing another trainer's graph or
+    stream in the middle of a capture aborts the process), errors confined to this thread."""
+    with no_gc_during_capture(), torch.cuda.graph(graph, pool=pool, stream=stream, capture_error_mode="thread_local"):
+        yield
 
 
 def grid_shared(on):

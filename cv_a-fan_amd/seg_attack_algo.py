@@ -7,41 +7,14 @@ reference's `Segmentation/attack_algo.py`:
     get_sample_points / mix_feature / tensor_clamp / linfball_proj                  (shared with attack_algo.py)
 
 `model` is anything that follows the reference's dict-dispatch protocol (`Segmentation/network/utils.py:14-47`):
-`model({'x', 'adv', 'out_idx', 'flag', 'low_level_feat'}) -> logits | feature dict`.  The sign-step / projection / noise /
-mix / lerp arithmetic runs in libafan_hip.so; the model's own layers are whatever the caller built (the DeepLabv3+
-network with the library's kernels is the next slice)."""
+`model({'x', 'adv', 'out_idx', 'flag', 'low_level_feat'}) -> logits | feature dict`.  The three attacks are pgd.py's loop around
+that protocol; the mix / lerp arithmetic runs in libafan_hip.so; the model's own layers are whatever the caller built."""
 import contextlib
 
 import torch
 
-from . import ops
+from . import ops, pgd
 from .attack_algo import get_sample_points, linfball_proj, mix_feature, sample_points_mixed, tensor_clamp  # noqa: F401 (same functions)
-from .resnet_s import dgrad_only
-
-
-def _start(x, eps, randinit):
-    if x.device.type != "cuda":
-        raise ops.AfanLibraryError("x must live on the MI355X (no CPU path in this build)")
-    x = x.detach().float()
-    x = x if (x.is_contiguous() or (x.dim() == 4 and x.is_contiguous(memory_format=torch.channels_last))) else x.contiguous()
-    x_adv = x.clone()     # keeps the feature map's own dense layout (channels-last on the bf16 path: no transposes per step)
-    if randinit:   # noise from the CPU default generator, like the reference (:44)
-        u = torch.rand(x_adv.shape).to(x.device, non_blocking=True)
-        if u.stride() != x_adv.stride():
-            u = u.contiguous(memory_format=torch.channels_last)
-        ops.axpy_noise_(x_adv, u, eps)
-    return x, x_adv
-
-
-def _ascend(x_adv, logits_of, criterion, y, gamma, x, eps, clip):
-    xin = x_adv.detach().requires_grad_(True)
-    with dgrad_only():          # only_inputs=True (:52): the library's layers must not add into the parameters' .grad here
-        loss = criterion(logits_of(xin), y)
-        root = ops.one(loss.device) if (getattr(criterion, "fused", False) and loss.dim() == 0) else None
-        grad = torch.autograd.grad(loss, xin, grad_outputs=root, only_inputs=True)[0]
-    if grad.stride() != x_adv.stride():
-        grad = grad.contiguous(memory_format=torch.channels_last) if x_adv.is_contiguous(memory_format=torch.channels_last) and not x_adv.is_contiguous() else grad.contiguous()
-    ops.pgd_step_(x_adv, grad, gamma, x, eps, clip)          # one launch: sign step (+ projection)
 
 
 def _low_res(criterion):
@@ -65,27 +38,20 @@ def _halves(o):
     return o[:n], o[n:]
 
 
-def _first_step(x_adv, grad0, gamma, x, eps, clip):
-    """The first ascent step from a gradient the caller already has (a positive multiple of d(loss)/d(x) at x itself)."""
-    g = grad0.detach()
-    if g.stride() != x_adv.stride():
-        g = g.contiguous(memory_format=torch.channels_last) if (x_adv.dim() == 4 and not x_adv.is_contiguous()) else g.contiguous()
-    ops.pgd_step_(x_adv, g, gamma, x, eps if eps is not None else 0.0, clip)
-
-
 def PGD(x, image_batch, low_level_feat, criterion, y=None, model=None, steps=3, eps=None, gamma=None, idx=1,
         randinit=False, clip=False, grad0=None):
     """SE-branch feature PGD (:40-59).  Returns a new fp32 leaf with requires_grad=True; `x` is not modified.
     grad0 (an addition; not with randinit): the first step's gradient, computed by the caller's clean pass."""
     if grad0 is not None and (randinit or steps < 1):
         raise ValueError("grad0 is the gradient at x: not with randinit, and only when there is a first step")
-    x, x_adv = _start(x, eps, randinit)
+    x, x_adv = pgd.start(x, eps, randinit)
+    loss_of = lambda t: criterion(model({"x": image_batch, "adv": t, "out_idx": idx, "flag": "tail", "low_level_feat": low_level_feat,
+                                         "low_res": _low_res(criterion)}), y)
     for t in range(steps):
         if t == 0 and grad0 is not None:
-            _first_step(x_adv, grad0, gamma, x, eps, clip)
-            continue
-        _ascend(x_adv, lambda t: model({"x": image_batch, "adv": t, "out_idx": idx, "flag": "tail",
-                                        "low_level_feat": low_level_feat, "low_res": _low_res(criterion)}), criterion, y, gamma, x, eps, clip)
+            pgd.step(x_adv, grad0, gamma, x, eps, clip)
+        else:
+            pgd.ascend(x_adv, loss_of, gamma, x, eps, clip)
     return x_adv.requires_grad_(True)
 
 
@@ -96,17 +62,18 @@ def decoder_PGD(input_dict, image_batch, criterion, y=None, model=None, steps=3,
     neither does this: same exception."""
     if grad0 is not None and (randinit or steps < 1):
         raise ValueError("grad0 is the gradient at the clean feature: not with randinit, and only when there is a first step")
-    _, x_adv = _start(input_dict["adv"], eps, randinit)
+    _, x_adv = pgd.start(input_dict["adv"], eps, randinit)
     input_dict["adv"] = x_adv
+
+    def loss_of(t):
+        d = dict(input_dict)
+        d["adv"] = t
+        return criterion(model({"x": image_batch, "adv": d, "out_idx": idx + "_tail", "flag": "clean", "low_res": _low_res(criterion)}), y)
     for t in range(steps):
-        def logits_of(t):
-            d = dict(input_dict)
-            d["adv"] = t
-            return model({"x": image_batch, "adv": d, "out_idx": idx + "_tail", "flag": "clean", "low_res": _low_res(criterion)})
         if t == 0 and grad0 is not None:
-            _first_step(x_adv, grad0, gamma, None, 0.0, False)
+            pgd.step(x_adv, grad0, gamma, None, None, False)
         else:
-            _ascend(x_adv, logits_of, criterion, y, gamma, None, 0.0, False)
+            pgd.ascend(x_adv, loss_of, gamma, None, None, False)
         if clip:
             raise NameError("name 'x' is not defined")
     input_dict["adv"] = x_adv.requires_grad_(True)
@@ -116,13 +83,12 @@ def decoder_PGD(input_dict, image_batch, criterion, y=None, model=None, steps=3,
 def adv_input(x=None, criterion=None, y=None, model=None, steps=3, eps=None, gamma=None, randinit=False, clip=False):
     """Image-space PGD (:86-105), clamped to [0, 1] at the end.  With seg_criterion's fused callable the model hands back its
     low-resolution logits and the criterion resizes inside its own kernel, as in PGD / decoder_PGD."""
-    x, x_adv = _start(x, eps, randinit)
+    x, x_adv = pgd.start(x, eps, randinit)
+    loss_of = lambda t: criterion(model({"x": t, "adv": None, "out_idx": 0, "flag": "clean", "low_level_feat": None,
+                                         "low_res": _low_res(criterion)}), y)
     for _ in range(steps):
-        _ascend(x_adv, lambda t: model({"x": t, "adv": None, "out_idx": 0, "flag": "clean", "low_level_feat": None,
-                                        "low_res": _low_res(criterion)}), criterion, y, gamma, x, eps, clip)
-    lo, hi = torch.zeros_like(x_adv), torch.ones_like(x_adv)
-    ops.tensor_clamp_(x_adv, lo, hi)
-    return x_adv.requires_grad_(True)
+        pgd.ascend(x_adv, loss_of, gamma, x, eps, clip)
+    return pgd.clamp01_(x_adv).requires_grad_(True)
 
 
 def _dropout_active(model):

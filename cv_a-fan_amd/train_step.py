@@ -380,7 +380,7 @@ class StepTrainer(GuardedTrainer):
         with self._around(inp):
             if not self._use_phases(inp):
                 g = torch.cuda.CUDAGraph()
-                with _capturing(g, stream):
+                with ops.capturing(g, stream):
                     out = self._graph_body(*static)
                 self._graph, self._static_in, self._static_out = g, static, out
                 return
@@ -390,7 +390,7 @@ class StepTrainer(GuardedTrainer):
                 while True:
                     n0 = ops.CALLS["conv_bn_fused"]
                     g = torch.cuda.CUDAGraph()
-                    with _capturing(g, stream, pool=pieces[0][0].pool() if pieces else None):
+                    with ops.capturing(g, stream, pool=pieces[0][0].pool() if pieces else None):
                         label = next(gen, None)
                     pieces.append((g, label))
                     fused.append(ops.CALLS["conv_bn_fused"] - n0)      # convolution + BatchNorm launches in this piece
@@ -425,14 +425,6 @@ class StepTrainer(GuardedTrainer):
             self._update()
         # graph-owned outputs are overwritten by the next replay: hand out copies of the small ones
         return {k: (v.clone() if k in self._small else v) for k, v in self._static_out.items()}
-
-
-@contextlib.contextmanager
-def _capturing(graph, stream, pool=None):
-    """torch.cuda.graph with what every capture here needs: no garbage collection meanwhile (freeing another trainer's graph or
-    stream in the middle of a capture aborts the process), errors confined to this thread."""
-    with ops.no_gc_during_capture(), torch.cuda.graph(graph, pool=pool, stream=stream, capture_error_mode="thread_local"):
-        yield
 
 
 class AfanTrainer(StepTrainer):

@@ -53,7 +53,7 @@ def main():
         t_eager = timed(lambda: at.attack_eager(x, y), a.iters)
         t_at = timed(lambda: at.attack(x, y), a.iters)
         rec = {"arch": arch, "batch": n, "image": side, "steps": a.steps, "eager_ms": round(t_eager, 4), "attacker_ms": round(t_at, 4),
-               "speedup": round(t_eager / t_at, 3), "fused": at.fused, "graphs": len(at._graphs)}
+               "speedup": round(t_eager / t_at, 3), "fused": at.fused, "graphs": len(at._shapes._graphs)}
         print(json.dumps(rec), flush=True)
         lines.append(rec)
     if a.out:

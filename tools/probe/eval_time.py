@@ -59,7 +59,7 @@ def main():
         t_eager = timed(eager, a.iters)
         t_ev = timed(lambda: ev.evaluate(x, y), a.iters)
         rec = {"arch": arch, "batch": n, "image": side, "eager_ms": round(t_eager, 4), "evaluator_ms": round(t_ev, 4),
-               "speedup": round(t_eager / t_ev, 3), "graphs": len(ev._graphs)}
+               "speedup": round(t_eager / t_ev, 3), "graphs": len(ev._shapes._graphs)}
         print(json.dumps(rec), flush=True)
         lines.append(rec)
     if a.out:
