@@ -10,11 +10,13 @@ DeepLabv3+ split-forward network), seg_attack_algo / seg_trainer (the Segmentati
 segmentation batches; main_aug_final is the entry point for cmd/run_seg.sh, main_ori for cmd/run_seg_base.sh), seg_entry (what the Segmentation entry
 points share: the parser, set-up, checkpoint and restore, the iteration loop), seg_eval (StreamSegMetrics with a one-launch confusion
 matrix, validate; main_seg_val scores a checkpoint, cmd/run_seg_val.sh), det_ops / det_attack_algo / det_model / det_trainer
-(the Detection operators, iteration, the Faster-RCNN / ResNet-101 model and its data-parallel trainer).
+(the Detection operators, iteration, the Faster-RCNN / ResNet-101 model and its data-parallel trainer), det_data (DetDeviceLoader: one-launch
+detection batches with their boxes), det_entry (the Detection parser, learning-rate schedule, checkpoint and iteration loop;
+train_aug_sat_muti_advt is the entry point for cmd/run_det.sh).
 """
 from . import _lib, ops  # noqa: F401
 from ._lib import AfanLibraryError, LIB_PATH  # noqa: F401
-from . import resnet_s, pgd, attack_algo, arena, grid_guard, train_step, learnable, seg_attack_algo, deeplab, seg_trainer, seg_data, seg_eval, det_ops, det_attack_algo, det_model, det_trainer, host, infer  # noqa: F401
+from . import resnet_s, pgd, attack_algo, arena, grid_guard, train_step, learnable, seg_attack_algo, deeplab, seg_trainer, seg_data, seg_eval, det_ops, det_attack_algo, det_model, det_trainer, det_data, det_entry, host, infer  # noqa: F401
 from .attack_algo import PGD, get_sample_points, linfball_proj, mix_feature, tensor_clamp  # noqa: F401
 
 __version__ = "0.1.0"

@@ -160,6 +160,7 @@ SIGNATURES = {
     "afan_normalize_nchw": (_i, [_p, _p, _i, _i, _l, _l, _l, _p, _p, _p]),
     "afan_batch_crop_flip_u8": (_i, [_p, _p, _l, _p, _p, _p, _p, _p, _p, _l, _l, _l, _l, _i, _p]),
     "afan_seg_batch_aug_u8": (_i, [_p, _p, _p, _p, _p, _l, _l, _p, _p, _p, _p, _p, _p, _p, _p, _l, _l, _l, C.c_double, _p]),
+    "afan_det_batch_resize_u8": (_i, [_p, _p, _p, _p, _l, _l, _p, _p, _p, _l, _p, _p, _p, _p, _p, _p, _p, _p, _l, _l, _l, _l, C.c_double, _p]),
     "afan_seg_batch_aug_jitter_u8": (_i, [_p, _p, _p, _p, _p, _l, _l, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _l, _l, _l,
                                           C.c_double, _p]),
     "afan_profile_enable": (_i, [_i]),

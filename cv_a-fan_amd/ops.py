@@ -21,8 +21,8 @@ _tls = threading.local()
 # "conv_general" counts passes of the fp32-arithmetic general kernels, afan_conv_f32.hip)
 class _Calls(dict):
     """The convolution counters are the dict's own items: what the logs and the tests enumerate (`dict(CALLS)`, `set(CALLS)`).
-    Counters of launches outside the convolution path (`batch_crop_flip`, `seg_batch_aug`, `seg_batch_aug_jitter`: the loaders'
-    kernels; `seg_confusion`:
+    Counters of launches outside the convolution path (`batch_crop_flip`, `seg_batch_aug`, `seg_batch_aug_jitter`, `det_batch_resize`:
+    the loaders' kernels; `seg_confusion`:
     validation's scoring kernel) live in `.other` and are read and
     written through the same subscript, `in` and `.get`, so that the enumerated table stays the convolution table
     (tests/test_host_logic.py::test_no_convolution_leaves_the_library pins `set(CALLS)` to the six convolution counters)."""
@@ -48,7 +48,7 @@ class _Calls(dict):
 
 
 CALLS = _Calls({"conv_fwd": 0, "conv_dgrad": 0, "conv_wgrad": 0, "conv_general": 0, "vendor_conv": 0, "conv_bn_fused": 0},
-               {"batch_crop_flip": 0, "seg_batch_aug": 0, "seg_batch_aug_jitter": 0, "seg_confusion": 0})
+               {"batch_crop_flip": 0, "seg_batch_aug": 0, "seg_batch_aug_jitter": 0, "seg_confusion": 0, "det_batch_resize": 0})
 
 
 def _need(t, name, dtype=None):
@@ -2200,6 +2200,49 @@ def seg_batch_aug_jitter(images, offsets, labels, hs, ws, index, oh, ow, top, le
                                            int(out_w), float(max_shrink), _stream(images)), "afan_seg_batch_aug_jitter_u8")
     CALLS["seg_batch_aug_jitter"] += 1
     return out, labels_out
+
+
+def det_batch_resize(images, offsets, hs, ws, boxes, classes, box_off, index, oh, ow, flip, scale, out_h, out_w, g_max, max_shrink=3.0):
+    """One detection batch from a resident split of variably sized images in one launch (afan_det_batch_resize_u8): images[index[b]]
+    mirrored where flip[b], Pillow's bilinear resize to (oh[b], ow[b]) at the top-left of an (out_h, out_w) plane of zeros, scaled by the
+    correctly rounded v / 255; the sample's boxes mirrored (l' = w - r, r' = w - l), multiplied by scale[b] and padded with zero rows
+    (label 0) up to g_max.  images: packed HWC uint8, offsets: int64 byte offsets, hs / ws: int32; boxes: fp32 [total, 4] (left, top,
+    right, bottom), classes: int64 [total], box_off: int64 [n + 1]; index, oh, ow, flip: int64 [m] (rows of one uploaded tensor will
+    do), scale: fp32 [m].  Returns (fp32 [m, 3, out_h, out_w], fp32 [m, g_max, 4], int64 [m, g_max]).  Out-of-range parameters are
+    clamped by the kernel; max_shrink (<= 3) is the caller's bound on in/out."""
+    lib = _lib.load()
+    _need(images, "images", torch.uint8)
+    _need(offsets, "offsets", torch.int64)
+    _need(hs, "hs", torch.int32)
+    _need(ws, "ws", torch.int32)
+    _need(boxes, "boxes", torch.float32)
+    _need(classes, "classes", torch.int64)
+    _need(box_off, "box_off", torch.int64)
+    per = (index, oh, ow, flip)
+    for t, name in zip(per, ("index", "oh", "ow", "flip")):
+        _need(t, name, torch.int64)
+    _need(scale, "scale", torch.float32)
+    m = index.shape[0]
+    if any(t.dim() != 1 or t.shape[0] != m for t in per + (scale,)):
+        raise ValueError("det_batch_resize: index, oh, ow, flip (int64) and scale (fp32) are vectors with one entry per sample")
+    n = offsets.shape[0]
+    if images.dim() != 1 or images.shape[0] % 3 or hs.shape != (n,) or ws.shape != (n,) or box_off.shape != (n + 1,):
+        raise ValueError("det_batch_resize: images is packed HWC uint8, offsets / hs / ws have one entry per image and box_off one more")
+    total = classes.shape[0]
+    if classes.dim() != 1 or boxes.shape != (total, 4):
+        raise ValueError("det_batch_resize: boxes is fp32 [total, 4] with one class per row")
+    out_h, out_w, g_max = int(out_h), int(out_w), int(g_max)
+    if min(out_h, out_w, g_max) < 0:
+        raise ValueError("det_batch_resize: out_h, out_w and g_max cannot be negative")
+    out = torch.empty((m, 3, out_h, out_w), dtype=torch.float32, device=images.device)
+    boxes_out = torch.empty((m, g_max, 4), dtype=torch.float32, device=images.device)
+    labels_out = torch.empty((m, g_max), dtype=torch.int64, device=images.device)
+    check(lib.afan_det_batch_resize_u8(_ptr(images), _ptr(offsets), _ptr(hs), _ptr(ws), n, images.shape[0] // 3, _ptr(boxes), _ptr(classes),
+                                       _ptr(box_off), total, _ptr(index), _ptr(oh), _ptr(ow), _ptr(flip), _ptr(scale), _ptr(out),
+                                       _ptr(boxes_out), _ptr(labels_out), m, out_h, out_w, g_max, float(max_shrink), _stream(images)),
+          "afan_det_batch_resize_u8")
+    CALLS["det_batch_resize"] += 1
+    return out, boxes_out, labels_out
 
 
 def jitter_factors(factors):

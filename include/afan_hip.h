@@ -866,6 +866,33 @@ int afan_seg_batch_aug_jitter_u8(const uint8_t* images, const int64_t* img_off, 
                                  const float* brightness, const float* contrast, const float* saturation, int64_t* gray_sum, float* out,
                                  int64_t* labels_out, int64_t m, int64_t out_h, int64_t out_w, double max_shrink, afan_stream_t stream);
 
+/* One detection batch in one launch — Detection/dataset/voc2007.py:95-116 and dataset/base.py:75-124 (ImageOps.mirror, Resize to
+ * min side / max side, ToTensor, padding_collate_fn) over a split of VARIABLY SIZED images resident in device memory.
+ * Split: images as for afan_seg_batch_aug_u8 (packed HWC uint8, image k at byte img_off[k] with hs[k] x ws[k] pixels, total_pixels
+ * in all); ground truth boxes_src fp32 [total_boxes, 4] (left, top, right, bottom, 0-based), cls_src int64 [total_boxes], image k
+ * owning rows box_off[k] .. box_off[k + 1] - 1 (box_off: int64 [n_src + 1]).
+ * Per sample b: index[b]; the resized size (oh[b], ow[b]); flip[b] != 0 mirrors; scale[b] (fp32) multiplies the boxes.
+ * out: fp32 NCHW [m, 3, out_h, out_w]; boxes_out: fp32 [m, g_max, 4]; labels_out: int64 [m, g_max].
+ * Image: where flip[b], source column c becomes w - 1 - c BEFORE the resize; then Pillow's 8-bit bilinear resize to oh x ow (horizontal
+ * pass, rounded to uint8, then vertical; double coefficients, 22 fraction bits; a pass whose size does not change is skipped).  The
+ * result sits at the top-left of the plane, everything to the right of ow and below oh is 0; oh > out_h or ow > out_w writes only
+ * the window at the origin.  Scaling: the correctly rounded fl(v / 255.0f).
+ * Boxes: row j < count = box_off[k + 1] - box_off[k]: where flip[b], l' = fl(w - r), r' = fl(w - l) in fp32; then every coordinate is
+ * fl(x * scale[b]) (no fma).  Rows j >= count are 0 with label 0; count > g_max is truncated.  The boxes are written by the
+ * sample's first workgroup of the same launch.
+ * max_shrink in [1, 3] is the caller's bound on in/out of either axis: oh / ow are CLAMPED into [ceil(h / max_shrink), 32768], index
+ * into [0, n_src); a table entry (offset, size, box range) that does not fit into total_pixels / total_boxes yields an all-zero
+ * sample (image, boxes and labels).  No value of the device arrays makes the launch read or write outside its buffers.
+ * Errors: a negative size, out_h, out_w or g_max above 2^20, more than INT_MAX pixels per plane, max_shrink outside [1, 3], or an
+ * empty split with m > 0: AFAN_ESHAPE; a pointer NULL with m > 0: AFAN_ENULL (boxes_src / cls_src may be NULL when total_boxes == 0,
+ * boxes_out / labels_out when g_max == 0); a pointer not aligned to its element: AFAN_EALIGN; m == 0 or an empty plane returns 0
+ * without a launch.  One launch on `stream`, no host synchronisation, capturable into a graph. */
+int afan_det_batch_resize_u8(const uint8_t* images, const int64_t* img_off, const int32_t* hs, const int32_t* ws, int64_t n_src,
+                             int64_t total_pixels, const float* boxes_src, const int64_t* cls_src, const int64_t* box_off,
+                             int64_t total_boxes, const int64_t* index, const int64_t* oh, const int64_t* ow, const int64_t* flip,
+                             const float* scale, float* out, float* boxes_out, int64_t* labels_out, int64_t m, int64_t out_h,
+                             int64_t out_w, int64_t g_max, double max_shrink, afan_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Measurement aid (no reference counterpart): per-launch HIP-event timing of the kernels above, recorded
  * on the launch stream.  afan_profile_enable(1) starts recording (launches are then not graph-capturable),
