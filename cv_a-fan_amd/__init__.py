@@ -12,11 +12,11 @@ points share: the parser, set-up, checkpoint and restore, the iteration loop), s
 matrix, validate; main_seg_val scores a checkpoint, cmd/run_seg_val.sh), det_ops / det_attack_algo / det_model / det_trainer
 (the Detection operators, iteration, the Faster-RCNN / ResNet-101 model and its data-parallel trainer), det_data (DetDeviceLoader: one-launch
 detection batches with their boxes), det_entry (the Detection parser, learning-rate schedule, checkpoint and iteration loop;
-train_aug_sat_muti_advt is the entry point for cmd/run_det.sh).
+train_aug_sat_muti_advt is the entry point for cmd/run_det.sh), det_eval (the VOC 2007 mean AP, the evaluator and the driver of eval.py, cmd/run_det_eval.sh).
 """
 from . import _lib, ops  # noqa: F401
 from ._lib import AfanLibraryError, LIB_PATH  # noqa: F401
-from . import resnet_s, pgd, attack_algo, arena, grid_guard, train_step, learnable, seg_attack_algo, deeplab, seg_trainer, seg_data, seg_eval, det_ops, det_attack_algo, det_model, det_trainer, det_data, det_entry, host, infer  # noqa: F401
+from . import resnet_s, pgd, attack_algo, arena, grid_guard, train_step, learnable, seg_attack_algo, deeplab, seg_trainer, seg_data, seg_eval, det_ops, det_attack_algo, det_model, det_trainer, det_data, det_entry, det_eval, host, infer  # noqa: F401
 from .attack_algo import PGD, get_sample_points, linfball_proj, mix_feature, tensor_clamp  # noqa: F401
 
 __version__ = "0.1.0"

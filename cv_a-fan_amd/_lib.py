@@ -146,6 +146,9 @@ SIGNATURES = {
     "afan_proposal_rows": (_i, [_p, _l, _p, _l, _p, _l, _p, _p, _p]),
     "afan_labels_limit": (_i, [_p, _l, _l, _p, _l, _p]),
     "afan_det_loss_bwd": (_i, [_p, _p, _p, _p, _p, _p, _l, _l, _l, _l, _l, _p, _p, _p]),
+    "afan_det_class_nms_supported": (_i, [_l, _l]),
+    "afan_det_class_nms": (_i, [_p, _p, _p, _p, _l, _l, _l, _f, _f, _f, _f, _p, _p, _p, _p]),
+    "afan_det_pack": (_i, [_p, _p, _p, _l, _l, _p, _p, _p]),
     "afan_roi_align_fwd": (_i, [_p, _p, _p, _i, _i, _l, _l, _l, _l, _i, _i, _f, _i, _p]),
     "afan_roi_align_bwd": (_i, [_p, _p, _p, _i, _i, _l, _l, _l, _l, _l, _i, _i, _f, _i, _p]),
     "afan_roi_align_bwd_workspace_bytes": (_l, [_l, _l, _l]),

@@ -269,6 +269,52 @@ def load_voc_det(root, name, train):
     return images, boxes, classes
 
 
+def load_voc_det_eval(root, name):
+    """The evaluation split of dataset/voc2007.py (Mode.EVAL) together with what voc_eval.py reads from the same files: VOC2007's test.txt
+    (voc20072012 evaluates on it too), EVERY image of the list kept.  -> (images, boxes, classes, image ids, ground truth): boxes /
+    classes are what the loader yields for the image — its non-difficult objects with the `- 1` on every coordinate, fp32 [g, 4] /
+    int64 [g], empty for an image that has none — and ground truth maps an image id to (classes int64 [k], difficult bool [k], boxes
+    int64 [k, 4]) of ALL its objects with the XML's own integers, which is what the matching compares detections with."""
+    import xml.etree.ElementTree as ET
+    if name not in DATASETS:
+        raise ValueError(f"load_voc_det_eval reads {' and '.join(DATASETS)}, not {name!r}")
+    try:
+        from PIL import Image
+    except ImportError as e:
+        raise ImportError("load_voc_det_eval decodes JPEG files with Pillow, which is not installed; --synthetic N needs no files") from e
+    voc_dir = os.path.join(root, 'VOCdevkit', 'VOC2007')
+    ids_txt = os.path.join(voc_dir, 'ImageSets', 'Main', 'test.txt')
+    ann_dir, jpg_dir = os.path.join(voc_dir, 'Annotations'), os.path.join(voc_dir, 'JPEGImages')
+    for path in (ids_txt, ann_dir, jpg_dir):
+        if not os.path.exists(path):
+            raise FileNotFoundError(f"VOC detection data not found: {path} is missing; there is no download in this build")
+    with open(ids_txt, 'r') as f:
+        image_ids = [line.rstrip() for line in f.readlines()]
+    images, boxes, classes, ground_truth = [], [], [], {}
+    for image_id in image_ids:
+        path = os.path.join(ann_dir, f'{image_id}.xml')
+        if not os.path.exists(path):
+            raise FileNotFoundError(f"VOC detection data not found: {path} is missing; there is no download in this build")
+        root_tag = ET.ElementTree(file=path).getroot()
+        cc, dd, raw = [], [], []
+        for obj in root_tag.iterfind('object'):
+            cc.append(CATEGORY_TO_LABEL_DICT[next(obj.iterfind('name')).text])
+            dd.append(next(obj.iterfind('difficult')).text == '1')
+            raw.append([next(obj.iterfind('bndbox/' + k)).text for k in ('xmin', 'ymin', 'xmax', 'ymax')])
+        cc, dd = np.array(cc, np.int64), np.array(dd, bool)
+        ground_truth[image_id] = (cc, dd, np.array([[int(v) for v in r] for r in raw], np.int64).reshape(-1, 4))
+        easy = ~dd
+        boxes.append((np.array([[float(v) for v in r] for r in raw], np.float64).reshape(-1, 4)[easy] - 1).astype(np.float32))
+        classes.append(cc[easy])
+        path = os.path.join(jpg_dir, root_tag.find('filename').text)
+        if not os.path.exists(path):
+            raise FileNotFoundError(f"VOC detection data not found: {path} is missing; there is no download in this build")
+        images.append(np.asarray(Image.open(path).convert("RGB"), dtype=np.uint8))
+    if not images:
+        raise FileNotFoundError(f"VOC detection data not found: the 'test' list under {root} names no image")
+    return images, boxes, classes, image_ids, ground_truth
+
+
 class SyntheticDetSplit:
     """A split for machines without the data: n seeded uint8 images with sides in [min_side, max_side], alternately tall and fat,
     each with 1 to max_boxes boxes inside the image (at least 4 pixels on a side) and classes in 1..classes-1."""
@@ -293,3 +339,13 @@ class SyntheticDetSplit:
 
     def __len__(self):
         return len(self.images)
+
+    @property
+    def image_ids(self):
+        """"000000", "000001", ...: the names an evaluation files its detections under."""
+        return ['{:06d}'.format(i) for i in range(len(self.images))]
+
+    def ground_truth(self):
+        """What load_voc_det_eval returns as ground truth: every object non-difficult, boxes as the 1-based integers an annotation
+        file would hold (the split's own boxes are 0-based)."""
+        return {i: (c.copy(), np.zeros(len(c), bool), b.astype(np.int64) + 1) for i, b, c in zip(self.image_ids, self.boxes, self.classes)}

@@ -1,0 +1,303 @@
+"""Detection evaluation: the VOC 2007 mean AP of the reference (Detection/voc_eval.py, dataset/voc2007.py:118-161, evaluator.py:20-47,
+eval.py) on in-memory arrays, the evaluator around Model.forward in eval mode, and the driver of eval.py.
+
+The metric runs on the host in numpy, float64, operation by operation as the reference does.  What the reference does on the way
+is part of its number and kept:
+  * detections make a round trip through `comp3_det_test_{category}.txt` written with `{:f}`: confidences and coordinates are rounded to
+    six decimals before they are sorted and matched (`round_trip`); with a results directory the files are written as well;
+  * the ground truth of the matching is the XML's raw integer box (voc_eval.py:23-26, no `- 1`) while detections come from 0-based
+    boxes divided by the scale;
+  * difficult objects stay in the ground truth: a detection whose best match is one counts neither way, and npos counts the others;
+  * `np.argsort(-confidence)`, `np.maximum(tp + fp, eps)`, the 11-point metric;
+  * a class without any detection gets AP 0 (voc2007.py:138-139: the reference's indexing of an empty array raises)."""
+import argparse
+import os
+import time
+import uuid
+import warnings
+
+import numpy as np
+
+from .det_data import CATEGORY_TO_LABEL_DICT
+
+LABEL_TO_CATEGORY_DICT = {v: k for k, v in CATEGORY_TO_LABEL_DICT.items()}
+NUM_CLASSES = 21
+MIN_PROB = 0.05                           # evaluator.py:35
+
+
+def round_trip(v):
+    """A value written with `{:f}` and read back (voc2007.py:157 -> voc_eval.py:140-141)."""
+    return float('{:f}'.format(v))
+
+
+def voc_ap(rec, prec, use_07_metric=False):
+    """voc_eval.py:31-62: the 11-point average of the VOC 2007 devkit (the largest precision at recall >= 0, 0.1, ..., 1, each
+    divided by 11 and added in that order; 0 where no recall reaches the point), or the area under the precision envelope."""
+    if use_07_metric:
+        total = 0.
+        for point in np.arange(0., 1.1, 0.1):
+            reached = rec >= point
+            best = 0 if np.sum(reached) == 0 else np.max(prec[reached])
+            total = total + best / 11.
+        return total
+    r = np.concatenate(([0.], rec, [1.]))
+    p = np.concatenate(([0.], prec, [0.]))
+    for k in range(p.size - 1, 0, -1):                      # the envelope: every precision at least the ones right of it
+        p[k - 1] = np.maximum(p[k - 1], p[k])
+    steps = np.where(r[1:] != r[:-1])[0]
+    return np.sum((r[steps + 1] - r[steps]) * p[steps + 1])
+
+
+def _overlaps(gt, det):
+    """IoU of one detection with an image's ground-truth boxes [g, 4], pixel-inclusive (+ 1), float64, in voc_eval.py:162-175's order
+    of operations: (detection area + ground-truth areas) - intersections."""
+    w = np.maximum(np.minimum(gt[:, 2], det[2]) - np.maximum(gt[:, 0], det[0]) + 1., 0.)
+    h = np.maximum(np.minimum(gt[:, 3], det[3]) - np.maximum(gt[:, 1], det[1]) + 1., 0.)
+    inter = w * h
+    union = ((det[2] - det[0] + 1.) * (det[3] - det[1] + 1.) + (gt[:, 2] - gt[:, 0] + 1.) * (gt[:, 3] - gt[:, 1] + 1.) - inter)
+    return inter / union
+
+
+def voc_eval(ground_truth, label, det_image_ids, det_confidence, det_boxes, ovthresh=0.5, use_07_metric=False):
+    """voc_eval.py:120-198 for one class.  ground_truth: {image id: (classes int64 [g], difficult bool [g], boxes int64 [g, 4] = the
+    XML's xmin, ymin, xmax, ymax)} over every image of the list; det_*: the class's detections as read back from the results file
+    (`round_trip` applied).  -> (rec, prec, ap).  No detection at all raises IndexError, as the reference's indexing of its empty
+    array does (VOC2007.evaluate turns it into AP 0)."""
+    per_image, npos = {}, 0
+    for image_id, (classes, difficult, boxes) in ground_truth.items():
+        own = np.asarray(classes).reshape(-1) == label
+        hard = np.asarray(difficult).reshape(-1)[own].astype(bool)
+        npos = npos + int(np.sum(~hard))                        # difficult objects are nobody's positive
+        per_image[image_id] = (np.asarray(boxes).reshape(-1, 4)[own].astype(float), hard, [False] * int(own.sum()))
+
+    if len(det_image_ids) == 0:
+        raise IndexError("no detection of this class")
+    confidence = np.array([float(v) for v in det_confidence])
+    order = np.argsort(-confidence)
+    dets = np.array([[float(v) for v in row] for row in det_boxes])[order, :]
+    ids = [det_image_ids[k] for k in order]
+
+    tp, fp = np.zeros(len(ids)), np.zeros(len(ids))
+    for k, image_id in enumerate(ids):
+        gt, hard, claimed = per_image[image_id]
+        best, arg = -np.inf, -1
+        if gt.size > 0:
+            iou = _overlaps(gt, dets[k, :].astype(float))
+            best, arg = np.max(iou), np.argmax(iou)
+        if not best > ovthresh:
+            fp[k] = 1.
+        elif hard[arg]:
+            pass                                                # the best match is a difficult object: neither true nor false
+        elif claimed[arg]:
+            fp[k] = 1.                                          # a duplicate of an object already found
+        else:
+            tp[k] = 1.
+            claimed[arg] = True
+
+    fp, tp = np.cumsum(fp), np.cumsum(tp)
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")                         # npos = 0 (a class without ground truth): the reference divides by zero too
+        rec = tp / float(npos)
+    prec = tp / np.maximum(tp + fp, np.finfo(np.float64).eps)
+    return rec, prec, voc_ap(rec, prec, use_07_metric)
+
+
+def result_line(image_id, prob, bbox):
+    """voc2007.py:157-158"""
+    return '{:s} {:f} {:f} {:f} {:f} {:f}\n'.format(image_id, prob, bbox[0], bbox[1], bbox[2], bbox[3])
+
+
+def write_results(path_to_results_dir, image_ids, bboxes, classes, probs):
+    """voc2007.py:151-161: one `comp3_det_test_{category}.txt` per foreground class."""
+    files = {c: open(os.path.join(path_to_results_dir, 'comp3_det_test_{:s}.txt'.format(LABEL_TO_CATEGORY_DICT[c])), 'w')
+             for c in range(1, NUM_CLASSES)}
+    try:
+        for image_id, bbox, cls, prob in zip(image_ids, bboxes, classes, probs):
+            files[cls].write(result_line(image_id, prob, bbox))
+    finally:
+        for f in files.values():
+            f.close()
+
+
+def evaluate_detail(ground_truth, image_ids, bboxes, classes, probs, path_to_results_dir=None):
+    """VOC2007.evaluate (voc2007.py:118-149) -> (mean_ap, detail, {label: (rec, prec, ap)}); rec and prec are None for a class whose AP
+    is the reference's `except IndexError` 0."""
+    if path_to_results_dir is not None:
+        write_results(path_to_results_dir, image_ids, bboxes, classes, probs)
+    per_class = {c: ([], [], []) for c in range(1, NUM_CLASSES)}
+    for image_id, bbox, cls, prob in zip(image_ids, bboxes, classes, probs):
+        ids, conf, bbs = per_class[cls]
+        ids.append(image_id)
+        conf.append(round_trip(prob))
+        bbs.append([round_trip(bbox[0]), round_trip(bbox[1]), round_trip(bbox[2]), round_trip(bbox[3])])
+    results, class_to_ap_dict = {}, {}
+    for c in range(1, NUM_CLASSES):
+        try:
+            rec, prec, ap = voc_eval(ground_truth, c, *per_class[c], ovthresh=0.5, use_07_metric=True)
+        except IndexError:
+            rec, prec, ap = None, None, 0
+        results[c] = (rec, prec, ap)
+        class_to_ap_dict[c] = ap
+    mean_ap = np.mean([v for k, v in class_to_ap_dict.items()]).item()
+    detail = ''
+    for c in range(1, NUM_CLASSES):
+        detail += '{:d}: {:s} AP = {:.4f}\n'.format(c, LABEL_TO_CATEGORY_DICT[c], class_to_ap_dict[c])
+    return mean_ap, detail, results
+
+
+def evaluate(ground_truth, image_ids, bboxes, classes, probs, path_to_results_dir=None):
+    """VOC2007.evaluate -> (mean_ap, detail)."""
+    mean_ap, detail, _ = evaluate_detail(ground_truth, image_ids, bboxes, classes, probs, path_to_results_dir)
+    return mean_ap, detail
+
+
+# ------------------------------------------------------------------------------------ the evaluator
+class Evaluator:
+    """evaluator.py:12-47.  loader: a det_data.DetDeviceLoader(train=False, batch=1) over the images of `ground_truth` =
+    (image ids, {image id: (classes, difficult, raw boxes)}) in list order.  Per image: the eval-mode forward with the 0.05 bound
+    passed down as min_prob, the boxes divided by the image's scale on the device, and ONE copy to the host of boxes | probs."""
+
+    def __init__(self, loader, ground_truth, results_dir=None):
+        if loader.train or loader.batch != 1:
+            raise ValueError("do not use batch size more than 1 on evaluation: the loader is DetDeviceLoader(train=False, batch=1)")
+        self.loader = loader
+        self.image_ids, self.ground_truth = ground_truth
+        if len(self.image_ids) != loader.n:
+            raise ValueError("the ground truth names one image per image of the loader")
+        self.results_dir = results_dir
+
+    def detect(self, model):
+        """-> (image ids, boxes, classes, probs) as the lists evaluator.py:41-44 builds."""
+        import torch
+        all_image_ids, all_bboxes, all_classes, all_probs = [], [], [], []
+        with torch.no_grad():
+            for image_id, (image_batch, _, _, scale_batch) in zip(self.image_ids, self.loader):
+                inputs_all = {"x": image_batch, "adv": None, "out_idx": None, "flag": 'clean', "min_prob": MIN_PROB}
+                bboxes, classes, probs, batch_indices = model.eval().forward(inputs_all)
+                bboxes = bboxes / scale_batch[batch_indices.to(scale_batch.device)].unsqueeze(dim=-1).expand_as(bboxes)
+                host = torch.cat([bboxes, probs.unsqueeze(dim=-1).to(bboxes.dtype)], dim=1).cpu()       # the image's one copy
+                classes = classes.cpu()
+                keep = (host[:, 4] > MIN_PROB).nonzero().view(-1)       # evaluator.py:35 (nothing left to drop where the model took min_prob)
+                host, classes = host[keep], classes[keep]
+                all_bboxes.extend(host[:, :4].tolist())
+                all_probs.extend(host[:, 4].tolist())
+                all_classes.extend(classes.tolist())
+                all_image_ids.extend([image_id] * host.shape[0])
+        return all_image_ids, all_bboxes, all_classes, all_probs
+
+    def evaluate(self, model):
+        return evaluate(self.ground_truth, *self.detect(model), path_to_results_dir=self.results_dir)
+
+
+# ------------------------------------------------------------------------------------ the driver of eval.py
+def get_argparser():
+    """eval.py:42-54, flag for flag."""
+    from . import det_entry
+    d = eval_defaults()
+    parser = argparse.ArgumentParser()
+    parser.add_argument('-s', '--dataset', type=str, choices=det_entry.DATASET_OPTIONS, required=True, help='name of dataset')
+    parser.add_argument('-b', '--backbone', type=str, choices=det_entry.BACKBONE_OPTIONS, required=True, help='name of backbone model')
+    parser.add_argument('-d', '--data_dir', type=str, default='./data', help='path to data directory')
+
+    parser.add_argument('--image_min_side', type=float, help='default: {:g}'.format(d["image_min_side"]))
+    parser.add_argument('--image_max_side', type=float, help='default: {:g}'.format(d["image_max_side"]))
+    parser.add_argument('--anchor_ratios', type=str, help='default: "{!s}"'.format(d["anchor_ratios"]))
+    parser.add_argument('--anchor_sizes', type=str, help='default: "{!s}"'.format(d["anchor_sizes"]))
+    parser.add_argument('--pooler_mode', type=str, choices=det_entry.POOLER_OPTIONS, help='default: {:s}'.format(d["pooler_mode"]))
+    parser.add_argument('--rpn_pre_nms_top_n', type=int, help='default: {:d}'.format(d["rpn_pre_nms_top_n"]))
+    parser.add_argument('--rpn_post_nms_top_n', type=int, help='default: {:d}'.format(d["rpn_post_nms_top_n"]))
+    parser.add_argument('checkpoint', type=str, help='path to evaluating checkpoint')
+    return parser
+
+
+ADDITIONS = ("synthetic", "dtype", "layout")
+_EVAL_KEYS = ("image_min_side", "image_max_side", "anchor_ratios", "anchor_sizes", "pooler_mode", "rpn_pre_nms_top_n", "rpn_post_nms_top_n")
+
+
+def eval_defaults():
+    """config/config.py:9-14 with config/eval_config.py:8-9 on top."""
+    from . import det_entry
+    d = {k: det_entry.DEFAULTS[k] for k in _EVAL_KEYS}
+    d.update(rpn_pre_nms_top_n=6000, rpn_post_nms_top_n=300)
+    return d
+
+
+def get_full_argparser():
+    parser = get_argparser()
+    parser.add_argument("--synthetic", type=int, default=0, help="evaluate on N synthetic images with boxes instead of VOC's test list")
+    parser.add_argument("--dtype", default="bf16", choices=["bf16", "fp32"], help="backbone compute dtype")
+    parser.add_argument("--layout", default="nhwc", choices=["nhwc", "nchw"], help="internal activation / weight layout")
+    return parser
+
+
+def config(args):
+    """EvalConfig.setup (config/eval_config.py:11-20): the defaults, each replaced by its flag where one was given."""
+    import ast
+    cfg = eval_defaults()
+    for k in cfg:
+        v = getattr(args, k, None)
+        if v is not None:
+            cfg[k] = ast.literal_eval(v) if k in ("anchor_ratios", "anchor_sizes") else v
+    return cfg
+
+
+def check_unbuilt(args):
+    """det_entry.check_unbuilt's refusals (the evaluation has no loss setting)."""
+    from . import det_entry
+    det_entry.check_unbuilt(argparse.Namespace(backbone=args.backbone, dataset=args.dataset, loss_settings=1))
+
+
+def results_dir(path_to_checkpoint):
+    """eval.py:62-64"""
+    return os.path.join(os.path.dirname(path_to_checkpoint), 'results-{:s}-{:s}-{:s}'.format(
+        time.strftime('%Y%m%d%H%M%S'), path_to_checkpoint.split(os.path.sep)[-1].split(os.path.curdir)[0],
+        str(uuid.uuid4()).split('-')[0]))
+
+
+def build_eval_split(args, cfg):
+    """-> (images, boxes for the loader, classes for the loader, (image ids, ground truth), num_classes)."""
+    from . import det_data
+    if args.synthetic:
+        hi = max(int(cfg["image_max_side"] * 0.5), 8)
+        lo = max(min(int(cfg["image_min_side"] * 0.625), hi - 1), 7)
+        s = det_data.SyntheticDetSplit(args.synthetic, seed=0, min_side=lo, max_side=hi)
+        return s.images, s.boxes, s.classes, (s.image_ids, s.ground_truth()), s.num_classes
+    images, boxes, classes, image_ids, ground_truth = det_data.load_voc_det_eval(args.data_dir, args.dataset)
+    return images, boxes, classes, (image_ids, ground_truth), NUM_CLASSES
+
+
+def main(program, argv=None):
+    from . import det_data, det_entry
+    args = get_full_argparser().parse_args(argv)
+    check_unbuilt(args)
+    cfg = config(args)
+    device = det_entry.setup_device(program)
+
+    path_to_checkpoint = args.checkpoint
+    path_to_results_dir = results_dir(path_to_checkpoint)
+    os.makedirs(path_to_results_dir)
+    log = det_entry.Log(os.path.join(path_to_results_dir, 'eval.log'))
+    log.i('Arguments:')
+    for k, v in vars(args).items():
+        log.i(f'\t{k} = {v}')
+    log.i(det_entry.describe(cfg))
+
+    images, boxes, classes, ground_truth, num_classes = build_eval_split(args, cfg)
+    loader = det_data.DetDeviceLoader(images, boxes, classes, 1, device, False, cfg["image_min_side"], cfg["image_max_side"])
+    evaluator = Evaluator(loader, ground_truth, path_to_results_dir)
+    log.i('Found {:d} samples'.format(len(images)))
+
+    model_cfg = dict(det_entry.DEFAULTS)
+    model_cfg.update(cfg)
+    model = det_entry.build_model(args, model_cfg, num_classes).to(device)
+    det_entry.load_checkpoint(path_to_checkpoint, model)
+
+    log.i('Start evaluating with 1 GPU (1 batch per GPU)')
+    mean_ap, detail = evaluator.evaluate(model)
+    log.i('Done')
+    print("-" * 36)
+    print("[{}]".format(path_to_checkpoint))
+    log.i('mean AP = {:.4f}'.format(mean_ap))
+    print("-" * 36)
+    log.i('\n' + detail)
+    return mean_ap, detail

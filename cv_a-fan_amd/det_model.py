@@ -24,8 +24,8 @@ import torch.nn.functional as F
 
 from . import ops
 from .deeplab import MaxPool2d, StemConv, _MaxPoolFn, _enter
-from .det_ops import (box_assign, box_decode_clip, fg_bg_draw, fg_bg_sample, labels_limit_, nms, per_image_losses, proposal_rows,
-                      roi_align, sample_lists)
+from .det_ops import (box_assign, box_decode_clip, class_nms, class_nms_supported, fg_bg_draw, fg_bg_sample, labels_limit_, nms,
+                      per_image_losses, proposal_rows, roi_align, sample_lists)
 from .resnet_s import (Conv2d, NormalizeByChannelMeanStd, _accumulates_in_place, _ConvFn, _dense, _Flags, _FrozenBlockFn, _like_layout, _linear,
                        dgrad_only, _own_conv_ok, _to_compute, _WgradStream)
 
@@ -1021,7 +1021,8 @@ class Model(nn.Module):
             obj, tr = self.rpn.forward(features)
             proposals = self.rpn.generate_proposals(anchors, obj, tr, iw, ih)
             classes, transformers = self.detection.forward(features, proposals)
-            return self.detection.generate_detections(proposals, classes, transformers, iw, ih)
+            # "min_prob" in the dict (det_eval.Evaluator: 0.05) filters inside the detection tail; absent, every survivor is returned
+            return self.detection.generate_detections(proposals, classes, transformers, iw, ih, min_prob=input_dict.get("min_prob"))
         idx = input_dict["out_idx"]
         if idx == "roi_tail":
             d = input_dict["adv"]
@@ -1081,6 +1082,8 @@ class Model(nn.Module):
         return self.detection.forward_many(pend)
 
     MERGE_READS = os.environ.get("AFAN_DET_MERGE_READS", "1") != "0"       # 0: the ROI head's sampling with its own host read (A/B, tests)
+
+    CLASS_NMS = os.environ.get("AFAN_DET_CLASS_NMS", "1") != "0"           # 0: the inference tail as the per-class loop (A/B, tests)
 
     def _roi_targets(self, gt_classes_batch, gt_bboxes_batch):
         if not Model.MERGE_READS:
@@ -1174,9 +1177,25 @@ class Model(nn.Module):
             return per_image_losses(proposal_classes, proposal_transformers, None, gt_proposal_classes, gt_proposal_transformers,
                                     batch_indices, batch_size, self._proposal_smooth_l1_loss_beta, norm=norm)
 
-        def generate_detections(self, proposal_bboxes, proposal_classes, proposal_transformers, image_width, image_height):
-            """:369-407 (inference): per-class decode, clip, softmax, NMS at 0.3."""
+        def generate_detections(self, proposal_bboxes, proposal_classes, proposal_transformers, image_width, image_height, min_prob=None):
+            """:369-407 (inference): per-class decode, clip, softmax, NMS at 0.3 -> (boxes [T, 4], classes [T] int, probs [T], image
+            indices [T] long), ordered by image, class, proposal.  min_prob: only detections with prob > min_prob (evaluator.py:35; greedy
+            NMS visits boxes in descending score, so a box at or below the bound suppresses only boxes at or below it: filtering before
+            equals filtering after).  Lists det_ops.class_nms takes go through it — softmax, two launches, one host read of the
+            counts — unless AFAN_DET_CLASS_NMS=0; the per-class loop below is the fallback for larger lists, and the yardstick."""
             b = proposal_bboxes.shape[0]
+            n = proposal_bboxes.shape[1]
+            if (Model.CLASS_NMS and proposal_bboxes.is_cuda and b > 0 and class_nms_supported(n, self.num_classes)):
+                probs = F.softmax(proposal_classes.float(), dim=-1)
+                norm = tuple(self._transformer_normalize_mean.tolist()) + tuple(self._transformer_normalize_std.tolist())
+                fb, fp, counts = class_nms(proposal_bboxes, proposal_transformers.float().reshape(b, n, self.num_classes, 4), probs, norm,
+                                           image_width, image_height, 0.3, min_prob)
+                counts = counts.cpu().view(-1)                              # the forward's one host read
+                total = int(counts.sum())
+                lists = torch.arange(b * (self.num_classes - 1))
+                cls = (lists % (self.num_classes - 1) + 1).to(torch.int)
+                img = lists // (self.num_classes - 1)
+                return fb[:total], torch.repeat_interleave(cls, counts), fp[:total], torch.repeat_interleave(img, counts)
             tr = proposal_transformers.view(b, -1, self.num_classes, 4)
             tr = tr * self._transformer_normalize_std.to(tr.device) + self._transformer_normalize_mean.to(tr.device)
             boxes = box_clip_(box_apply(proposal_bboxes.unsqueeze(dim=2).repeat(1, 1, self.num_classes, 1), tr), image_width, image_height)
@@ -1190,7 +1209,12 @@ class Model(nn.Module):
                     out_c.append(torch.full((len(keep),), c, dtype=torch.int))
                     out_p.append(cp[keep])
                     out_i.append(torch.full((len(keep),), bi, dtype=torch.long))
-            return torch.cat(out_b, dim=0), torch.cat(out_c, dim=0), torch.cat(out_p, dim=0), torch.cat(out_i, dim=0)
+            out = torch.cat(out_b, dim=0), torch.cat(out_c, dim=0), torch.cat(out_p, dim=0), torch.cat(out_i, dim=0)
+            if min_prob is None or min_prob < 0:
+                return out
+            kept = (out[2] > min_prob).nonzero().view(-1)               # evaluator.py:35-39
+            kept_host = kept.cpu()
+            return out[0][kept], out[1][kept_host], out[2][kept], out[3][kept_host]
 
 
 def fasterrcnn_resnet101(num_classes=21, pooler_mode="align", **kw):

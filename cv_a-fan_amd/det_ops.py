@@ -103,6 +103,43 @@ def box_decode_clip(src, transformers, right, bottom):
     return out
 
 
+def class_nms_supported(n, c):
+    """Whether class_nms takes lists of n proposals over c classes (afan_det_class_nms_supported; no GPU touched)."""
+    return bool(_lib.load().afan_det_class_nms_supported(int(n), int(c)))
+
+
+def class_nms(proposals, transformers, probs, norm, right, bottom, threshold, min_prob=None):
+    """The inference tail of model.py:369-407 for all (image, foreground class) lists in one launch (afan_det_class_nms) and one that
+    packs them (afan_det_pack): proposals [B, N, 4], transformers [B, N, C, 4] (the head's raw output), probs [B, N, C] (after the
+    softmax), norm = mean[4] + std[4].  Per list: clip(apply_transformer(proposals, transformers * std + mean)), the rows with
+    prob > min_prob (None: all), greedy NMS at IoU > threshold in descending probability.  Returns (boxes [T, 4], probs [T], counts
+    [B, C - 1] int64), all on the device: the survivors ordered by image, class, proposal index, of which the FIRST counts.sum() rows
+    are the result (T = B * (C - 1) * N is its upper bound: the caller reads the counts once and slices)."""
+    proposals, transformers, probs = _f32c(proposals, "class_nms"), _f32c(transformers, "class_nms"), _f32c(probs, "class_nms")
+    if proposals.dim() != 3 or proposals.shape[-1] != 4:
+        raise ValueError("class_nms: proposals [B, N, 4]")
+    B, N, _ = proposals.shape
+    if probs.dim() != 3 or probs.shape[:2] != (B, N):
+        raise ValueError("class_nms: probs [B, N, C]")
+    Cc = probs.shape[2]
+    if transformers.numel() != B * N * Cc * 4:
+        raise ValueError("class_nms: transformers [B, N, C, 4]")
+    if len(norm) != 8:
+        raise ValueError("class_nms: norm = mean[4] + std[4]")
+    lib, dev = _lib.load(), proposals.device
+    L = B * (Cc - 1)
+    lists_b = torch.empty((L * N, 4), dtype=torch.float32, device=dev)
+    lists_p = torch.empty(L * N, dtype=torch.float32, device=dev)
+    counts = torch.empty((B, Cc - 1), dtype=torch.int64, device=dev)
+    flat_b, flat_p = torch.empty_like(lists_b), torch.empty_like(lists_p)
+    nrm = (C.c_float * 8)(*[float(v) for v in norm])
+    check(lib.afan_det_class_nms(_ptr(proposals), _ptr(transformers), _ptr(probs), nrm, B, N, Cc, float(right), float(bottom), float(threshold),
+                                 -1.0 if min_prob is None else float(min_prob), _ptr(lists_b), _ptr(lists_p), _ptr(counts), _stream(dev)),
+          "afan_det_class_nms")
+    check(lib.afan_det_pack(_ptr(lists_b), _ptr(lists_p), _ptr(counts), L, N, _ptr(flat_b), _ptr(flat_p), _stream(dev)), "afan_det_pack")
+    return flat_b, flat_p, counts
+
+
 def box_assign(boxes, gt_bboxes, mode, lo, hi=0.0, gt_classes=None):
     """(labels [B, N] int64, assign [B, N] int64) of boxes [B, N, 4] against gt [B, G, 4]: mode 'anchor'
     (region_proposal_network.py:66-82, thresholds lo / hi) or 'proposal' (model.py:256-264, threshold lo, classes [B, G])."""

@@ -8,7 +8,8 @@ instead of eight DataLoader workers, the learning rate is WarmUpMultiStepLR's cl
 loss stays on the device until a `[Step s] Avg. Loss = ...` line needs it.
 
 Not built here: backbones other than resnet101 and datasets other than voc2007 / voc20072012 (they raise, each with its reason);
-tensorboardX summaries (not installed: none are written); ImageNet weights (no download: see det_entry.build_model); evaluation."""
+tensorboardX summaries (not installed: none are written); ImageNet weights (no download: see det_entry.build_model).  Evaluation is
+eval.py."""
 import os
 import sys
 

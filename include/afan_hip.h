@@ -724,6 +724,20 @@ int afan_labels_limit(int64_t* labels, int64_t B, int64_t N, const int64_t* kept
 int afan_det_loss_bwd(const float* g_ce, const float* g_sl1, const float* save, const int64_t* rows, const int64_t* gt_labels,
                       const int64_t* batch, int64_t S, int64_t B, int64_t C, int64_t K, int64_t R, float* d_logits, float* d_deltas,
                       afan_stream_t stream);
+/* afan_det_class_nms — the inference tail `generate_detections` (Detection/model.py:369-407) for every (image, foreground class)
+ * list in ONE launch, one workgroup per list, all in LDS: boxes = clip(apply_transformer(proposals, transformers * std + mean))
+ * (afan_box_decode_clip's arithmetic), rows with probs > min_prob (min_prob < 0: all rows) in descending probability, ties by
+ * ascending row, greedy NMS at IoU > nms_threshold (afan_nms's decision, inclusive = 0).  proposals [B,N,4], transformers
+ * [B,N,C,4] as the head gives them, probs [B,N,C] after the softmax, norm: HOST mean[4], std[4].  Output per list l = b * (C-1) +
+ * c - 1: counts[l] survivors, their boxes out_boxes [B,C-1,N,4] and probabilities out_probs [B,C-1,N] in ascending row order
+ * (rows >= counts[l] are not written).  afan_det_class_nms_supported: 1 for 1 <= N <= 2048 and 2 <= C <= 64, else 0.
+ * afan_det_pack — L lists [L,N,...] with counts [L] -> their rows back to back: flat_boxes [>= sum, 4], flat_probs [>= sum]. */
+int afan_det_class_nms_supported(int64_t N, int64_t C);
+int afan_det_class_nms(const float* proposals, const float* transformers, const float* probs, const float* norm, int64_t B, int64_t N,
+                       int64_t C, float right, float bottom, float nms_threshold, float min_prob, float* out_boxes, float* out_probs,
+                       int64_t* counts, afan_stream_t stream);
+int afan_det_pack(const float* boxes, const float* probs, const int64_t* counts, int64_t L, int64_t N, float* flat_boxes,
+                  float* flat_probs, afan_stream_t stream);
 /* afan_roi_align_{fwd,bwd} — `support._C.roi_align_forward / roi_align_backward` (ROIAlign.h:12-47 -> ROIAlign_cuda.cu:256-346).
  * x [N,C,H,W], rois [num_rois,5] fp32 = (batch index, x1, y1, x2, y2) in image coordinates (scaled by spatial_scale, NOT
  * rounded), y [num_rois,C,PH,PW]; sampling_ratio <= 0: ceil(roi extent / pooled extent) sample points per bin and axis.
