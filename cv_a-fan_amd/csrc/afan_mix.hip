@@ -554,7 +554,6 @@ int afan_lerp_mix(const float* clean, const float* adv, float* out, int64_t n, i
             stage = pix >= 8;
             if (!stage) pix = 64;
         }
-        if (stage && bytes(pix, true) > (size_t)156 * 1024) stage = false;     // (same tile, clean re-read instead of staged)
         while (pix > 8 && pix / 2 >= hw) pix >>= 1;
         const int tiles = (int)((hw + pix - 1) / pix);
         const int64_t blocks = n * tiles;
