@@ -54,16 +54,12 @@ SIGNATURES = {
     "afan_bn_backward": (_i, [_p, _p, _p, _p, _p, _i, _i, _l, _l, _l, _p, _p, _p, _i, _p, _p, _p, _i, _p, _l, _p]),
     "afan_conv_supported": (_i, [_l, _l, _i, _i]),
     "afan_conv_fwd_nhwc_bf16": (_i, [_p, _p, _p, _l, _l, _l, _l, _l, _i, _i, _i, _p, _p, _p, _i, _p]),
-    "afan_conv_fwd_affine_nhwc_bf16": (_i, [_p, _p, _p, _l, _l, _l, _l, _l, _i, _i, _p, _p, _i, _p]),
-    "afan_conv_fwd_affine_any_nhwc_bf16": (_i, [_p, _p, _p, _l, _l, _l, _l, _l, _i, _i, _p, _p, _i, _p]),
-    "afan_conv_fwd_affine_dil_nhwc_bf16": (_i, [_p, _p, _p, _l, _l, _l, _l, _l, _i, _i, _i, _p, _p, _i, _p]),
+    "afan_conv_fwd_affine_nhwc_bf16": (_i, [_p, _p, _p, _l, _l, _l, _l, _l, _i, _i, _i, _p, _p, _i, _i, _p]),
     "afan_conv_fwd_multi_nhwc_bf16": (_i, [_p, _p, _p, _i, _l, _l, _l, _l, _l, _p, _i, _p, _p, _p, _i, _p]),
     "afan_conv_fwd_tiles": (_l, [_l, _l, _l, _l, _l, _i, _i]),
     "afan_bn_train_forward_partials": (_i, [_p, _p, _p, _i, _l, _l, _l, _f, _f, _p, _p, _i, _p, _l, _p, _p, _p, _p, _p, _p]),
     "afan_conv_dgrad_nhwc_bf16": (_i, [_p, _p, _p, _l, _l, _l, _l, _l, _i, _i, _i, _p, _p, _p, _i, _p, _p, _p, _i, _p]),
-    "afan_conv_dgrad_affine_nhwc_bf16": (_i, [_p, _p, _p, _l, _l, _l, _l, _l, _i, _i, _p, _p, _p]),
-    "afan_conv_dgrad_affine_any_nhwc_bf16": (_i, [_p, _p, _p, _l, _l, _l, _l, _l, _i, _i, _p, _p, _p]),
-    "afan_conv_dgrad_affine_dil_nhwc_bf16": (_i, [_p, _p, _p, _l, _l, _l, _l, _l, _i, _i, _i, _p, _p, _p]),
+    "afan_conv_dgrad_affine_nhwc_bf16": (_i, [_p, _p, _p, _l, _l, _l, _l, _l, _i, _i, _i, _p, _p, _i, _p]),
     "afan_conv_dgrad_dual_nhwc_bf16": (_i, [_p, _p, _p, _p, _l, _l, _l, _l, _l, _i, _i, _p, _p, _p, _p]),
     "afan_conv_dgrad_sc_nhwc_bf16": (_i, [_p, _p, _p, _p, _l, _l, _l, _l, _l, _p, _p, _i, _p, _p, _p, _p]),
     "afan_grid_barrier_bytes": (_i, []),
@@ -110,14 +106,9 @@ SIGNATURES = {
     "afan_maxpool2d_bwd": (_i, [_p, _p, _p, _p, _i, _i, _l, _l, _l, _l, _i, _i, _i, _p]),
     "afan_affine_relu_bwd": (_i, [_p, _p, _p, _p, _p, _i, _i, _l, _l, _l, _i, _p]),
     "afan_affine_coefs": (_i, [_p, _p, _p, _p, _l, _p, _p]),
-    "afan_frozen_bottleneck_fwd": (_i, [_p, _l, _l, _l, _l, _l, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
+    "afan_frozen_bottleneck_fwd": (_i, [_p, _l, _l, _l, _l, _l, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
     "afan_frozen_bottleneck_bwd_scratch": (_l, [_l, _l, _l, _l, _l, _i]),
-    "afan_frozen_bottleneck_bwd": (_i, [_p, _p, _p, _p, _p, _l, _l, _l, _l, _l, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p,
-                                        _p, _p]),
-    "afan_frozen_bottleneck_bwd_chain": (_i, [_p, _p, _p, _p, _p, _p, _p, _l, _l, _l, _l, _l, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p,
-                                              _p, _p, _p, _p, _p, _p]),
-    "afan_frozen_bottleneck_fwd_dil": (_i, [_p, _l, _l, _l, _l, _l, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
-    "afan_frozen_bottleneck_bwd_chain_dil": (_i, [_p, _p, _p, _p, _p, _p, _p, _l, _l, _l, _l, _l, _i, _i] + [_p] * 19),
+    "afan_frozen_bottleneck_bwd": (_i, [_p, _p, _p, _p, _p, _p, _p, _l, _l, _l, _l, _l, _i, _i] + [_p] * 19),
     "afan_affine_apply": (_i, [_p, _p, _p, _i, _l, _l, _l, _p, _i, _p]),
     "afan_avgpool_fwd": (_i, [_p, _p, _i, _i, _l, _l, _l, _i, _p]),
     "afan_avgpool_bwd": (_i, [_p, _p, _i, _i, _l, _l, _l, _i, _p]),

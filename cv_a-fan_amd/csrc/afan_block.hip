@@ -22,20 +22,12 @@ extern "C" {
 // w1 [planes, cin, 1, 1], w2 [planes, planes, 3, 3], w3 [4 planes, planes, 1, 1], wd [4 planes, cin, 1, 1] or NULL (identity
 // shortcut: cin == 4 planes, stride 1) — KRSC bf16; k1 .. kd: afan_affine_coefs blocks.  a1 [n, planes, h, w] and
 // a2 [n, planes, ho, wo] are kept for the backward; scratch: bf16 elements for the raw convolution outputs,
-// n * (planes * h * w + 2 * 4 planes * ho * wo) of them.
-int afan_frozen_bottleneck_fwd(const void* x, int64_t n, int64_t h, int64_t w, int64_t cin, int64_t planes, int stride,
+// n * (planes * h * w + 2 * 4 planes * ho * wo) of them.  dilation: of the 3x3 convolution (padding = dilation; dilation > 1:
+// stride 1 — the atrous bottlenecks of Segmentation/network/backbone/resnet.py:29-32 in eval mode).
+int afan_frozen_bottleneck_fwd(const void* x, int64_t n, int64_t h, int64_t w, int64_t cin, int64_t planes, int stride, int dilation,
                                const void* w1, const void* w2, const void* w3, const void* wd, const float* k1, const float* k2,
                                const float* k3, const float* kd, void* scratch, void* a1, void* a2, void* out,
                                afan_stream_t stream) {
-    return afan_frozen_bottleneck_fwd_dil(x, n, h, w, cin, planes, stride, 1, w1, w2, w3, wd, k1, k2, k3, kd, scratch, a1, a2, out, stream);
-}
-
-// The same with the dilation of the 3x3 convolution (padding = dilation; dilation > 1: stride 1 — the atrous bottlenecks of
-// Segmentation/network/backbone/resnet.py:29-32 in eval mode).  Dilation 1 issues exactly the launches it always did.
-int afan_frozen_bottleneck_fwd_dil(const void* x, int64_t n, int64_t h, int64_t w, int64_t cin, int64_t planes, int stride, int dilation,
-                                   const void* w1, const void* w2, const void* w3, const void* wd, const float* k1, const float* k2,
-                                   const float* k3, const float* kd, void* scratch, void* a1, void* a2, void* out,
-                                   afan_stream_t stream) {
     if (!x || !w1 || !w2 || !w3 || !k1 || !k2 || !k3 || !scratch || !a1 || !a2 || !out) return AFAN_ENULL;
     if (wd && !kd) return AFAN_ENULL;
     if (n <= 0 || h <= 0 || w <= 0 || cin <= 0 || planes <= 0 || !(stride == 1 || stride == 2)) return AFAN_ESHAPE;
@@ -47,12 +39,11 @@ int afan_frozen_bottleneck_fwd_dil(const void* x, int64_t n, int64_t h, int64_t 
     uint16_t* rd = r3 + n * co * ho * wo;                    // [n, co, ho, wo]: the projection branch, raw then normalised in place
     int e;
     // a convolution and its frozen BatchNorm (+ residual) (+ ReLU) as ONE launch where the tiled kernel takes the shape
-    // (afan_conv_fwd_affine_nhwc_bf16: the same bits), else the two launches
+    // (afan_conv_fwd_affine_nhwc_bf16: the same bits; at dilation 1 the other kernel families keep their two launches), else the two launches
     auto conv_bn = [&](const void* in, const void* wt, void* raw, void* dst, int64_t hi_, int64_t wi_, int64_t ci_, int64_t co_, int k, int st_,
                        const float* kc, const void* res, int relu, int dil = 1) -> int {
         int rc = !fuse_affine() ? AFAN_ESHAPE
-                 : dil > 1 ? afan_conv_fwd_affine_dil_nhwc_bf16(in, wt, dst, n, hi_, wi_, ci_, co_, k, st_, dil, kc, res, relu, stream)
-                           : afan_conv_fwd_affine_nhwc_bf16(in, wt, dst, n, hi_, wi_, ci_, co_, k, st_, kc, res, relu, stream);
+                                : afan_conv_fwd_affine_nhwc_bf16(in, wt, dst, n, hi_, wi_, ci_, co_, k, st_, dil, kc, res, relu, dil > 1, stream);
         if (rc != AFAN_ESHAPE) return rc;
         if ((rc = afan_conv_fwd_nhwc_bf16(in, wt, raw, n, hi_, wi_, ci_, co_, k, st_, dil, nullptr, nullptr, nullptr, 1, stream))) return rc;
         const int64_t ho_ = (hi_ - 1) / st_ + 1, wo_ = (wi_ - 1) / st_ + 1;
@@ -80,39 +71,21 @@ int64_t afan_frozen_bottleneck_bwd_scratch(int64_t n, int64_t h, int64_t w, int6
 // gw1 .. gwd: fp32 KRSC gradient tensors the weight gradients are ADDED into (NULL: that layer's weight gradient is not
 // wanted — frozen layers, input-gradient-only passes); wgrad_ws: the sum of the wanted layers'
 // afan_conv_wgrad_workspace_floats; dx (nullable) [n, cin, h, w].
-int afan_frozen_bottleneck_bwd(const void* g, const void* x, const void* a1, const void* a2, const void* out, int64_t n,
-                               int64_t h, int64_t w, int64_t cin, int64_t planes, int stride, const void* wt1, const void* wt2,
-                               const void* wt3, const void* wtd, const float* al1, const float* al2, const float* al3,
-                               const float* ald, float* gw1, float* gw2, float* gw3, float* gwd, float* wgrad_ws, void* scratch,
-                               void* dx, afan_stream_t stream) {
-    return afan_frozen_bottleneck_bwd_chain(g, nullptr, nullptr, x, a1, a2, out, n, h, w, cin, planes, stride, wt1, wt2, wt3, wtd, al1, al2, al3,
-                                            ald, gw1, gw2, gw3, gwd, wgrad_ws, scratch, dx, nullptr, nullptr, nullptr, stream);
-}
-
-// The same inside a chain of blocks (a stage: block i + 1's input IS block i's output).  Entering: g as above, or — g NULL — the
+// Alone or inside a chain of blocks (a stage: block i + 1's input IS block i's output).  Entering: g as above, or — g NULL — the
 // first step of this block's backward already done by the block behind it: pre_d3 = bf16(m * al3), pre_dres = m with m = the
 // output's ReLU mask applied to the gradient (pre_dres may be overwritten).  Leaving: dx as above, or — dx NULL, prev_al3 given —
 // that first step of the block IN FRONT done here, in the epilogue of this block's last input-gradient launch
 // (afan_conv_dgrad_dual_nhwc_bf16; where that kernel does not take the shape: the gradient into prev_dres, then the separate
 // launch): prev_d3 / prev_dres [n, cin, h, w] with prev_al3 = the block in front's last alpha row, its stored output = x.
 // One launch per block and pass less (the Detection iteration: ~410 of 4 800).  Same bits either way.
-int afan_frozen_bottleneck_bwd_chain(const void* g, void* pre_d3, void* pre_dres, const void* x, const void* a1, const void* a2,
-                                     const void* out, int64_t n, int64_t h, int64_t w, int64_t cin, int64_t planes, int stride,
-                                     const void* wt1, const void* wt2, const void* wt3, const void* wtd, const float* al1, const float* al2,
-                                     const float* al3, const float* ald, float* gw1, float* gw2, float* gw3, float* gwd, float* wgrad_ws,
-                                     void* scratch, void* dx, const float* prev_al3, void* prev_d3, void* prev_dres, afan_stream_t stream) {
-    return afan_frozen_bottleneck_bwd_chain_dil(g, pre_d3, pre_dres, x, a1, a2, out, n, h, w, cin, planes, stride, 1, wt1, wt2, wt3, wtd, al1, al2,
-                                                al3, ald, gw1, gw2, gw3, gwd, wgrad_ws, scratch, dx, prev_al3, prev_d3, prev_dres, stream);
-}
-
-// The same with the dilation of the 3x3 convolution (see afan_frozen_bottleneck_fwd_dil).  Dilation 1 issues exactly the launches it
-// always did; the weight gradients, where asked for, take the dilation too (one by one: the multi launch's plan knows dilation 1).
-int afan_frozen_bottleneck_bwd_chain_dil(const void* g, void* pre_d3, void* pre_dres, const void* x, const void* a1, const void* a2,
-                                         const void* out, int64_t n, int64_t h, int64_t w, int64_t cin, int64_t planes, int stride,
-                                         int dilation, const void* wt1, const void* wt2, const void* wt3, const void* wtd,
-                                         const float* al1, const float* al2, const float* al3, const float* ald, float* gw1, float* gw2,
-                                         float* gw3, float* gwd, float* wgrad_ws, void* scratch, void* dx, const float* prev_al3,
-                                         void* prev_d3, void* prev_dres, afan_stream_t stream) {
+// dilation: of the 3x3 convolution (see afan_frozen_bottleneck_fwd); the weight gradients, where asked for, take it too (one by
+// one: the multi launch's plan knows dilation 1).
+int afan_frozen_bottleneck_bwd(const void* g, void* pre_d3, void* pre_dres, const void* x, const void* a1, const void* a2,
+                               const void* out, int64_t n, int64_t h, int64_t w, int64_t cin, int64_t planes, int stride,
+                               int dilation, const void* wt1, const void* wt2, const void* wt3, const void* wtd,
+                               const float* al1, const float* al2, const float* al3, const float* ald, float* gw1, float* gw2,
+                               float* gw3, float* gwd, float* wgrad_ws, void* scratch, void* dx, const float* prev_al3,
+                               void* prev_d3, void* prev_dres, afan_stream_t stream) {
     if (!x || !a1 || !a2 || !out || !wt1 || !wt2 || !wt3 || !al1 || !al2 || !al3 || !scratch) return AFAN_ENULL;
     if (!g && (!pre_d3 || !pre_dres)) return AFAN_ENULL;
     if (prev_al3 && (dx || !prev_d3 || !prev_dres)) return AFAN_ENULL;
@@ -137,8 +110,7 @@ int afan_frozen_bottleneck_bwd_chain_dil(const void* g, void* pre_d3, void* pre_
     auto dgrad_bn = [&](const void* dyp, const void* wt, void* raw, void* dst, int64_t hi_, int64_t wi_, int64_t ci_, int64_t co_, int k, int st_,
                         const float* al, const void* act, int dil = 1) -> int {
         int rc = !fuse_affine() ? AFAN_ESHAPE
-                 : dil > 1 ? afan_conv_dgrad_affine_dil_nhwc_bf16(dyp, wt, dst, n, hi_, wi_, ci_, co_, k, st_, dil, al, act, stream)
-                           : afan_conv_dgrad_affine_nhwc_bf16(dyp, wt, dst, n, hi_, wi_, ci_, co_, k, st_, al, act, stream);
+                                : afan_conv_dgrad_affine_nhwc_bf16(dyp, wt, dst, n, hi_, wi_, ci_, co_, k, st_, dil, al, act, dil > 1, stream);
         if (rc != AFAN_ESHAPE) return rc;
         if ((rc = afan_conv_dgrad_nhwc_bf16(dyp, wt, raw, n, hi_, wi_, ci_, co_, k, st_, dil, nullptr, nullptr, nullptr, 0, nullptr, nullptr,
                                             nullptr, 1, stream))) return rc;

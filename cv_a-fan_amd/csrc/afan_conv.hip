@@ -1646,11 +1646,101 @@ int check_dims(int64_t n, int64_t hi, int64_t wi, int64_t ci, int64_t co, int k,
     return AFAN_OK;
 }
 
-static int dgrad_impl(const void* dy, const void* dy_sc, const void* wt, void* dx, int64_t n, int64_t hi, int64_t wi,
-                      int64_t ci, int64_t co, int k, int stride, int dilation, const void* addend, const void* bn_x,
-                      const float* bn_stats, int bn_relu, const void* bn_y, float* bn_partials, double* bn_acc, int groups,
-                      afan_stream_t stream, const float* aff_alpha = nullptr, const void* aff_act = nullptr, void* dx2 = nullptr,
-                      const ConvP* bnf = nullptr, bool any_family = false) {
+static int conv_out(int64_t in, int k, int stride) { return (int)((in + 2 * (k / 2) - k) / stride + 1); }
+
+// ---- forward problems: one builder, one family choice -----------------------------------------------------------------------------
+// the taps of one dense forward problem: tap (r, s) reads the input pixel (r - pad, s - pad) * dilation away
+static void fwd_taps(ConvClass& c, int k, int dilation, int64_t ci, int Ho, int Wo) {
+    const int pad = k / 2;
+    c.Hg = Ho; c.Wg = Wo; c.out_h0 = 0; c.out_w0 = 0; c.T = k * k;
+    for (int r = 0; r < k; ++r)
+        for (int s = 0; s < k; ++s) {
+            const int t = r * k + s;
+            c.dh[t] = (r - pad) * dilation; c.dw[t] = (s - pad) * dilation; c.wofs[t] = (int)(t * ci);
+        }
+}
+
+// check_dims, then the geometry of y[N,Ho,Wo,Co] = conv(x[N,Hi,Wi,Ci], w[Co,k,k,Ci]), padding dilation * (k / 2), as ONE problem
+// without image groups (max_pad = dilation: an atrous problem never takes the LDS-resident halo form, halo_ok()); the caller adds
+// its pointers and its epilogue
+static int fwd_problem(ConvP& p, int64_t n, int64_t hi, int64_t wi, int64_t ci, int64_t co, int k, int stride, int dilation) {
+    const int e = check_dims(n, hi, wi, ci, co, k, stride, dilation);
+    if (e) return e;
+    p.N = (int)n; p.Hi = (int)hi; p.Wi = (int)wi; p.Ci = (int)ci;
+    p.Ho = conv_out(hi, k, stride); p.Wo = conv_out(wi, k, stride); p.Co = (int)co;
+    p.in_s = stride; p.out_s = 1; p.w_row_stride = (int)(k * k * ci); p.n_classes = 1;
+    p.max_pad = dilation;
+    p.groups = 1;
+    p.acc_ns = afan_nhwc::acc_slot_count(co);
+    fwd_taps(p.cls[0], k, dilation, ci, p.Ho, p.Wo);
+    return AFAN_OK;
+}
+
+// Which forward kernel takes p: the small-channel kernel (afan_conv_small.hip), the 64 -> 64 weights-in-registers kernel
+// (afan_conv_c64.hip; dilation 1), the tiled kernel, or none.  small_ok / c64_ok = false: the caller has no such form and the shape
+// stays with the tiled kernel.  (The 3-channel image stem is chosen by ci == 3, before a ConvP exists.)
+enum FwdFamily { FWD_NONE, FWD_SMALL, FWD_C64, FWD_TILED };
+static FwdFamily fwd_family(const ConvP& p, int k, int stride, bool small_ok, bool c64_ok) {
+    if (small_ok && small_eligible(p)) return FWD_SMALL;
+    if (p.Ci % 8 != 0 || p.Co % 8 != 0 || p.Ci < 40 || p.Co < 40) return FWD_NONE;   // (a small shape that asked for the partial-slab statistics, too)
+    if (c64_ok && p.max_pad == 1 && afan_c64::eligible(p.N, p.Hi, p.Wi, p.Ci, p.Co, k, stride)) return FWD_C64;
+    return FWD_TILED;
+}
+
+static int fwd_launch(FwdFamily f, const ConvP& p, hipStream_t st) {
+    if (f == FWD_SMALL) return small_launch(p, st);
+    if (f == FWD_C64) {
+        afan_c64::Params q{};
+        q.x = p.x; q.w = p.w; q.y = p.y; q.N = p.N; q.H = p.Hi; q.W = p.Wi; q.flip = 0;
+        q.acc = p.acc; q.acc_ns = p.acc_ns; q.shift = p.shift;
+        q.aff = p.aff; q.aff_res = p.aff_res; q.aff_relu = p.aff_relu;
+        return afan_c64::launch(q, st);
+    }
+    return dispatch(p, st, false);
+}
+
+// The train-mode BatchNorm (+ ReLU) a forward launch applies behind its grid barrier (ConvP::bnf = 1): y_act = [relu](bn(y)) with
+// the batch statistics of the launch's (first) problem, M positions per channel; stats [4][co] out, the running buffers updated
+// afan_bn_set_running_updates() times like the stand-alone launches
+struct FwdBn {
+    void* y_act; const float* weight; const float* bias; float eps, momentum;
+    float* stats; float* running_mean; float* running_var; int64_t* num_batches; int relu; void* barrier;
+};
+static void set_fwd_bnf(ConvP& p, const FwdBn& b, int64_t M) {
+    const int pending = afan_nhwc::set_running_updates(1);
+    afan_nhwc::set_running_updates(pending);
+    p.bnf = 1; p.bar = (unsigned*)b.barrier; p.y2 = (uint16_t*)b.y_act;
+    p.bnf_w = b.weight; p.bnf_b = b.bias; p.bnf_eps = b.eps; p.bnf_mom = b.momentum;
+    p.bnf_rmean = b.running_mean; p.bnf_rvar = b.running_var; p.bnf_nbt = b.num_batches; p.bnf_updates = pending;
+    p.bnf_stats = b.stats; p.bnf_relu = b.relu ? 1 : 0;
+    p.bnf_inv_m = 1.0 / (double)M;
+    p.bnf_unbias = M > 1 ? (float)((double)M / (double)(M - 1)) : 1.0f;
+}
+
+// ---- input gradients: what a caller of dgrad_impl may ask for beyond the plain problem ----------------------------------------------
+struct DgradReq {
+    int dilation = 1;
+    const void* dy_sc = nullptr;          // the stride-2 pair form: the projection's dy (behind dy in one allocation), wt = [Ci][10][Co]
+    const void* addend = nullptr;         // dx += addend
+    const void* bn_x = nullptr;           // the BatchNorm backward's sums over dx: its input, its statistics, its stored output ...
+    const float* bn_stats = nullptr;
+    int bn_relu = 0;
+    const void* bn_y = nullptr;
+    float* bn_partials = nullptr;         // ... into partial slabs, or
+    double* bn_acc = nullptr;             // ... into f64 accumulators (never both)
+    int groups = 1;
+    const float* aff_alpha = nullptr;     // the frozen BatchNorm (+ ReLU: aff_act, its stored output) in front, applied in the epilogue
+    const void* aff_act = nullptr;
+    void* dx2 = nullptr;                  // ... in the dual form (afan_conv_dgrad_dual_nhwc_bf16): the masked gradient
+    bool any_family = false;              // ... on the small-channel and the 64 -> 64 kernels too (there aff_act is optional)
+    const ConvP* bnf = nullptr;           // the BatchNorm backward itself behind a grid barrier in this launch: bar, y2, bnf_dw/db/accum, bsc
+};
+
+static int dgrad_impl(const void* dy, const void* wt, void* dx, int64_t n, int64_t hi, int64_t wi, int64_t ci, int64_t co, int k,
+                      int stride, afan_stream_t stream, const DgradReq& r) {
+    const void* const dy_sc = r.dy_sc;
+    const ConvP* const bnf = r.bnf;
+    const int dilation = r.dilation, groups = r.groups;
     int e = check_dims(n, hi, wi, co, ci, k, stride, dilation);   // reduction runs over co here
     if (e) return e;
     AFAN_TRACE_PROBLEM(0, afan::trace::DGRAD, n, hi, wi, ci, co, k, stride, dilation);
@@ -1658,7 +1748,7 @@ static int dgrad_impl(const void* dy, const void* dy_sc, const void* wt, void* d
     if (!dy || !wt || !dx) return AFAN_ENULL;
     if (!aligned(dy, 16) || !aligned(wt, 16) || !aligned(dx, 16)) return AFAN_EALIGN;
     const int pad = k / 2;
-    const int ho = (int)((hi + 2 * pad - k) / stride + 1), wo = (int)((wi + 2 * pad - k) / stride + 1);
+    const int ho = conv_out(hi, k, stride), wo = conv_out(wi, k, stride);
     hipStream_t st = (hipStream_t)stream;
     ConvP p{};
     p.x = (const uint16_t*)dy; p.w = (const uint16_t*)wt; p.y = (uint16_t*)dx;
@@ -1676,31 +1766,31 @@ static int dgrad_impl(const void* dy, const void* dy_sc, const void* wt, void* d
         p.a_extra = sc_off * 2;
     }
     p.max_pad = dilation;
-    p.addend = (const uint16_t*)addend;
-    if (aff_alpha) {                                         // the layer in front's frozen BatchNorm + ReLU backward in the epilogue
-        // any_family (afan_conv_dgrad_affine_any_nhwc_bf16): the small-channel and the 64 -> 64 kernels too, in instantiations of their
-        // own, and there the ReLU mask is optional (aff_act == NULL: a frozen BatchNorm without a ReLU)
-        any_family = any_family && !dx2;
-        if (!aff_act && !any_family) return AFAN_ENULL;
-        if ((addend && !dx2) || bn_partials || bn_acc || dy_sc || groups > 1 || !aligned(aff_act, 16)) return AFAN_ESHAPE;
-        if (dx2 && (!aligned(dx2, 16) || (addend && !aligned(addend, 16)))) return AFAN_EALIGN;
+    p.addend = (const uint16_t*)r.addend;
+    // any_family (afan_conv_dgrad_affine_nhwc_bf16): the small-channel and the 64 -> 64 kernels too, in instantiations of their own,
+    // and there the ReLU mask is optional (aff_act == NULL: a frozen BatchNorm without a ReLU)
+    const bool any_family = r.any_family && !r.dx2;
+    if (r.aff_alpha) {                                       // the layer in front's frozen BatchNorm + ReLU backward in the epilogue
+        if (!r.aff_act && !any_family) return AFAN_ENULL;
+        if ((r.addend && !r.dx2) || r.bn_partials || r.bn_acc || dy_sc || groups > 1 || !aligned(r.aff_act, 16)) return AFAN_ESHAPE;
+        if (r.dx2 && (!aligned(r.dx2, 16) || (r.addend && !aligned(r.addend, 16)))) return AFAN_EALIGN;
         if (!any_family && afan_c64::eligible(n, hi, wi, co, ci, k, stride)) return AFAN_ESHAPE;      // (that kernel's training epilogue has no such form)
-        p.aff = aff_alpha; p.aff_res = (const uint16_t*)aff_act; p.aff_bwd = dx2 ? 2 : 1; p.y2 = (uint16_t*)dx2;
+        p.aff = r.aff_alpha; p.aff_res = (const uint16_t*)r.aff_act; p.aff_bwd = r.dx2 ? 2 : 1; p.y2 = (uint16_t*)r.dx2;
     }
-    if (bn_partials && bn_acc) return AFAN_ESHAPE;
-    if (bn_partials || bn_acc) {
-        if (!bn_x || !bn_stats) return AFAN_ENULL;
-        if (bn_acc && !aligned(bn_acc, 16)) return AFAN_EALIGN;
+    if (r.bn_partials && r.bn_acc) return AFAN_ESHAPE;
+    if (r.bn_partials || r.bn_acc) {
+        if (!r.bn_x || !r.bn_stats) return AFAN_ENULL;
+        if (r.bn_acc && !aligned(r.bn_acc, 16)) return AFAN_EALIGN;
         // image groups: every parity class of a stride-2 launch has at least (hi/2)*(wi/2) positions per image, a
         // multiple of that class's own count is what matters; the smallest class decides
-        if ((e = set_groups(p, groups, n, stride == 1 ? hi * wi : (hi / 2) * (wi / 2), ci, bn_acc != nullptr))) return e;
+        if ((e = set_groups(p, groups, n, stride == 1 ? hi * wi : (hi / 2) * (wi / 2), ci, r.bn_acc != nullptr))) return e;
         if (groups == 2 && stride == 2 && ((hi | wi) & 1)) return AFAN_ESHAPE;
-        p.stats = bn_partials; p.acc = bn_acc; p.acc_ns = afan_nhwc::acc_slot_count(ci);
-        p.bnx = (const uint16_t*)bn_x; p.bn_stats = bn_stats; p.bn_relu = bn_relu; p.bny = (const uint16_t*)bn_y;
+        p.stats = r.bn_partials; p.acc = r.bn_acc; p.acc_ns = afan_nhwc::acc_slot_count(ci);
+        p.bnx = (const uint16_t*)r.bn_x; p.bn_stats = r.bn_stats; p.bn_relu = r.bn_relu; p.bny = (const uint16_t*)r.bn_y;
     }
     if (bnf) {      // the BatchNorm backward itself behind a grid barrier in this launch (afan_conv_dgrad_bn_nhwc_bf16)
         // stride 1 (3x3 incl. atrous, 1x1), or the stride-2 pair form (a block's first 3x3 + its projection, four output-parity classes)
-        if (!bn_acc || (k != 3 && k != 1) || aff_alpha || groups > 1) return AFAN_ESHAPE;
+        if (!r.bn_acc || (k != 3 && k != 1) || r.aff_alpha || groups > 1) return AFAN_ESHAPE;
         if (!((stride == 1 && !dy_sc) || (stride == 2 && dy_sc && k == 3 && dilation == 1 && !((hi | wi) & 1)))) return AFAN_ESHAPE;
         if (afan_c64::eligible(n, hi, wi, co, ci, k, stride)) return AFAN_ESHAPE;          // (that kernel has no such epilogue)
         p.bnf = 2; p.bar = bnf->bar; p.y2 = bnf->y2; p.bnf_dw = bnf->bnf_dw; p.bnf_db = bnf->bnf_db; p.bnf_accum = bnf->bnf_accum;
@@ -1711,13 +1801,13 @@ static int dgrad_impl(const void* dy, const void* dy_sc, const void* wt, void* d
     AFAN_PROF_FLOPS(bnf ? "conv_bn_dgrad_kernel" : "conv_igemm_dgrad_kernel", bytes + (dy_sc ? 2.0 * ((double)n * ho * wo * co + (double)co * ci) : 0.0),
                     2.0 * (double)n * ho * wo * co * (k * k + (dy_sc ? 1 : 0)) * ci, st);
     p.in_s = 1;
-    if (!dy_sc && !bn_partials && groups <= 1 && dilation == 1 && afan_c64::eligible(n, hi, wi, co, ci, k, stride)) {
+    if (!dy_sc && !r.bn_partials && groups <= 1 && dilation == 1 && afan_c64::eligible(n, hi, wi, co, ci, k, stride)) {
         afan_c64::Params q{};
         q.x = p.x; q.w = p.w; q.y = p.y; q.N = p.N; q.H = (int)hi; q.W = (int)wi; q.flip = 1;
-        q.acc = bn_acc; q.acc_ns = p.acc_ns; q.bnx = p.bnx; q.bn_stats = p.bn_stats; q.bn_relu = p.bn_relu; q.bny = p.bny;
+        q.acc = r.bn_acc; q.acc_ns = p.acc_ns; q.bnx = p.bnx; q.bn_stats = p.bn_stats; q.bn_relu = p.bn_relu; q.bny = p.bny;
         q.addend = p.addend;
         if (p.aff) {                                         // (any_family: the c64_dgrad_aff instantiation reads its alpha row as 16-byte vectors)
-            if (!aligned(aff_alpha, 16)) return AFAN_EALIGN;
+            if (!aligned(r.aff_alpha, 16)) return AFAN_EALIGN;
             q.aff = p.aff; q.aff_res = p.aff_res; q.aff_relu = p.aff_res ? 1 : 0;
         }
         return afan_c64::launch(q, st);
@@ -1727,60 +1817,55 @@ static int dgrad_impl(const void* dy, const void* dy_sc, const void* wt, void* d
         p.out_s = 1; p.n_classes = 1;
         ConvClass& c0 = p.cls[0];
         c0.Hg = (int)hi; c0.Wg = (int)wi; c0.out_h0 = 0; c0.out_w0 = 0; c0.T = k * k;
-        for (int r = 0; r < k; ++r)
-            for (int s = 0; s < k; ++s) {
-                const int t = r * k + s;
-                c0.dh[t] = (pad - r) * dilation; c0.dw[t] = (pad - s) * dilation; c0.wofs[t] = (int)(t * co);
+        for (int a = 0; a < k; ++a)
+            for (int b = 0; b < k; ++b) {
+                const int t = a * k + b;
+                c0.dh[t] = (pad - a) * dilation; c0.dw[t] = (pad - b) * dilation; c0.wofs[t] = (int)(t * co);
             }
-        if (bnf) return small_eligible(p) ? AFAN_ESHAPE : dispatch_bnf(p, st, true);
-        if (small_eligible(p)) {
-            if ((p.aff && (!any_family || dilation > 1)) || !small_groups_ok(p)) return AFAN_ESHAPE;   // (atrous affine form: the tiled kernel only)
-            if (p.aff && !aligned(aff_alpha, 16)) return AFAN_EALIGN;              // (small_dgrad_aff reads its alpha row as 16-byte vectors)
-            return small_launch(p, st);
-        }
-        if (co % 8 != 0 || ci % 8 != 0 || co < 40 || ci < 40) return AFAN_ESHAPE;   // (small shape asked for the partial-slab sums)
-        if (p.aff && !p.aff_res) return AFAN_ESHAPE;                                // (the tiled kernel's backward epilogue always masks)
-        return dispatch(p, st, true);
-    }
-    // stride 2: output pixel (2h'+ph, 2w'+pw) receives tap (r,s) iff (ph + pad - r) and (pw + pad - s) are even;
-    // then the dy pixel is (h' + (ph+pad-r)/2, w' + (pw+pad-s)/2).  Four classes (1/2/2/4 taps for k = 3) in ONE launch.
-    p.out_s = 2;
-    int nc = 0;
-    for (int ph = 0; ph < 2; ++ph)
-        for (int pw = 0; pw < 2; ++pw) {
-            ConvClass& c = p.cls[nc];
-            c.Hg = (int)((hi - ph + 1) / 2); c.Wg = (int)((wi - pw + 1) / 2);
-            if (c.Hg <= 0 || c.Wg <= 0) continue;
-            c.out_h0 = ph; c.out_w0 = pw;
-            int T = 0;
-            for (int r = 0; r < k; ++r)
-                for (int s = 0; s < k; ++s) {
-                    const int a = ph + pad - r, b = pw + pad - s;
-                    if ((a & 1) || (b & 1)) continue;
-                    c.dh[T] = a / 2; c.dw[T] = b / 2; c.wofs[T] = (int)((r * k + s) * co);
+    } else {
+        // stride 2: output pixel (2h'+ph, 2w'+pw) receives tap (a,b) iff (ph + pad - a) and (pw + pad - b) are even;
+        // then the dy pixel is (h' + (ph+pad-a)/2, w' + (pw+pad-b)/2).  Four classes (1/2/2/4 taps for k = 3) in ONE launch.
+        p.out_s = 2;
+        int nc = 0;
+        for (int ph = 0; ph < 2; ++ph)
+            for (int pw = 0; pw < 2; ++pw) {
+                ConvClass& c = p.cls[nc];
+                c.Hg = (int)((hi - ph + 1) / 2); c.Wg = (int)((wi - pw + 1) / 2);
+                if (c.Hg <= 0 || c.Wg <= 0) continue;
+                c.out_h0 = ph; c.out_w0 = pw;
+                int T = 0;
+                for (int a = 0; a < k; ++a)
+                    for (int b = 0; b < k; ++b) {
+                        const int u = ph + pad - a, v = pw + pad - b;
+                        if ((u & 1) || (v & 1)) continue;
+                        c.dh[T] = u / 2; c.dw[T] = v / 2; c.wofs[T] = (int)((a * k + b) * co);
+                        ++T;
+                    }
+                if (dy_sc && ph == 0 && pw == 0) {               // the 1x1 / 2 projection: one more tap of the even/even class
+                    c.dh[T] = 0; c.dw[T] = 0; c.wofs[T] = (int)(9 * co); c.aofs[T] = (int)sc_off;
                     ++T;
                 }
-            if (dy_sc && ph == 0 && pw == 0) {               // the 1x1 / 2 projection: one more tap of the even/even class
-                c.dh[T] = 0; c.dw[T] = 0; c.wofs[T] = (int)(9 * co); c.aofs[T] = (int)sc_off;
-                ++T;
+                if (T == 0) {
+                    // no tap reaches this parity class (1x1 stride 2): its gradient is zero.  One all-invalid tap makes
+                    // the kernel write zeros through its normal path.
+                    T = 1; c.dh[0] = -(ho + 2); c.dw[0] = 0; c.wofs[0] = 0;   // (small enough for the 32-bit tap offset)
+                }
+                c.T = T;
+                ++nc;
             }
-            if (T == 0) {
-                // no tap reaches this parity class (1x1 stride 2): its gradient is zero.  One all-invalid tap makes
-                // the kernel write zeros through its normal path.
-                T = 1; c.dh[0] = -(ho + 2); c.dw[0] = 0; c.wofs[0] = 0;   // (small enough for the 32-bit tap offset)
-            }
-            c.T = T;
-            ++nc;
-        }
-    p.n_classes = nc;
-    if (bnf) return nc == 4 ? dispatch_bnf(p, st, true) : AFAN_ESHAPE;      // (even sizes: four classes of equal size, no idle tiles)
-    if (!dy_sc && small_eligible(p)) {
-        if ((p.aff && !any_family) || !small_groups_ok(p)) return AFAN_ESHAPE;
-        if (p.aff && !aligned(aff_alpha, 16)) return AFAN_EALIGN;
+        p.n_classes = nc;
+    }
+    // the family: in-launch BatchNorm (tiled instantiations only), small-channel (never the pair form), tiled
+    const bool small = !dy_sc && small_eligible(p);
+    // (stride 2 in-launch: even sizes only — four classes of equal size, no idle tiles)
+    if (bnf) return (small || p.n_classes != (stride == 1 ? 1 : 4)) ? AFAN_ESHAPE : dispatch_bnf(p, st, true);
+    if (small) {
+        if ((p.aff && (!any_family || dilation > 1)) || !small_groups_ok(p)) return AFAN_ESHAPE;   // (atrous affine form: the tiled kernel only)
+        if (p.aff && !aligned(r.aff_alpha, 16)) return AFAN_EALIGN;                // (small_dgrad_aff reads its alpha row as 16-byte vectors)
         return small_launch(p, st);
     }
-    if (co % 8 != 0 || ci % 8 != 0 || co < 40 || ci < 40) return AFAN_ESHAPE;
-    if (p.aff && !p.aff_res) return AFAN_ESHAPE;
+    if (co % 8 != 0 || ci % 8 != 0 || co < 40 || ci < 40) return AFAN_ESHAPE;   // (small shape asked for the partial-slab sums)
+    if (p.aff && !p.aff_res) return AFAN_ESHAPE;                                // (the tiled kernel's backward epilogue always masks)
     return dispatch(p, st, true);
 }
 
@@ -1826,55 +1911,39 @@ int afan_conv_fwd_nhwc_bf16(const void* x, const void* w, void* y, int64_t n, in
         AFAN_PROF_FLOPS("conv_stem_fwd_kernel", 2.0 * (M * co + M * 3 + 27.0 * co), 2.0 * M * co * 27, st);
         return afan_stem::fwd_launch(x, w, y, n, hi, wi, co, stats_acc, afan_nhwc::acc_slot_count(co), stats_shift, st);
     }
-    int e = check_dims(n, hi, wi, ci, co, k, stride, dilation);
+    ConvP p{};
+    int e = fwd_problem(p, n, hi, wi, ci, co, k, stride, dilation);
     if (e) return e;
     if (!x || !w || !y) return AFAN_ENULL;
     if (!aligned(x, 16) || !aligned(w, 16) || !aligned(y, 16)) return AFAN_EALIGN;
-    const int pad = k / 2;
-    ConvP p{};
-    p.max_pad = dilation;
     p.x = (const uint16_t*)x; p.w = (const uint16_t*)w; p.y = (uint16_t*)y;
-    p.N = (int)n; p.Hi = (int)hi; p.Wi = (int)wi; p.Ci = (int)ci;
-    p.Ho = (int)((hi + 2 * pad - k) / stride + 1); p.Wo = (int)((wi + 2 * pad - k) / stride + 1); p.Co = (int)co;
-    p.in_s = stride; p.out_s = 1; p.w_row_stride = (int)(k * k * ci); p.n_classes = 1;
     if (stats_partials && stats_acc) return AFAN_ESHAPE;   // one destination for the moments, not both
     if (stats_acc && !aligned(stats_acc, 16)) return AFAN_EALIGN;
-    p.stats = stats_partials; p.shift = stats_shift; p.acc = stats_acc; p.acc_ns = afan_nhwc::acc_slot_count(co);
+    p.stats = stats_partials; p.shift = stats_shift; p.acc = stats_acc;
     if ((e = set_groups(p, groups, n, (int64_t)p.Ho * p.Wo, co, stats_acc != nullptr))) return e;
-    ConvClass& c0 = p.cls[0];
-    c0.Hg = p.Ho; c0.Wg = p.Wo; c0.out_h0 = 0; c0.out_w0 = 0; c0.T = k * k;
-    for (int r = 0; r < k; ++r)
-        for (int s = 0; s < k; ++s) {
-            const int t = r * k + s;
-            c0.dh[t] = (r - pad) * dilation; c0.dw[t] = (s - pad) * dilation; c0.wofs[t] = (int)(t * ci);
-        }
     hipStream_t st = (hipStream_t)stream;
     const double M = (double)n * p.Ho * p.Wo;
     AFAN_PROF_FLOPS("conv_igemm_fwd_kernel", 2.0 * (M * co + (double)n * hi * wi * ci + (double)co * k * k * ci),
                     2.0 * M * co * k * k * ci, st);
-    if (small_eligible(p)) return small_groups_ok(p) ? small_launch(p, st) : AFAN_ESHAPE;
-    if (ci % 8 != 0 || co % 8 != 0 || ci < 40 || co < 40) return AFAN_ESHAPE;   // (small shape asked for the partial-slab statistics)
-    if (!stats_partials && groups <= 1 && dilation == 1 && afan_c64::eligible(n, hi, wi, ci, co, k, stride)) {   // weights-in-registers kernel
-        afan_c64::Params q{};
-        q.x = p.x; q.w = p.w; q.y = p.y; q.N = p.N; q.H = p.Hi; q.W = p.Wi; q.flip = 0;
-        q.acc = stats_acc; q.acc_ns = p.acc_ns; q.shift = stats_shift;
-        return afan_c64::launch(q, st);
-    }
-    return dispatch(p, st, false);
+    // (the weights-in-registers kernel has neither the partial-slab statistics nor image groups: the tiled kernel takes those)
+    const FwdFamily f = fwd_family(p, k, stride, true, !stats_partials && groups <= 1);
+    if (f == FWD_NONE || (f == FWD_SMALL && !small_groups_ok(p))) return AFAN_ESHAPE;
+    return fwd_launch(f, p, st);
 }
 
-// The same convolution with a FROZEN BatchNorm (+ residual) (+ ReLU) applied in its epilogue: y = [relu](bf16(conv(x, w)) * alpha
-// + beta [+ residual]), coefs = an afan_affine_coefs block — bit for bit the convolution launch followed by afan_affine_apply,
-// without the raw tensor's round trip and the second launch.  any_family = 0 (afan_conv_fwd_affine_nhwc_bf16, Detection's frozen
-// bottlenecks: seven launches of 5-13 us per block become three or four): shapes of the tiled kernel only, AFAN_ESHAPE for the
-// others (the caller issues the two launches).  any_family = 1 (afan_conv_fwd_affine_any_nhwc_bf16, Classification's eval-mode
-// forward, infer.py: one launch per convolution): every forward family of afan_conv_fwd_nhwc_bf16 at dilation 1 — the tiled kernel,
-// the small-channel kernel (afan_conv_small.hip), the 64 -> 64 weights-in-registers kernel (afan_conv_c64.hip) and the 3-channel
-// image stem (afan_conv_stem.hip; no residual there), each in an instantiation of its own (the training kernels are not touched).
-// The 7x7 stem (afan_conv_stem7.hip) has no such form.
-static int fwd_affine_impl(const void* x, const void* w, void* y, int64_t n, int64_t hi, int64_t wi, int64_t ci, int64_t co, int k,
-                           int stride, const float* coefs, const void* residual, int relu, afan_stream_t stream, bool any_family,
-                           int dilation = 1) {
+// The same convolution with a FROZEN BatchNorm (+ residual) (+ ReLU) applied in its epilogue: y = [relu](bf16(conv(x, w; padding =
+// dilation * (k / 2), dilation)) * alpha + beta [+ residual]), coefs = an afan_affine_coefs block — bit for bit
+// afan_conv_fwd_nhwc_bf16(dilation) followed by afan_affine_apply, without the raw tensor's round trip and the second launch.
+// any_family = 0 (Detection's frozen bottlenecks: seven launches of 5-13 us per block become three or four): shapes of the tiled
+// kernel only, AFAN_ESHAPE for the others (the caller issues the two launches).  any_family = 1 (the eval-mode forwards, infer.py and
+// deeplab.py: one launch per convolution): at dilation 1 every forward family of afan_conv_fwd_nhwc_bf16 — the tiled kernel, the
+// small-channel kernel (afan_conv_small.hip), the 64 -> 64 weights-in-registers kernel (afan_conv_c64.hip) and the 3-channel image stem
+// (afan_conv_stem.hip; no residual there), each in an instantiation of its own (the training kernels are not touched).  dilation > 1:
+// 3x3 at stride 1 on the tiled kernel, whose epilogue carries the affine in every instantiation — the launch is the one
+// afan_conv_fwd_nhwc_bf16 would choose, so no kernel is added.  The 7x7 stem (afan_conv_stem7.hip) has no such form.
+int afan_conv_fwd_affine_nhwc_bf16(const void* x, const void* w, void* y, int64_t n, int64_t hi, int64_t wi, int64_t ci, int64_t co,
+                                   int k, int stride, int dilation, const float* coefs, const void* residual, int relu,
+                                   int any_family, afan_stream_t stream) {
     if (any_family && ci == 3 && dilation == 1) {                                // the image stem: affine + ReLU at its staged store
         AFAN_TRACE_PROBLEM(0, afan::trace::FWD, n, hi, wi, ci, co, k, stride, 1);
         if (!afan_stem::eligible(n, hi, wi, ci, co, k, stride) || residual) return AFAN_ESHAPE;
@@ -1885,69 +1954,24 @@ static int fwd_affine_impl(const void* x, const void* w, void* y, int64_t n, int
         AFAN_PROF_FLOPS("conv_stem_fwd_kernel", 2.0 * (M * co + M * 3 + 27.0 * co), 2.0 * M * co * 27, st);
         return afan_stem::fwd_aff_launch(x, w, y, n, hi, wi, co, coefs, relu, st);
     }
-    int e = check_dims(n, hi, wi, ci, co, k, stride, dilation);
+    ConvP p{};
+    const int e = fwd_problem(p, n, hi, wi, ci, co, k, stride, dilation);
     if (e) return e;
     AFAN_TRACE_PROBLEM(0, afan::trace::FWD, n, hi, wi, ci, co, k, stride, dilation);
     if (!x || !w || !y || !coefs) return AFAN_ENULL;
     if (!aligned(x, 16) || !aligned(w, 16) || !aligned(y, 16) || (residual && !aligned(residual, 16))) return AFAN_EALIGN;
-    const int pad = k / 2;     // (a dilated 3x3 at stride 1 keeps the spatial size, like the plain one)
-    ConvP p{};
-    p.max_pad = dilation;      // (atrous: never the LDS-resident halo form, halo_ok())
     p.x = (const uint16_t*)x; p.w = (const uint16_t*)w; p.y = (uint16_t*)y;
-    p.N = (int)n; p.Hi = (int)hi; p.Wi = (int)wi; p.Ci = (int)ci;
-    p.Ho = (int)((hi + 2 * pad - k) / stride + 1); p.Wo = (int)((wi + 2 * pad - k) / stride + 1); p.Co = (int)co;
-    p.in_s = stride; p.out_s = 1; p.w_row_stride = (int)(k * k * ci); p.n_classes = 1;
-    p.acc_ns = afan_nhwc::acc_slot_count(co);
-    if ((e = set_groups(p, 1, n, (int64_t)p.Ho * p.Wo, co, false))) return e;
     p.aff = coefs; p.aff_res = (const uint16_t*)residual; p.aff_relu = relu ? 1 : 0;
-    ConvClass& c0 = p.cls[0];
-    c0.Hg = p.Ho; c0.Wg = p.Wo; c0.out_h0 = 0; c0.out_w0 = 0; c0.T = k * k;
-    for (int r = 0; r < k; ++r)
-        for (int s = 0; s < k; ++s) {
-            const int t = r * k + s;
-            c0.dh[t] = (r - pad) * dilation; c0.dw[t] = (s - pad) * dilation; c0.wofs[t] = (int)(t * ci);
-        }
-    if (dilation > 1 && small_eligible(p)) return AFAN_ESHAPE;     // (atrous: the tiled kernel only, as afan_conv_fwd_nhwc_bf16's callers ask)
-    const bool small = small_eligible(p), c64 = !small && dilation == 1 && afan_c64::eligible(n, hi, wi, ci, co, k, stride);
-    if (!any_family && (small || c64)) return AFAN_ESHAPE;
-    if (!small && (ci % 8 != 0 || co % 8 != 0 || ci < 40 || co < 40)) return AFAN_ESHAPE;
-    if ((small || c64) && !aligned(coefs, 16)) return AFAN_EALIGN;   // (those two read the coefficient rows as 16-byte vectors)
+    // the small-channel and the 64 -> 64 kernels: for any_family callers, at dilation 1 (atrous: the tiled kernel only, as
+    // afan_conv_fwd_nhwc_bf16's callers ask); they read the coefficient rows as 16-byte vectors
+    const FwdFamily f = fwd_family(p, k, stride, true, true);
+    if (f == FWD_NONE || (f != FWD_TILED && !(any_family && dilation == 1))) return AFAN_ESHAPE;
+    if (f != FWD_TILED && !aligned(coefs, 16)) return AFAN_EALIGN;
     hipStream_t st = (hipStream_t)stream;
     const double M = (double)n * p.Ho * p.Wo;
     AFAN_PROF_FLOPS("conv_igemm_fwd_kernel", 2.0 * (M * co * (residual ? 2 : 1) + (double)n * hi * wi * ci + (double)co * k * k * ci),
                     2.0 * M * co * k * k * ci, st);
-    if (small) return small_launch(p, st);
-    if (c64) {
-        afan_c64::Params q{};
-        q.x = p.x; q.w = p.w; q.y = p.y; q.N = p.N; q.H = p.Hi; q.W = p.Wi; q.flip = 0; q.acc_ns = p.acc_ns;
-        q.aff = coefs; q.aff_res = p.aff_res; q.aff_relu = p.aff_relu;
-        return afan_c64::launch(q, st);
-    }
-    return dispatch(p, st, false);
-}
-
-int afan_conv_fwd_affine_nhwc_bf16(const void* x, const void* w, void* y, int64_t n, int64_t hi, int64_t wi, int64_t ci, int64_t co,
-                                   int k, int stride, const float* coefs, const void* residual, int relu, afan_stream_t stream) {
-    return fwd_affine_impl(x, w, y, n, hi, wi, ci, co, k, stride, coefs, residual, relu, stream, false);
-}
-
-int afan_conv_fwd_affine_any_nhwc_bf16(const void* x, const void* w, void* y, int64_t n, int64_t hi, int64_t wi, int64_t ci,
-                                       int64_t co, int k, int stride, const float* coefs, const void* residual, int relu,
-                                       afan_stream_t stream) {
-    return fwd_affine_impl(x, w, y, n, hi, wi, ci, co, k, stride, coefs, residual, relu, stream, true);
-}
-
-// The same with a dilation (Segmentation's eval-mode DeepLab, deeplab.py: the atrous 3x3 convolutions of layer3 / layer4 and of ASPP with
-// their BatchNorms): y = [relu](bf16(conv(x, w; padding = dilation * (k / 2), dilation)) * alpha + beta [+ residual]), bit for bit
-// afan_conv_fwd_nhwc_bf16(dilation) followed by afan_affine_apply.  dilation == 1: afan_conv_fwd_affine_any_nhwc_bf16.  dilation > 1:
-// 3x3 at stride 1 on the tiled kernel, whose epilogue carries the affine in every instantiation — the launch is the one
-// afan_conv_fwd_nhwc_bf16 would choose (max_pad = dilation: never the LDS-resident halo form), so no kernel is added and the training
-// kernels are not touched.  AFAN_ESHAPE where no kernel takes the problem (the caller issues the two launches).
-int afan_conv_fwd_affine_dil_nhwc_bf16(const void* x, const void* w, void* y, int64_t n, int64_t hi, int64_t wi, int64_t ci, int64_t co,
-                                       int k, int stride, int dilation, const float* coefs, const void* residual, int relu,
-                                       afan_stream_t stream) {
-    if (dilation == 1) return fwd_affine_impl(x, w, y, n, hi, wi, ci, co, k, stride, coefs, residual, relu, stream, true);
-    return fwd_affine_impl(x, w, y, n, hi, wi, ci, co, k, stride, coefs, residual, relu, stream, true, dilation);
+    return fwd_launch(f, p, st);
 }
 
 // nb <= 4 forward problems on the SAME input with the SAME output shape in one launch (grid.z = problem): ASPP's atrous 3x3
@@ -1958,7 +1982,7 @@ int afan_conv_fwd_affine_dil_nhwc_bf16(const void* x, const void* w, void* y, in
 // BatchNorm moments go to f64 accumulator blocks (one per problem; groups = 2: two consecutive ones, one per half-batch) or nowhere.
 static int fwd_multi_impl(const void* x, const void* const* w, void* const* y, int nb, int64_t n, int64_t hi, int64_t wi,
                           int64_t ci, int64_t co, const int* ksize, int stride, const int* dilation,
-                          const float* const* stats_shift, double* const* stats_acc, int groups, afan_stream_t stream, const ConvP* bnf) {
+                          const float* const* stats_shift, double* const* stats_acc, int groups, afan_stream_t stream, const FwdBn* bnf) {
     if (nb < 1 || nb > 4) return AFAN_ESHAPE;
     if (groups != 1 && (groups != 2 || !stats_acc || (n & 1))) return AFAN_ESHAPE;
     if (!w || !y || !dilation || !ksize) return AFAN_ENULL;
@@ -1973,30 +1997,25 @@ static int fwd_multi_impl(const void* x, const void* const* w, void* const* y, i
         if (!aligned(w[b], 16) || !aligned(y[b], 16)) return AFAN_EALIGN;
         if (stats_acc && (!stats_acc[b] || !aligned(stats_acc[b], 16))) return stats_acc[b] ? AFAN_EALIGN : AFAN_ENULL;
         if (dilation[b] > dmax) dmax = dilation[b];
-        const int pad = ksize[b] / 2;                 // (a dilated 3x3 at stride 1 keeps the spatial size, like the plain one)
-        const int64_t h_b = (hi + 2 * pad - ksize[b]) / stride + 1, w_b = (wi + 2 * pad - ksize[b]) / stride + 1;
+        const int64_t h_b = conv_out(hi, ksize[b], stride), w_b = conv_out(wi, ksize[b], stride);   // (a dilated 3x3 at stride 1 keeps the spatial size, like the plain one)
         if (b && (h_b != ho || w_b != wo)) return AFAN_ESHAPE;
         ho = h_b; wo = w_b;
     }
     if (!x) return AFAN_ENULL;
     if (!aligned(x, 16)) return AFAN_EALIGN;
-    if (ci % 8 != 0 || co % 8 != 0 || ci < 40 || co < 40 || ci == 3) return AFAN_ESHAPE;
     ConvP p{};
-    p.max_pad = dmax;
+    fwd_problem(p, n, hi, wi, ci, co, ksize[0], stride, dilation[0]);     // (problem 0, checked above; the others' taps below)
+    p.n_classes = nb; p.multi = 1; p.max_pad = dmax;
+    if (fwd_family(p, ksize[0], stride, false, false) != FWD_TILED) return AFAN_ESHAPE;     // (the tiled kernel only)
     p.x = (const uint16_t*)x; p.w = (const uint16_t*)w[0]; p.y = (uint16_t*)y[0];
-    p.N = (int)n; p.Hi = (int)hi; p.Wi = (int)wi; p.Ci = (int)ci;
-    p.Ho = (int)ho; p.Wo = (int)wo; p.Co = (int)co;
-    p.in_s = stride; p.out_s = 1; p.w_row_stride = (int)(ksize[0] * ksize[0] * ci); p.n_classes = nb;
-    p.multi = 1;
     p.acc = stats_acc ? stats_acc[0] : nullptr; p.shift = stats_shift ? stats_shift[0] : nullptr;
-    p.acc_ns = afan_nhwc::acc_slot_count(co);
     {   // groups = 2: the batch is two half-batches, each problem's accumulator block is two consecutive blocks (one per half)
         const int e = set_groups(p, groups, n, ho * wo, co, stats_acc != nullptr);
         if (e) return e;
     }
     double flops = 0, wbytes = 0;
     for (int b = 0; b < nb; ++b) {
-        const int k = ksize[b], pad = k / 2;
+        const int k = ksize[b];
         p.w_off[b] = (const uint16_t*)w[b] - (const uint16_t*)w[0];
         p.y_off[b] = (uint16_t*)y[b] - (uint16_t*)y[0];
         p.w_rs[b] = (int)(k * k * ci);
@@ -2005,13 +2024,7 @@ static int fwd_multi_impl(const void* x, const void* const* w, void* const* y, i
             p.acc_off[b] = stats_acc[b] - stats_acc[0];
             p.shift_off[b] = stats_shift[0] ? stats_shift[b] - stats_shift[0] : 0;
         }
-        ConvClass& c = p.cls[b];
-        c.Hg = p.Ho; c.Wg = p.Wo; c.out_h0 = 0; c.out_w0 = 0; c.T = k * k;
-        for (int r = 0; r < k; ++r)
-            for (int s = 0; s < k; ++s) {
-                const int t = r * k + s;
-                c.dh[t] = (r - pad) * dilation[b]; c.dw[t] = (s - pad) * dilation[b]; c.wofs[t] = (int)(t * ci);
-            }
+        fwd_taps(p.cls[b], k, dilation[b], ci, p.Ho, p.Wo);
         flops += 2.0 * n * ho * wo * co * k * k * ci;
         wbytes += 2.0 * co * k * k * ci;
     }
@@ -2019,15 +2032,7 @@ static int fwd_multi_impl(const void* x, const void* const* w, void* const* y, i
     AFAN_PROF_FLOPS(bnf ? "conv_bn_fwd_kernel" : "conv_igemm_fwd_kernel", (nb + (bnf ? 1 : 0)) * 2.0 * n * ho * wo * co + wbytes + 2.0 * (double)n * hi * wi * ci, flops, st);
     if (bnf) {         // problem 0's train-mode BatchNorm (+ ReLU) inside the launch (afan_conv_fwd_multi_bn_nhwc_bf16)
         if (!stats_acc || groups != 1 || ci % 64 != 0 || co % 64 != 0) return AFAN_ESHAPE;
-        const int64_t M = n * ho * wo;
-        const int pending = afan_nhwc::set_running_updates(1);
-        afan_nhwc::set_running_updates(pending);
-        p.bnf = 1; p.bar = bnf->bar; p.y2 = bnf->y2;
-        p.bnf_w = bnf->bnf_w; p.bnf_b = bnf->bnf_b; p.bnf_eps = bnf->bnf_eps; p.bnf_mom = bnf->bnf_mom;
-        p.bnf_rmean = bnf->bnf_rmean; p.bnf_rvar = bnf->bnf_rvar; p.bnf_nbt = bnf->bnf_nbt; p.bnf_updates = pending;
-        p.bnf_stats = bnf->bnf_stats; p.bnf_relu = bnf->bnf_relu;
-        p.bnf_inv_m = 1.0 / (double)M;
-        p.bnf_unbias = M > 1 ? (float)((double)M / (double)(M - 1)) : 1.0f;
+        set_fwd_bnf(p, *bnf, n * ho * wo);
         return dispatch_bnf(p, st, false);
     }
     return dispatch(p, st, false);
@@ -2051,10 +2056,7 @@ int afan_conv_fwd_multi_bn_nhwc_bf16(const void* x, const void* const* w, void* 
     if (!y_act0 || !stats0 || !barrier || !stats_acc || !stats_shift) return AFAN_ENULL;
     if (!aligned(y_act0, 16) || !aligned(barrier, 64)) return AFAN_EALIGN;
     if (nb < 2) return AFAN_ESHAPE;
-    ConvP b{};
-    b.bar = (unsigned*)barrier; b.y2 = (uint16_t*)y_act0;
-    b.bnf_w = bn_weight; b.bnf_b = bn_bias; b.bnf_eps = eps; b.bnf_mom = momentum;
-    b.bnf_rmean = running_mean; b.bnf_rvar = running_var; b.bnf_nbt = num_batches; b.bnf_stats = stats0; b.bnf_relu = relu ? 1 : 0;
+    const FwdBn b{y_act0, bn_weight, bn_bias, eps, momentum, stats0, running_mean, running_var, num_batches, relu, barrier};
     return fwd_multi_impl(x, w, y, nb, n, hi, wi, ci, co, ksize, stride, dilation, stats_shift, stats_acc, 1, stream, &b);
 }
 
@@ -2087,43 +2089,29 @@ int afan_conv_dgrad_nhwc_bf16(const void* dy, const void* wt, void* dx, int64_t 
                               int64_t co, int k, int stride, int dilation, const void* addend, const void* bn_x,
                               const float* bn_stats, int bn_relu, const void* bn_y, float* bn_partials,
                               double* bn_acc, int groups, afan_stream_t stream) {
-    return dgrad_impl(dy, nullptr, wt, dx, n, hi, wi, ci, co, k, stride, dilation, addend, bn_x, bn_stats, bn_relu, bn_y,
-                      bn_partials, bn_acc, groups, stream);
+    DgradReq r;
+    r.dilation = dilation; r.addend = addend; r.groups = groups;
+    r.bn_x = bn_x; r.bn_stats = bn_stats; r.bn_relu = bn_relu; r.bn_y = bn_y; r.bn_partials = bn_partials; r.bn_acc = bn_acc;
+    return dgrad_impl(dy, wt, dx, n, hi, wi, ci, co, k, stride, stream, r);
 }
 
-// The input gradient of a convolution whose INPUT came out of a frozen BatchNorm + ReLU (Detection's bottlenecks), with that layer's
-// backward applied on the way out: dx = bf16((act > 0 ? bf16(dgrad(dy)) : 0) * alpha[c]) — bit for bit afan_conv_dgrad_nhwc_bf16
-// followed by afan_affine_relu_bwd(relu = 1), without the raw gradient's round trip and the second launch.  alpha = that layer's
-// alpha row [ci], act = its stored output [n, ci, hi, wi].  AFAN_ESHAPE where another kernel owns the shape.
+// The input gradient of a convolution whose INPUT came out of a frozen BatchNorm + ReLU, with that layer's backward applied on the way
+// out: dx = bf16((act > 0 ? bf16(dgrad(dy, wt; dilation)) : 0) * alpha[c]) — bit for bit afan_conv_dgrad_nhwc_bf16(dilation) followed by
+// afan_affine_relu_bwd(relu = 1), without the raw gradient's round trip and the second launch.  alpha = that layer's alpha row [ci],
+// act = its stored output [n, ci, hi, wi].  any_family = 0 (Detection's bottlenecks): the tiled kernel only, AFAN_ESHAPE where
+// another kernel owns the shape.  any_family = 1 (the eval-mode backwards, infer.py and deeplab.py: one launch per convolution): at
+// dilation 1 the small-channel kernel (small_dgrad_aff<KK>) and the 64 -> 64 weights-in-registers kernel (c64_dgrad_aff) too, each in
+// an instantiation of its own (the training kernels are not touched).  On those two the ReLU mask is optional (act == NULL:
+// dx = bf16(bf16(dgrad(dy)) * alpha[c]), afan_affine_relu_bwd(relu = 0)) and alpha is 16-byte aligned; the tiled kernel — dilation > 1:
+// 3x3 at stride 1 on it, the launch afan_conv_dgrad_nhwc_bf16 would choose — always masks and answers AFAN_ESHAPE without a mask,
+// like every problem no input-gradient kernel takes (the caller issues the two launches).
 int afan_conv_dgrad_affine_nhwc_bf16(const void* dy, const void* wt, void* dx, int64_t n, int64_t hi, int64_t wi, int64_t ci, int64_t co,
-                                     int k, int stride, const float* alpha, const void* act, afan_stream_t stream) {
-    if (!alpha || !act) return AFAN_ENULL;
-    return dgrad_impl(dy, nullptr, wt, dx, n, hi, wi, ci, co, k, stride, 1, nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr, 1, stream,
-                      alpha, act);
-}
-
-// The same on every input-gradient family of afan_conv_dgrad_nhwc_bf16 at dilation 1 (Classification's eval-mode backward, infer.py:
-// one launch per convolution): the tiled kernel as above, the small-channel kernel (small_dgrad_aff<KK>) and the 64 -> 64
-// weights-in-registers kernel (c64_dgrad_aff), each in an instantiation of its own (the training kernels are not touched).  On those
-// two the ReLU mask is optional (act == NULL: dx = bf16(bf16(dgrad(dy)) * alpha[c]), afan_affine_relu_bwd(relu = 0)) and alpha is
-// 16-byte aligned; the tiled kernel answers AFAN_ESHAPE without a mask.  AFAN_ESHAPE where no input-gradient kernel takes the shape.
-int afan_conv_dgrad_affine_any_nhwc_bf16(const void* dy, const void* wt, void* dx, int64_t n, int64_t hi, int64_t wi, int64_t ci,
-                                         int64_t co, int k, int stride, const float* alpha, const void* act, afan_stream_t stream) {
-    if (!alpha) return AFAN_ENULL;
-    return dgrad_impl(dy, nullptr, wt, dx, n, hi, wi, ci, co, k, stride, 1, nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr, 1, stream,
-                      alpha, act, nullptr, nullptr, true);
-}
-
-// The same with a dilation (the eval-mode DeepLab's backward): dx = bf16((act > 0 ? bf16(dgrad(dy, wt; dilation)) : 0) * alpha[c]), bit for
-// bit afan_conv_dgrad_nhwc_bf16(dilation) followed by afan_affine_relu_bwd.  dilation == 1: afan_conv_dgrad_affine_any_nhwc_bf16.
-// dilation > 1: 3x3 at stride 1 on the tiled kernel (the launch afan_conv_dgrad_nhwc_bf16 would choose), whose backward epilogue
-// always masks: act == NULL answers AFAN_ESHAPE there, like every problem no kernel takes (the caller issues the two launches).
-int afan_conv_dgrad_affine_dil_nhwc_bf16(const void* dy, const void* wt, void* dx, int64_t n, int64_t hi, int64_t wi, int64_t ci,
-                                         int64_t co, int k, int stride, int dilation, const float* alpha, const void* act,
-                                         afan_stream_t stream) {
-    if (!alpha) return AFAN_ENULL;
-    return dgrad_impl(dy, nullptr, wt, dx, n, hi, wi, ci, co, k, stride, dilation, nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr, 1,
-                      stream, alpha, act, nullptr, nullptr, true);
+                                     int k, int stride, int dilation, const float* alpha, const void* act, int any_family,
+                                     afan_stream_t stream) {
+    if (!alpha || (!any_family && !act)) return AFAN_ENULL;
+    DgradReq r;
+    r.dilation = dilation; r.aff_alpha = alpha; r.aff_act = act; r.any_family = any_family != 0;
+    return dgrad_impl(dy, wt, dx, n, hi, wi, ci, co, k, stride, stream, r);
 }
 
 // The input gradient that arrives at the OUTPUT of a frozen-BatchNorm residual block (Detection's bottlenecks: out = relu(bn3(conv3) +
@@ -2136,8 +2124,9 @@ int afan_conv_dgrad_dual_nhwc_bf16(const void* dy, const void* wt, void* d3, voi
                                    int64_t co, int k, int stride, const void* addend, const float* alpha, const void* act,
                                    afan_stream_t stream) {
     if (!alpha || !act || !dres) return AFAN_ENULL;
-    return dgrad_impl(dy, nullptr, wt, d3, n, hi, wi, ci, co, k, stride, 1, addend, nullptr, nullptr, 0, nullptr, nullptr, nullptr, 1, stream,
-                      alpha, act, dres);
+    DgradReq r;
+    r.addend = addend; r.aff_alpha = alpha; r.aff_act = act; r.dx2 = dres;
+    return dgrad_impl(dy, wt, d3, n, hi, wi, ci, co, k, stride, stream, r);
 }
 
 // The input gradient of a residual block's two stride-2 branches in ONE launch (Classification/resnet_s.py:52-77, option B):
@@ -2149,8 +2138,10 @@ int afan_conv_dgrad_sc_nhwc_bf16(const void* dy, const void* dy_sc, const void* 
                                  int64_t wi, int64_t ci, int64_t co, const void* bn_x, const float* bn_stats, int bn_relu,
                                  const void* bn_y, float* bn_partials, double* bn_acc, afan_stream_t stream) {
     if (!dy_sc) return AFAN_ENULL;
-    return dgrad_impl(dy, dy_sc, wt10, dx, n, hi, wi, ci, co, 3, 2, 1, nullptr, bn_x, bn_stats, bn_relu, bn_y, bn_partials,
-                      bn_acc, 1, stream);
+    DgradReq r;
+    r.dy_sc = dy_sc;
+    r.bn_x = bn_x; r.bn_stats = bn_stats; r.bn_relu = bn_relu; r.bn_y = bn_y; r.bn_partials = bn_partials; r.bn_acc = bn_acc;
+    return dgrad_impl(dy, wt10, dx, n, hi, wi, ci, co, 3, 2, stream, r);
 }
 // ---- round 5: convolution + train-mode BatchNorm in ONE launch (ConvP::bnf; kernels in afan_conv_bnf.hip) -------------------------
 // The BatchNorm's batch statistics need every tile of the launch, so the epilogue meets the launch's other workgroups at a grid-wide
@@ -2181,8 +2172,9 @@ int afan_conv_fwd_bn_nhwc_bf16(const void* x, const void* w, void* y_raw, void* 
                                const float* sc_bias, float sc_eps, float sc_momentum, float* sc_stats, float* sc_running_mean,
                                float* sc_running_var, int64_t* sc_num_batches, void* barrier, afan_stream_t stream) {
     if ((ksize != 1 && ksize != 3) || dilation < 1 || (ksize == 1 && dilation != 1)) return AFAN_ESHAPE;
-    const int k = ksize, stride = 1, pad = k / 2;
-    int e = check_dims(n, hi, wi, ci, co, k, stride, dilation);
+    const int k = ksize, stride = 1;
+    ConvP p{};
+    const int e = fwd_problem(p, n, hi, wi, ci, co, k, stride, dilation);
     if (e) return e;
     AFAN_TRACE_PROBLEM(0, afan::trace::FWD, n, hi, wi, ci, co, k, stride, dilation);
     if (!x || !w || !y_raw || !y_act || !acc || !stats || !barrier) return AFAN_ENULL;
@@ -2191,36 +2183,17 @@ int afan_conv_fwd_bn_nhwc_bf16(const void* x, const void* w, void* y_raw, void* 
         return AFAN_EALIGN;
     if (sc_raw && (residual || !sc_acc || !sc_stats || !relu)) return AFAN_ESHAPE;
     if (ci % 64 != 0 || co % 64 != 0) return AFAN_ESHAPE;
-    ConvP p{};
-    p.max_pad = dilation;
-    p.x = (const uint16_t*)x; p.w = (const uint16_t*)w; p.y = (uint16_t*)y_raw; p.y2 = (uint16_t*)y_act;
-    p.N = (int)n; p.Hi = (int)hi; p.Wi = (int)wi; p.Ci = (int)ci;
-    p.Ho = (int)hi; p.Wo = (int)wi; p.Co = (int)co;
-    p.in_s = 1; p.out_s = 1; p.w_row_stride = (int)(k * k * ci); p.n_classes = 1;
-    p.shift = shift; p.acc = acc; p.acc_ns = afan_nhwc::acc_slot_count(co);
-    p.groups = 1;
-    ConvClass& c0 = p.cls[0];
-    c0.Hg = p.Ho; c0.Wg = p.Wo; c0.T = k * k;
-    for (int r = 0; r < k; ++r)
-        for (int q = 0; q < k; ++q) {
-            const int t = r * k + q;
-            c0.dh[t] = (r - pad) * dilation; c0.dw[t] = (q - pad) * dilation; c0.wofs[t] = (int)(t * ci);
-        }
+    p.x = (const uint16_t*)x; p.w = (const uint16_t*)w; p.y = (uint16_t*)y_raw;
+    p.shift = shift; p.acc = acc;
     const int64_t M = n * hi * wi;
-    const int pending = afan_nhwc::set_running_updates(1);
-    afan_nhwc::set_running_updates(pending);
-    p.bnf = 1; p.bar = (unsigned*)barrier;
-    p.bnf_w = bn_weight; p.bnf_b = bn_bias; p.bnf_eps = eps; p.bnf_mom = momentum;
-    p.bnf_rmean = running_mean; p.bnf_rvar = running_var; p.bnf_nbt = num_batches; p.bnf_updates = pending;
-    p.bnf_stats = stats; p.bnf_relu = relu ? 1 : 0;
+    set_fwd_bnf(p, FwdBn{y_act, bn_weight, bn_bias, eps, momentum, stats, running_mean, running_var, num_batches, relu, barrier}, M);
     p.bnf_res = (const uint16_t*)(sc_raw ? sc_raw : residual);
-    p.bnf_inv_m = 1.0 / (double)M;
-    p.bnf_unbias = M > 1 ? (float)((double)M / (double)(M - 1)) : 1.0f;
     if (sc_raw) {
         p.bnf_sc.acc = sc_acc; p.bnf_sc.w = sc_weight; p.bnf_sc.b = sc_bias; p.bnf_sc.eps = sc_eps; p.bnf_sc.mom = sc_momentum;
         p.bnf_sc.rmean = sc_running_mean; p.bnf_sc.rvar = sc_running_var; p.bnf_sc.nbt = sc_num_batches; p.bnf_sc.stats = sc_stats;
     }
-    if (small_eligible(p) || afan_c64::eligible(n, hi, wi, ci, co, k, stride)) return AFAN_ESHAPE;
+    // the tiled instantiations only (an atrous 64 -> 64 problem passes here and is declined by dispatch_bnf: 64 output channels)
+    if (fwd_family(p, k, stride, true, true) != FWD_TILED) return AFAN_ESHAPE;
     hipStream_t st = (hipStream_t)stream;
     // (its own label: the launch does the convolution's FLOPs AND the BatchNorm's passes — bench.py prices it separately)
     AFAN_PROF_FLOPS("conv_bn_fwd_kernel", 2.0 * ((double)M * co * (p.bnf_res ? 3 : 2) + (double)M * ci + (double)co * k * k * ci),
@@ -2251,8 +2224,10 @@ int afan_conv_dgrad_bn_nhwc_bf16(const void* dy, const void* wt, void* dx, void*
         b.bsc.x = (const uint16_t*)sc_x; b.bsc.stats = sc_stats; b.bsc.acc = sc_acc; b.bsc.y3 = (uint16_t*)d_sc;
         b.bsc.dw = sc_dweight; b.bsc.db = sc_dbias;
     }
-    return dgrad_impl(dy, nullptr, wt, dx, n, hi, wi, ci, co, ksize, 1, dilation, addend, bn_x, bn_stats, bn_relu, bn_y, nullptr, bn_acc, 1, stream,
-                      nullptr, nullptr, nullptr, &b);
+    DgradReq r;
+    r.dilation = dilation; r.addend = addend; r.bnf = &b;
+    r.bn_x = bn_x; r.bn_stats = bn_stats; r.bn_relu = bn_relu; r.bn_y = bn_y; r.bn_acc = bn_acc;
+    return dgrad_impl(dy, wt, dx, n, hi, wi, ci, co, ksize, 1, stream, r);
 }
 
 // The same for the stride-2 pair form (afan_conv_dgrad_sc_nhwc_bf16: a block's first 3x3 / 2 and its 1x1 / 2 projection, whose input
@@ -2267,8 +2242,10 @@ int afan_conv_dgrad_sc_bn_nhwc_bf16(const void* dy, const void* dy_sc, const voi
     if (ci % 64 != 0 || co % 64 != 0) return AFAN_ESHAPE;
     ConvP b{};
     b.bar = (unsigned*)barrier; b.y2 = (uint16_t*)dres; b.bnf_dw = dweight; b.bnf_db = dbias; b.bnf_accum = accumulate;
-    return dgrad_impl(dy, dy_sc, wt10, dx, n, hi, wi, ci, co, 3, 2, 1, nullptr, bn_x, bn_stats, bn_relu, bn_y, nullptr, bn_acc, 1, stream,
-                      nullptr, nullptr, nullptr, &b);
+    DgradReq r;
+    r.dy_sc = dy_sc; r.bnf = &b;
+    r.bn_x = bn_x; r.bn_stats = bn_stats; r.bn_relu = bn_relu; r.bn_y = bn_y; r.bn_acc = bn_acc;
+    return dgrad_impl(dy, wt10, dx, n, hi, wi, ci, co, 3, 2, stream, r);
 }
 
 // ---- batched KRSC -> CRSK transpose of every convolution weight (dgrad operands), once per SGD step -------------------

@@ -19,9 +19,9 @@ struct Params {
     int bn_relu;
     const uint16_t* bny;
     const uint16_t* addend;
-    // forward only, a separate instantiation: the frozen BatchNorm behind the convolution (afan_conv_fwd_affine_any_nhwc_bf16),
+    // forward only, a separate instantiation: the frozen BatchNorm behind the convolution (afan_conv_fwd_affine_nhwc_bf16 with any_family = 1),
     // y = [relu](bf16(conv) * alpha + beta [+ aff_res]) with aff an afan_affine_coefs block [4][64]; no addend, no sums
-    // input gradient (flip = 1) with aff set, a third instantiation (afan_conv_dgrad_affine_any_nhwc_bf16): aff = the alpha row [64] of
+    // input gradient (flip = 1) with aff set, a third instantiation (afan_conv_dgrad_affine_nhwc_bf16 with any_family = 1): aff = the alpha row [64] of
     // the frozen BatchNorm in front of the convolution, aff_res = its stored output (NULL: no ReLU mask),
     // y = bf16((aff_res > 0 ? bf16(dgrad) : 0) * alpha)
     const float* aff;

@@ -388,13 +388,13 @@ int launch(const Params& p, hipStream_t st) {
     }
 #else
     static const int xcd_pair = [] { const char* v = getenv("AFAN_C64_XCD"); return v ? atoi(v) : 1; }();
-    if (p.aff && p.flip) {                         // input gradient + frozen BatchNorm / ReLU backward (afan_conv_dgrad_affine_any_nhwc_bf16)
+    if (p.aff && p.flip) {                         // input gradient + frozen BatchNorm / ReLU backward (afan_conv_dgrad_affine_nhwc_bf16 with any_family = 1)
         conv3x3_c64_kernel<2><<<grid, THREADS, LDS_BYTES, st>>>(p, tiles, logW, nullptr, xcd_pair);
         AFAN_LAUNCH_CHECK();
         AFAN_TRACE_LAUNCH("c64_dgrad_aff");
         return AFAN_OK;
     }
-    if (p.aff) {                                   // forward with a frozen BatchNorm (afan_conv_fwd_affine_any_nhwc_bf16)
+    if (p.aff) {                                   // forward with a frozen BatchNorm (afan_conv_fwd_affine_nhwc_bf16 with any_family = 1)
         conv3x3_c64_kernel<1><<<grid, THREADS, LDS_BYTES, st>>>(p, tiles, logW, nullptr, xcd_pair);
         AFAN_LAUNCH_CHECK();
         AFAN_TRACE_LAUNCH("c64_fwd_aff");

@@ -29,9 +29,9 @@ typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 constexpr int THREADS = 256;
 constexpr int NB = 32;       // output channels per workgroup column
 
-// AFF = 1: the frozen-BatchNorm epilogue of afan_conv_fwd_affine_any_nhwc_bf16 (ConvP::aff, forward only) in place of the addend
+// AFF = 1: the frozen-BatchNorm epilogue of afan_conv_fwd_affine_nhwc_bf16 with any_family = 1 (ConvP::aff, forward only) in place of the addend
 // and the BatchNorm sums; AFF = 2: the frozen BatchNorm (+ ReLU) BACKWARD on an input gradient's way out
-// (afan_conv_dgrad_affine_any_nhwc_bf16: ConvP::aff = the alpha row, aff_res = the stored activation or NULL).  Separate
+// (afan_conv_dgrad_affine_nhwc_bf16 with any_family = 1: ConvP::aff = the alpha row, aff_res = the stored activation or NULL).  Separate
 // instantiations, so the training kernels' (AFF = 0) code is untouched
 template <int KK, int AFF>   // MFMA k-steps per tap = reduction channels / 16
 __global__ __launch_bounds__(THREADS) void conv_small_kernel(const ConvP pp) {
@@ -246,7 +246,7 @@ int small_launch(const ConvP& p, hipStream_t st) {
     if (gx < 1) gx = 1;
     if (p.groups == 2) gx = (gx + 1) & ~(int64_t)1;            // a workgroup never mixes the two image groups
     dim3 grid((unsigned)gx, (unsigned)p.n_classes, (unsigned)((p.Co + NB - 1) / NB));
-    if (p.aff && p.aff_bwd) {                                  // input gradient + frozen BatchNorm / ReLU backward (afan_conv_dgrad_affine_any_nhwc_bf16)
+    if (p.aff && p.aff_bwd) {                                  // input gradient + frozen BatchNorm / ReLU backward (afan_conv_dgrad_affine_nhwc_bf16 with any_family = 1)
         if (p.Ci == 16) conv_small_kernel<1, 2><<<grid, THREADS, 0, st>>>(p);
         else if (p.Ci == 32) conv_small_kernel<2, 2><<<grid, THREADS, 0, st>>>(p);
         else conv_small_kernel<4, 2><<<grid, THREADS, 0, st>>>(p);
@@ -254,7 +254,7 @@ int small_launch(const ConvP& p, hipStream_t st) {
         AFAN_TRACE_LAUNCH("small_dgrad_aff<%d>", p.Ci == 16 ? 1 : p.Ci == 32 ? 2 : 4);
         return AFAN_OK;
     }
-    if (p.aff) {                                               // forward with a frozen BatchNorm (afan_conv_fwd_affine_any_nhwc_bf16)
+    if (p.aff) {                                               // forward with a frozen BatchNorm (afan_conv_fwd_affine_nhwc_bf16 with any_family = 1)
         if (p.Ci == 16) conv_small_kernel<1, 1><<<grid, THREADS, 0, st>>>(p);
         else if (p.Ci == 32) conv_small_kernel<2, 1><<<grid, THREADS, 0, st>>>(p);
         else conv_small_kernel<4, 1><<<grid, THREADS, 0, st>>>(p);

@@ -89,7 +89,7 @@ struct FwdP {
     const float* aff; int aff_relu;   // AFF only: afan_affine_coefs block [4][Co] of the frozen BatchNorm behind the stem, ReLU flag
 };
 
-// AFF: y = [relu](bf16(conv) * alpha + beta) at the staged store (afan_conv_fwd_affine_any_nhwc_bf16; no residual, no sums) —
+// AFF: y = [relu](bf16(conv) * alpha + beta) at the staged store (afan_conv_fwd_affine_nhwc_bf16 with any_family = 1; no residual, no sums) —
 // its own instantiation, the training kernel's code is untouched
 template <int CG, bool AFF>   // groups of 32 output channels
 __global__ __launch_bounds__(THREADS) void stem_fwd_kernel(const FwdP p) {

@@ -354,7 +354,7 @@ int launch_step_norms(float* x_adv, const void* grad, const float* x_clean, uint
 
 extern "C" {
 
-int afan_version(void) { return 100; }
+int afan_version(void) { return 101; }
 const char* afan_arch(void) { return "gfx950"; }
 
 int afan_pgd_step(float* x_adv, const void* grad, int grad_dtype, const float* x_clean,

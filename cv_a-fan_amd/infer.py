@@ -2,7 +2,7 @@
 main_learnable (through it) and main_inference.
 
 bf16 channels-last models run a fused forward: every convolution is ONE launch with its eval-mode BatchNorm (running
-statistics, a frozen affine) (+ the block's residual) (+ ReLU) in the epilogue (afan_conv_fwd_affine_any_nhwc_bf16; the tiled,
+statistics, a frozen affine) (+ the block's residual) (+ ReLU) in the epilogue (afan_conv_fwd_affine_nhwc_bf16 with any_family = 1; the tiled,
 small-channel, 64 -> 64 and 3-channel-stem kernels all have that form) — bit for bit the eager path's convolution followed by
 its afan_bn_apply.  A projection shortcut's BatchNorm goes through its own convolution's epilogue; the option-A pad shortcut,
 the ResNet-50 max-pool and the classifier head are the eager path's calls.  The ResNet-50 7x7 stem is its im2col followed by

@@ -633,26 +633,6 @@ def bn_train_forward_dual(xa, bna, sta, mom_a, xb, bnb, stb, mom_b):
     return y, stats[0], stats[1]
 
 
-def frozen_bottleneck_fwd(x, planes, stride, ws, ks):
-    """One native call for a frozen-BatchNorm bottleneck's forward (afan_frozen_bottleneck_fwd): ws = (w1, w2, w3, wd | None)
-    KRSC bf16, ks = (k1, k2, k3, kd | None) coefficient blocks.  Returns (out, a1, a2)."""
-    lib = _lib.load()
-    _cl4(x, "x")
-    n, cin, h, w = x.shape
-    ho, wo = (h - 1) // stride + 1, (w - 1) // stride + 1
-    co = 4 * planes
-    cl = torch.channels_last
-    a1 = torch.empty((n, planes, h, w), dtype=torch.bfloat16, device=x.device, memory_format=cl)
-    a2 = torch.empty((n, planes, ho, wo), dtype=torch.bfloat16, device=x.device, memory_format=cl)
-    out = torch.empty((n, co, ho, wo), dtype=torch.bfloat16, device=x.device, memory_format=cl)
-    scratch = _workspace(x, (n * (planes * h * w + 2 * co * ho * wo) + 1) // 2, "fbk_fwd")
-    CALLS["conv_fwd"] += 3 + (ws[3] is not None)
-    check(lib.afan_frozen_bottleneck_fwd(_ptr(x), n, h, w, cin, planes, int(stride), _ptr(ws[0]), _ptr(ws[1]), _ptr(ws[2]), _ptr(ws[3]),
-                                         _ptr(ks[0]), _ptr(ks[1]), _ptr(ks[2]), _ptr(ks[3]), _ptr(scratch), _ptr(a1), _ptr(a2),
-                                         _ptr(out), _stream(x)), "afan_frozen_bottleneck_fwd")
-    return out, a1, a2
-
-
 class FrozenBlockPlan:
     """Everything about one frozen bottleneck at one input shape that does not change between optimizer steps — sizes, scratch
     requirements, the ctypes pointer objects of its weights / transposed weights / coefficient rows / gradient views — gathered
@@ -664,8 +644,10 @@ class FrozenBlockPlan:
 
 
 def frozen_bottleneck_plan(x, planes, stride, ws, ks, wts, als, gws, dilation=1):
-    """dilation: of the block's 3x3 convolution (padding = dilation; > 1 needs stride 1: DeepLab's atrous bottlenecks in eval mode,
-    afan_frozen_bottleneck_*_dil).  dilation = 1 issues the calls it always did."""
+    """One frozen-BatchNorm bottleneck for the one-call sequencers (afan_frozen_bottleneck_fwd / _bwd): ws = (w1, w2, w3, wd | None)
+    KRSC bf16, ks = (k1, k2, k3, kd | None) coefficient blocks, wts = transposed weights, als = alpha rows, gws = fp32 arena gradient
+    views to add into (None entries: not wanted).  dilation: of the block's 3x3 convolution (padding = dilation; > 1 needs stride 1:
+    DeepLab's atrous bottlenecks in eval mode)."""
     lib = _lib.load()
     p = FrozenBlockPlan()
     p.dilation = int(dilation)
@@ -698,23 +680,17 @@ def frozen_bottleneck_fwd_plan(x, p):
     scratch = _workspace(x, p.fwd_scratch, "fbk_fwd")
     CALLS["conv_fwd"] += p.n_fwd
     w, k = p.w_ptrs, p.k_ptrs
-    if p.dilation != 1:
-        check(lib.afan_frozen_bottleneck_fwd_dil(C.c_void_p(x.data_ptr()), p.n, p.h, p.w, p.cin, p.planes, p.stride, p.dilation, w[0], w[1], w[2], w[3],
-                                                 k[0], k[1], k[2], k[3], C.c_void_p(scratch.data_ptr()), C.c_void_p(a1.data_ptr()),
-                                                 C.c_void_p(a2.data_ptr()), C.c_void_p(out.data_ptr()), C.c_void_p(_raw_stream(dev.index))),
-              "afan_frozen_bottleneck_fwd_dil")
-        return out, a1, a2
-    check(lib.afan_frozen_bottleneck_fwd(C.c_void_p(x.data_ptr()), p.n, p.h, p.w, p.cin, p.planes, p.stride, w[0], w[1], w[2], w[3], k[0], k[1], k[2], k[3],
-                                         C.c_void_p(scratch.data_ptr()), C.c_void_p(a1.data_ptr()), C.c_void_p(a2.data_ptr()),
-                                         C.c_void_p(out.data_ptr()), C.c_void_p(_raw_stream(dev.index))), "afan_frozen_bottleneck_fwd")
+    check(lib.afan_frozen_bottleneck_fwd(C.c_void_p(x.data_ptr()), p.n, p.h, p.w, p.cin, p.planes, p.stride, p.dilation, w[0], w[1], w[2], w[3],
+                                         k[0], k[1], k[2], k[3], C.c_void_p(scratch.data_ptr()), C.c_void_p(a1.data_ptr()),
+                                         C.c_void_p(a2.data_ptr()), C.c_void_p(out.data_ptr()), C.c_void_p(_raw_stream(dev.index))),
+          "afan_frozen_bottleneck_fwd")
     return out, a1, a2
 
 
 def frozen_bottleneck_bwd_plan(g, x, a1, a2, out, p, want_dx, pre=None, prev=None):
     """One block's backward.  Inside a stage's chain (det_model._stage_backward): `pre` = (d3, dres), this block's first backward
     step as the block behind it left it (g is then None); `prev` = the plan of the block in front, whose first step this call's
-    last input-gradient launch performs on the way out — returns that block's (d3, dres) instead of dx
-    (afan_frozen_bottleneck_bwd_chain)."""
+    last input-gradient launch performs on the way out — returns that block's (d3, dres) instead of dx."""
     lib = _lib.load()
     scratch = _workspace(x, p.bwd_scratch, "fbk_bwd")
     wws = _workspace(x, p.wgrad_ws, "wgrad") if p.wgrad_ws else None
@@ -726,41 +702,13 @@ def frozen_bottleneck_bwd_plan(g, x, a1, a2, out, p, want_dx, pre=None, prev=Non
         nd3, ndres = torch.empty_like(x), torch.empty_like(x)
     elif want_dx:
         dx = torch.empty_like(x)
-    if p.dilation != 1:
-        check(lib.afan_frozen_bottleneck_bwd_chain_dil(_ptr(g), _ptr(pre[0]) if pre else None, _ptr(pre[1]) if pre else None, C.c_void_p(x.data_ptr()),
-                                                       C.c_void_p(a1.data_ptr()), C.c_void_p(a2.data_ptr()), C.c_void_p(out.data_ptr()), p.n, p.h, p.w,
-                                                       p.cin, p.planes, p.stride, p.dilation, wt[0], wt[1], wt[2], wt[3], al[0], al[1], al[2], al[3],
-                                                       gw[0], gw[1], gw[2], gw[3], _ptr(wws), C.c_void_p(scratch.data_ptr()), _ptr(dx),
-                                                       prev.al_ptrs[2] if prev is not None else None, _ptr(nd3), _ptr(ndres),
-                                                       C.c_void_p(_raw_stream(x.device.index))), "afan_frozen_bottleneck_bwd_chain_dil")
-        return (nd3, ndres) if prev is not None else dx
-    check(lib.afan_frozen_bottleneck_bwd_chain(_ptr(g), _ptr(pre[0]) if pre else None, _ptr(pre[1]) if pre else None, C.c_void_p(x.data_ptr()),
-                                               C.c_void_p(a1.data_ptr()), C.c_void_p(a2.data_ptr()), C.c_void_p(out.data_ptr()), p.n, p.h, p.w, p.cin,
-                                               p.planes, p.stride, wt[0], wt[1], wt[2], wt[3], al[0], al[1], al[2], al[3], gw[0], gw[1], gw[2], gw[3],
-                                               _ptr(wws), C.c_void_p(scratch.data_ptr()), _ptr(dx), prev.al_ptrs[2] if prev is not None else None,
-                                               _ptr(nd3), _ptr(ndres), C.c_void_p(_raw_stream(x.device.index))), "afan_frozen_bottleneck_bwd_chain")
+    check(lib.afan_frozen_bottleneck_bwd(_ptr(g), _ptr(pre[0]) if pre else None, _ptr(pre[1]) if pre else None, C.c_void_p(x.data_ptr()),
+                                         C.c_void_p(a1.data_ptr()), C.c_void_p(a2.data_ptr()), C.c_void_p(out.data_ptr()), p.n, p.h, p.w,
+                                         p.cin, p.planes, p.stride, p.dilation, wt[0], wt[1], wt[2], wt[3], al[0], al[1], al[2], al[3],
+                                         gw[0], gw[1], gw[2], gw[3], _ptr(wws), C.c_void_p(scratch.data_ptr()), _ptr(dx),
+                                         prev.al_ptrs[2] if prev is not None else None, _ptr(nd3), _ptr(ndres),
+                                         C.c_void_p(_raw_stream(x.device.index))), "afan_frozen_bottleneck_bwd")
     return (nd3, ndres) if prev is not None else dx
-
-
-def frozen_bottleneck_bwd(g, x, a1, a2, out, planes, stride, wts, als, gws, want_dx):
-    """The backward of the same block in one native call: wts = transposed weights, als = alpha rows, gws = fp32 arena gradient
-    views to add into (None entries: not wanted).  Returns dx | None."""
-    lib = _lib.load()
-    n, cin, h, w = x.shape
-    co = 4 * planes
-    scratch = _workspace(x, (lib.afan_frozen_bottleneck_bwd_scratch(n, h, w, cin, planes, int(stride)) + 1) // 2, "fbk_bwd")
-    ho, wo = (h - 1) // stride + 1, (w - 1) // stride + 1
-    shapes = ((n, ho, wo, planes, co, 1, 1), (n, h, w, planes, planes, 3, stride), (n, h, w, cin, planes, 1, 1), (n, h, w, cin, co, 1, stride))
-    total = sum(lib.afan_conv_wgrad_workspace_floats(*sh) for sh, gw in zip(shapes, (gws[2], gws[1], gws[0], gws[3])) if gw is not None)
-    wws = _workspace(x, total, "wgrad") if total else None
-    dx = torch.empty_like(x) if want_dx else None
-    CALLS["conv_dgrad"] += 2 + (1 if want_dx else 0) + (1 if (want_dx and wts[3] is not None) else 0)
-    CALLS["conv_wgrad"] += sum(gw is not None for gw in gws)
-    check(lib.afan_frozen_bottleneck_bwd(_ptr(g), _ptr(x), _ptr(a1), _ptr(a2), _ptr(out), n, h, w, cin, planes, int(stride),
-                                         _ptr(wts[0]), _ptr(wts[1]), _ptr(wts[2]), _ptr(wts[3]), _ptr(als[0]), _ptr(als[1]),
-                                         _ptr(als[2]), _ptr(als[3]), _ptr(gws[0]), _ptr(gws[1]), _ptr(gws[2]), _ptr(gws[3]),
-                                         _ptr(wws), _ptr(scratch), _ptr(dx), _stream(x)), "afan_frozen_bottleneck_bwd")
-    return dx
 
 
 def bn_apply(x, mean, invstd, weight, bias, residual=None, relu=False):
@@ -1223,11 +1171,11 @@ def _conv_dgrad_bn_pair(dy, pair, in_hw, bn_x, bn_stats, relu, bn_y, want_dres, 
 
 def conv_fwd_affine(x, w, stride, coefs, residual=None, relu=False, any_kernel=False, dilation=1):
     """[relu](bf16(conv2d(x, w)) * alpha + beta [+ residual]) in ONE launch: a convolution with the frozen BatchNorm behind it in its
-    epilogue.  any_kernel=False (afan_conv_fwd_affine_nhwc_bf16): the tiled kernel's shapes; None where the shape belongs to another
-    kernel (the caller issues conv_fwd + affine_apply: the same bits).  any_kernel=True (afan_conv_fwd_affine_any_nhwc_bf16, the
-    eval forward of infer.py): every forward kernel family of conv_fwd (tiled, small-channel, 64 -> 64 weights-in-registers,
+    epilogue (afan_conv_fwd_affine_nhwc_bf16).  any_kernel=False: the tiled kernel's shapes; None where the shape belongs to another
+    kernel (the caller issues conv_fwd + affine_apply: the same bits).  any_kernel=True (any_family = 1, the eval forward of
+    infer.py): every forward kernel family of conv_fwd (tiled, small-channel, 64 -> 64 weights-in-registers,
     3-channel image stem — the stem without a residual), coefs a 16-byte aligned afan_affine_coefs block; None where no kernel takes
-    the shape.  dilation > 1 (afan_conv_fwd_affine_dil_nhwc_bf16, the eval-mode DeepLab's atrous 3x3 convolutions at stride 1, padding
+    the shape.  dilation > 1 (any_family = 1 too: the eval-mode DeepLab's atrous 3x3 convolutions at stride 1, padding
     = dilation): the tiled kernel; the same bits as conv_fwd(dilation=) + affine_apply."""
     lib = _lib.load()
     _cl4(x, "x"), _cl4(w, "w")
@@ -1237,21 +1185,11 @@ def conv_fwd_affine(x, w, stride, coefs, residual=None, relu=False, any_kernel=F
     pad = dilation * (k // 2)
     ho, wo = (hi + 2 * pad - dilation * (k - 1) - 1) // stride + 1, (wi + 2 * pad - dilation * (k - 1) - 1) // stride + 1
     y = torch.empty((n, co, ho, wo), dtype=torch.bfloat16, device=x.device, memory_format=torch.channels_last)
-    if dilation != 1:
-        name = "afan_conv_fwd_affine_dil_nhwc_bf16"
-        rc = lib.afan_conv_fwd_affine_dil_nhwc_bf16(_ptr(x), _ptr(w), _ptr(y), n, hi, wi, ci, co, k, int(stride), dilation, _ptr(coefs),
-                                                    _ptr(residual), int(bool(relu)), _stream(x))
-        if rc == -3:
-            return None
-        check(rc, name)
-        CALLS["conv_fwd"] += 1
-        return y
-    name = "afan_conv_fwd_affine_any_nhwc_bf16" if any_kernel else "afan_conv_fwd_affine_nhwc_bf16"
-    rc = getattr(lib, name)(_ptr(x), _ptr(w), _ptr(y), n, hi, wi, ci, co, k, int(stride), _ptr(coefs), _ptr(residual),
-                            int(bool(relu)), _stream(x))
+    rc = lib.afan_conv_fwd_affine_nhwc_bf16(_ptr(x), _ptr(w), _ptr(y), n, hi, wi, ci, co, k, int(stride), dilation, _ptr(coefs),
+                                            _ptr(residual), int(bool(relu)), int(any_kernel or dilation != 1), _stream(x))
     if rc == -3:
         return None
-    check(rc, name)
+    check(rc, "afan_conv_fwd_affine_nhwc_bf16")
     CALLS["conv_fwd"] += 1
     return y
 
@@ -1777,11 +1715,11 @@ def maxpool2d_backward(dy, idx, in_shape, k, stride, pad=0, x=None, channels_las
 
 def conv_dgrad_affine(dy, wt, in_hw, stride, alpha, act, any_kernel=False, dilation=1):
     """dx = bf16((act > 0 ? bf16(dgrad(dy, wt)) : 0) * alpha[c]) in ONE launch: an input gradient with the backward of the frozen
-    BatchNorm + ReLU it runs into.  any_kernel=False (afan_conv_dgrad_affine_nhwc_bf16): the tiled kernel's shapes; None where another
+    BatchNorm + ReLU it runs into (afan_conv_dgrad_affine_nhwc_bf16).  any_kernel=False: the tiled kernel's shapes; None where another
     kernel owns the shape (the caller issues conv_dgrad + affine_relu_backward: the same bits).  any_kernel=True
-    (afan_conv_dgrad_affine_any_nhwc_bf16, the eval backward of infer.py): every input-gradient family of conv_dgrad (tiled,
+    (any_family = 1, the eval backward of infer.py): every input-gradient family of conv_dgrad (tiled,
     small-channel, 64 -> 64 weights-in-registers), alpha 16-byte aligned; act=None (no ReLU mask: bf16(bf16(dgrad) * alpha[c])) on
-    the latter two; None where no kernel takes the problem.  dilation > 1 (afan_conv_dgrad_affine_dil_nhwc_bf16: atrous 3x3 at
+    the latter two; None where no kernel takes the problem.  dilation > 1 (any_family = 1 too: atrous 3x3 at
     stride 1): the tiled kernel, which always masks — None without `act`."""
     lib = _lib.load()
     _cl4(dy, "dy"), _cl4(wt, "wt")
@@ -1797,20 +1735,11 @@ def conv_dgrad_affine(dy, wt, in_hw, stride, alpha, act, any_kernel=False, dilat
     if alpha.numel() != ci or (act is not None and tuple(act.shape) != (n, ci, hi, wi)):
         raise ValueError("conv_dgrad_affine: alpha [Ci] and act of dx's shape")
     dx = torch.empty((n, ci, hi, wi), dtype=torch.bfloat16, device=dy.device, memory_format=torch.channels_last)
-    if dilation != 1:
-        name = "afan_conv_dgrad_affine_dil_nhwc_bf16"
-        rc = lib.afan_conv_dgrad_affine_dil_nhwc_bf16(_ptr(dy), _ptr(wt), _ptr(dx), n, hi, wi, ci, co, k, int(stride), dilation, _ptr(alpha),
-                                                      _ptr(act), _stream(dy))
-        if rc == -3:
-            return None
-        check(rc, name)
-        CALLS["conv_dgrad"] += 1
-        return dx
-    name = "afan_conv_dgrad_affine_any_nhwc_bf16" if any_kernel else "afan_conv_dgrad_affine_nhwc_bf16"
-    rc = getattr(lib, name)(_ptr(dy), _ptr(wt), _ptr(dx), n, hi, wi, ci, co, k, int(stride), _ptr(alpha), _ptr(act), _stream(dy))
+    rc = lib.afan_conv_dgrad_affine_nhwc_bf16(_ptr(dy), _ptr(wt), _ptr(dx), n, hi, wi, ci, co, k, int(stride), dilation, _ptr(alpha),
+                                              _ptr(act), int(any_kernel or dilation != 1), _stream(dy))
     if rc == -3:
         return None
-    check(rc, name)
+    check(rc, "afan_conv_dgrad_affine_nhwc_bf16")
     CALLS["conv_dgrad"] += 1
     return dx
 

@@ -836,7 +836,7 @@ class _FrozenBlockFn(torch.autograd.Function):
     the same launches as the layer-by-layer form — three (four) tuned convolutions, three (four) fused affine(+residual)
     (+ReLU) launches forward; affine backward, input gradient and weight gradient per layer backward, the identity shortcut's
     gradient added in the first convolution's dgrad epilogue — but one `Function.apply`, one backward node and ONE native call
-    each way (afan_frozen_bottleneck_fwd / _bwd issue the launches from C++) instead of seven of each: the Detection
+    each way (ops.frozen_bottleneck_fwd_plan / _bwd_plan: afan_frozen_bottleneck_fwd / _bwd issue the launches from C++) instead of seven of each: the Detection
     iteration is bound by Python dispatch (2 600 applies per iteration before this node)."""
 
     @staticmethod

@@ -260,24 +260,18 @@ int afan_conv_fwd_nhwc_bf16(const void* x, const void* w, void* y, int64_t n, in
 
 /* afan_conv_fwd_affine_nhwc_bf16 — a convolution of Detection's frozen-BatchNorm backbone (backbone/resnet101_ori.py:97-119 under
  * model.py:27-35,46-47: every BatchNorm in eval mode) with that BatchNorm (+ the block's residual) (+ ReLU) applied in the epilogue:
- * y = [relu](bf16(conv(x, w)) * alpha + beta [+ residual]); coefs = an afan_affine_coefs block [4][co].  Bit for bit
- * afan_conv_fwd_nhwc_bf16 followed by afan_affine_apply.  AFAN_ESHAPE for shapes the stem / small-channel / 64 -> 64 kernels take. */
+ * y = [relu](bf16(conv(x, w; padding = dilation * (k / 2), dilation)) * alpha + beta [+ residual]); coefs = an afan_affine_coefs
+ * block [4][co].  Bit for bit afan_conv_fwd_nhwc_bf16(dilation) followed by afan_affine_apply.  any_family = 0: the tiled kernel only,
+ * AFAN_ESHAPE for shapes the stem / small-channel / 64 -> 64 kernels take.  any_family = 1 (the eval-mode forwards of Classification
+ * and of Segmentation's DeepLab, backbone/resnet.py:29-32 and _deeplab.py:146-153): at dilation 1 every forward family of
+ * afan_conv_fwd_nhwc_bf16 — the tiled kernel, the small-channel kernel, the 64 -> 64 weights-in-registers kernel and the 3-channel
+ * image stem (ci == 3: no residual, AFAN_ESHAPE with one), each in an instantiation of its own, coefs 16-byte aligned; dilation > 1:
+ * 3x3 at stride 1 on the tiled kernel.  AFAN_ESHAPE where no kernel takes the problem.
+ * (Version 100's afan_conv_fwd_affine_nhwc_bf16 is (dilation 1, any_family 0), its _any entry (1, 1),
+ * its _dil entry (dilation, 1).) */
 int afan_conv_fwd_affine_nhwc_bf16(const void* x, const void* w, void* y, int64_t n, int64_t hi, int64_t wi, int64_t ci, int64_t co,
-                                   int k, int stride, const float* coefs, const void* residual, int relu, afan_stream_t stream);
-/* afan_conv_fwd_affine_any_nhwc_bf16 — the same, on every forward family of afan_conv_fwd_nhwc_bf16 at dilation 1 (Classification's
- * eval-mode forward): the tiled kernel, the small-channel kernel, the 64 -> 64 weights-in-registers kernel and the 3-channel image
- * stem (ci == 3: no residual, AFAN_ESHAPE with one), each in an instantiation of its own; coefs 16-byte aligned.  AFAN_ESHAPE where
- * no forward kernel takes the shape. */
-int afan_conv_fwd_affine_any_nhwc_bf16(const void* x, const void* w, void* y, int64_t n, int64_t hi, int64_t wi, int64_t ci,
-                                       int64_t co, int k, int stride, const float* coefs, const void* residual, int relu,
-                                       afan_stream_t stream);
-/* afan_conv_fwd_affine_dil_nhwc_bf16 — the same with a dilation (Segmentation's eval-mode DeepLab: the atrous 3x3 convolutions of
- * backbone/resnet.py:29-32 and _deeplab.py:146-153 with their BatchNorms): padding = dilation * (k / 2).  dilation == 1:
- * afan_conv_fwd_affine_any_nhwc_bf16.  dilation > 1: 3x3 at stride 1 on the tiled kernel, bit for bit
- * afan_conv_fwd_nhwc_bf16(dilation) followed by afan_affine_apply.  AFAN_ESHAPE where no kernel takes the problem. */
-int afan_conv_fwd_affine_dil_nhwc_bf16(const void* x, const void* w, void* y, int64_t n, int64_t hi, int64_t wi, int64_t ci, int64_t co,
-                                       int k, int stride, int dilation, const float* coefs, const void* residual, int relu,
-                                       afan_stream_t stream);
+                                   int k, int stride, int dilation, const float* coefs, const void* residual, int relu,
+                                   int any_family, afan_stream_t stream);
 /* nb (1..4) forward convolutions on the SAME input x with the SAME output shape in ONE launch: w[b] / y[b] / ksize[b] (1 or 3)
  * / dilation[b] per problem (host arrays; device pointers inside), BatchNorm moments of y[b] around stats_shift[b] into the
  * f64 accumulator block stats_acc[b] (both arrays NULL: no moments).  (1) The atrous branches of ASPP,
@@ -305,24 +299,18 @@ int afan_conv_dgrad_nhwc_bf16(const void* dy, const void* wt, void* dx, int64_t 
 
 /* afan_conv_dgrad_affine_nhwc_bf16 — the input gradient of a convolution whose input came out of a frozen BatchNorm + ReLU
  * (backbone/resnet101_ori.py:97-119 under model.py:27-35,46-47), with that layer's backward applied in the epilogue:
- * dx = bf16((act > 0 ? bf16(dgrad(dy)) : 0) * alpha[c]); alpha = the layer's alpha row [ci], act = its stored output.  Bit for bit
- * afan_conv_dgrad_nhwc_bf16 followed by afan_affine_relu_bwd(relu = 1).  AFAN_ESHAPE where another kernel owns the shape. */
+ * dx = bf16((act > 0 ? bf16(dgrad(dy, wt; dilation)) : 0) * alpha[c]); alpha = the layer's alpha row [ci], act = its stored output.
+ * Bit for bit afan_conv_dgrad_nhwc_bf16(dilation) followed by afan_affine_relu_bwd(relu = 1).  any_family = 0: the tiled kernel only,
+ * act required, AFAN_ESHAPE where another kernel owns the shape.  any_family = 1 (the eval-mode backwards of Classification and of
+ * DeepLab): at dilation 1 the small-channel kernel and the 64 -> 64 weights-in-registers kernel too, in instantiations of their own;
+ * there act may be NULL (no ReLU mask: dx = bf16(bf16(dgrad(dy)) * alpha[c]), afan_affine_relu_bwd(relu = 0)) and alpha is 16-byte
+ * aligned.  The tiled kernel (dilation > 1: 3x3 at stride 1 on it) always masks: AFAN_ESHAPE without act, and where no input-gradient
+ * kernel takes the problem.
+ * (Version 100's afan_conv_dgrad_affine_nhwc_bf16 is (dilation 1, any_family 0), its _any entry (1, 1),
+ * its _dil entry (dilation, 1).) */
 int afan_conv_dgrad_affine_nhwc_bf16(const void* dy, const void* wt, void* dx, int64_t n, int64_t hi, int64_t wi, int64_t ci, int64_t co,
-                                     int k, int stride, const float* alpha, const void* act, afan_stream_t stream);
-/* afan_conv_dgrad_affine_any_nhwc_bf16 — the same, on every input-gradient family of afan_conv_dgrad_nhwc_bf16 at dilation 1
- * (Classification's eval-mode backward): the tiled kernel, the small-channel kernel and the 64 -> 64 weights-in-registers kernel,
- * the latter two in instantiations of their own.  There act may be NULL (no ReLU mask: dx = bf16(bf16(dgrad(dy)) * alpha[c]),
- * afan_affine_relu_bwd(relu = 0)) and alpha is 16-byte aligned; the tiled kernel answers AFAN_ESHAPE without act.  AFAN_ESHAPE where no
- * input-gradient kernel takes the shape. */
-int afan_conv_dgrad_affine_any_nhwc_bf16(const void* dy, const void* wt, void* dx, int64_t n, int64_t hi, int64_t wi, int64_t ci,
-                                         int64_t co, int k, int stride, const float* alpha, const void* act, afan_stream_t stream);
-/* afan_conv_dgrad_affine_dil_nhwc_bf16 — the same with a dilation (the eval-mode DeepLab's backward).  dilation == 1:
- * afan_conv_dgrad_affine_any_nhwc_bf16.  dilation > 1: 3x3 at stride 1 on the tiled kernel, bit for bit
- * afan_conv_dgrad_nhwc_bf16(dilation) followed by afan_affine_relu_bwd(relu = 1); AFAN_ESHAPE without act (that kernel's backward
- * epilogue always masks) and where no kernel takes the problem. */
-int afan_conv_dgrad_affine_dil_nhwc_bf16(const void* dy, const void* wt, void* dx, int64_t n, int64_t hi, int64_t wi, int64_t ci,
-                                         int64_t co, int k, int stride, int dilation, const float* alpha, const void* act,
-                                         afan_stream_t stream);
+                                     int k, int stride, int dilation, const float* alpha, const void* act, int any_family,
+                                     afan_stream_t stream);
 /* The gradient arriving at the OUTPUT of a frozen-BatchNorm residual block with that block's first backward step applied on the way
  * out: g = bf16(bf16(dgrad(dy)) + addend) (addend optional), m = act > 0 ? g : 0, dres = m, d3 = bf16(m * alpha[c]) — bit for bit
  * afan_conv_dgrad_nhwc_bf16(addend) followed by afan_affine_relu_bwd(relu = 1) with both outputs (Detection/backbone/
@@ -579,39 +567,28 @@ int afan_affine_apply(const void* x, const void* residual, void* y, int dtype, i
  * all activations bf16 channels-last; w1 / w2 / w3 / wd KRSC bf16 (wd NULL: identity shortcut), wt*: their CRSK transposes;
  * k*: afan_affine_coefs blocks, al*: their alpha rows.  fwd scratch: n * (planes*h*w + 2 * 4planes*ho*wo) bf16 elements;
  * a1 [n, planes, h, w], a2 [n, planes, ho, wo] are what the backward needs besides x and out.  bwd: gw* (nullable) fp32 KRSC
- * gradients ADDED into; wgrad_ws: the sum of the wanted layers' afan_conv_wgrad_workspace_floats; dx nullable. */
-int afan_frozen_bottleneck_fwd(const void* x, int64_t n, int64_t h, int64_t w, int64_t cin, int64_t planes, int stride,
+ * gradients ADDED into; wgrad_ws: the sum of the wanted layers' afan_conv_wgrad_workspace_floats; dx nullable.
+ * dilation: of the 3x3 convolution (padding = dilation; stride 1 whenever dilation > 1: the atrous bottlenecks of
+ * Segmentation/network/backbone/resnet.py:29-32 in eval mode), which then goes through the affine entries with any_family = 1.
+ * (Version 100's afan_frozen_bottleneck_fwd is dilation 1, its _fwd_dil entry this one.) */
+int afan_frozen_bottleneck_fwd(const void* x, int64_t n, int64_t h, int64_t w, int64_t cin, int64_t planes, int stride, int dilation,
                                const void* w1, const void* w2, const void* w3, const void* wd, const float* k1, const float* k2,
                                const float* k3, const float* kd, void* scratch, void* a1, void* a2, void* out,
                                afan_stream_t stream);
 int64_t afan_frozen_bottleneck_bwd_scratch(int64_t n, int64_t h, int64_t w, int64_t cin, int64_t planes, int stride);
-int afan_frozen_bottleneck_bwd(const void* g, const void* x, const void* a1, const void* a2, const void* out, int64_t n,
-                               int64_t h, int64_t w, int64_t cin, int64_t planes, int stride, const void* wt1, const void* wt2,
-                               const void* wt3, const void* wtd, const float* al1, const float* al2, const float* al3,
-                               const float* ald, float* gw1, float* gw2, float* gw3, float* gwd, float* wgrad_ws, void* scratch,
-                               void* dx, afan_stream_t stream);
-/* The same inside a chain of blocks (a stage: block i + 1's input is block i's output): g NULL -> the first step of this block's
- * backward was done by the block behind it (pre_d3 = bf16(m * al3), pre_dres = m, m = the output's ReLU mask applied to the
- * gradient; pre_dres may be overwritten); dx NULL and prev_al3 given -> that step of the block in front is done HERE, in the
- * epilogue of the last input-gradient launch (afan_conv_dgrad_dual_nhwc_bf16): prev_d3 / prev_dres [n, cin, h, w]. */
-int afan_frozen_bottleneck_bwd_chain(const void* g, void* pre_d3, void* pre_dres, const void* x, const void* a1, const void* a2,
-                                     const void* out, int64_t n, int64_t h, int64_t w, int64_t cin, int64_t planes, int stride,
-                                     const void* wt1, const void* wt2, const void* wt3, const void* wtd, const float* al1, const float* al2,
-                                     const float* al3, const float* ald, float* gw1, float* gw2, float* gw3, float* gwd, float* wgrad_ws,
-                                     void* scratch, void* dx, const float* prev_al3, void* prev_d3, void* prev_dres, afan_stream_t stream);
-/* The two sequencers with the dilation of the 3x3 convolution (padding = dilation; stride 1 whenever dilation > 1: the atrous
- * bottlenecks of Segmentation/network/backbone/resnet.py:29-32 in eval mode).  The 3x3 goes through
- * afan_conv_fwd_affine_dil_nhwc_bf16 / afan_conv_dgrad_affine_dil_nhwc_bf16; dilation 1 = the functions above. */
-int afan_frozen_bottleneck_fwd_dil(const void* x, int64_t n, int64_t h, int64_t w, int64_t cin, int64_t planes, int stride, int dilation,
-                                   const void* w1, const void* w2, const void* w3, const void* wd, const float* k1, const float* k2,
-                                   const float* k3, const float* kd, void* scratch, void* a1, void* a2, void* out,
-                                   afan_stream_t stream);
-int afan_frozen_bottleneck_bwd_chain_dil(const void* g, void* pre_d3, void* pre_dres, const void* x, const void* a1, const void* a2,
-                                         const void* out, int64_t n, int64_t h, int64_t w, int64_t cin, int64_t planes, int stride,
-                                         int dilation, const void* wt1, const void* wt2, const void* wt3, const void* wtd,
-                                         const float* al1, const float* al2, const float* al3, const float* ald, float* gw1, float* gw2,
-                                         float* gw3, float* gwd, float* wgrad_ws, void* scratch, void* dx, const float* prev_al3,
-                                         void* prev_d3, void* prev_dres, afan_stream_t stream);
+/* The backward, alone or inside a chain of blocks (a stage: block i + 1's input is block i's output): g = d(loss)/d(out), or g NULL ->
+ * the first step of this block's backward was done by the block behind it (pre_d3 = bf16(m * al3), pre_dres = m, m = the output's
+ * ReLU mask applied to the gradient; pre_dres may be overwritten; both NULL with g); dx as above, or dx NULL and prev_al3 given ->
+ * that step of the block in front is done HERE, in the epilogue of the last input-gradient launch (afan_conv_dgrad_dual_nhwc_bf16):
+ * prev_d3 / prev_dres [n, cin, h, w] (all three NULL otherwise).
+ * (Version 100's afan_frozen_bottleneck_bwd is (pre_* NULL, dilation 1, prev_* NULL), its _bwd_chain entry dilation 1,
+ * its _bwd_chain_dil entry this one.) */
+int afan_frozen_bottleneck_bwd(const void* g, void* pre_d3, void* pre_dres, const void* x, const void* a1, const void* a2,
+                               const void* out, int64_t n, int64_t h, int64_t w, int64_t cin, int64_t planes, int stride,
+                               int dilation, const void* wt1, const void* wt2, const void* wt3, const void* wtd,
+                               const float* al1, const float* al2, const float* al3, const float* ald, float* gw1, float* gw2,
+                               float* gw3, float* gwd, float* wgrad_ws, void* scratch, void* dx, const float* prev_al3,
+                               void* prev_d3, void* prev_dres, afan_stream_t stream);
 /* nn.AdaptiveAvgPool2d(1) (_deeplab.py:133): y[n,c] = mean over hw (fp32 accumulate); dx = dy / hw broadcast.
  * pooled_f32 != 0: the pooled side (y / dy) is fp32 whatever `dtype` the map has. */
 int afan_avgpool_fwd(const void* x, void* y, int dtype, int layout, int64_t n, int64_t c, int64_t hw, int pooled_f32,

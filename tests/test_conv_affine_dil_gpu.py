@@ -1,5 +1,6 @@
-"""The atrous epilogue forms (afan_conv_fwd_affine_dil_nhwc_bf16, afan_conv_dgrad_affine_dil_nhwc_bf16; ops.conv_fwd_affine /
-conv_dgrad_affine with dilation=) and the frozen bottleneck with an atrous 3x3 (afan_frozen_bottleneck_*_dil).
+"""The atrous epilogue forms (afan_conv_fwd_affine_nhwc_bf16, afan_conv_dgrad_affine_nhwc_bf16 at dilation > 1, any_family = 1;
+ops.conv_fwd_affine / conv_dgrad_affine with dilation=) and the frozen bottleneck with an atrous 3x3 (afan_frozen_bottleneck_fwd / _bwd
+with dilation > 1).
 
 Two checks per problem:
   * elementwise against float64, with tests/test_conv_pinned_gpu.py's pin and its constant: the convolution's bf16 result r is the
@@ -8,7 +9,7 @@ Two checks per problem:
     between the epilogue of the window's two ends, and equals the epilogue of RNE(float64) except at a few elements;
   * torch.equal against the two launches the form stands for (conv_fwd(dilation=) + affine_apply; conv_dgrad(dilation=) +
     affine_relu_backward): the library's definition of an epilogue form.
-At dilation 1 the entries are the _any entries.  Without a ReLU mask the tiled kernel has no input-gradient epilogue (its backward
+At dilation 1 any_family decides which kernel families answer.  Without a ReLU mask the tiled kernel has no input-gradient epilogue (its backward
 epilogue always masks): dilation > 1 with act=None declines, launching nothing, and the two launches are what is pinned there.
 The argument errors need no GPU (host pointers, nothing is launched)."""
 import ctypes
@@ -122,30 +123,52 @@ def test_dgrad_affine_dil(pkg, gpu, h, w, d, ci, co):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("ci,co,k,st", [(64, 64, 3, 1), (128, 64, 3, 1), (64, 256, 3, 2), (64, 32, 3, 1), (256, 64, 1, 1)])
-def test_dilation_one_is_the_any_entry(pkg, gpu, ci, co, k, st):
-    """dilation = 1 delegates: the same bits as the _any entries on every kernel family (64 -> 64 weights-in-registers, tiled,
-    stride 2, small-channel, 1x1), with and without the ReLU mask where that family has the unmasked form."""
+def test_dilation_one_any_family(pkg, gpu, ci, co, k, st):
+    """dilation = 1, both directions: on a shape the tiled kernel takes, any_family = 0 and 1 give identical bits; on a shape of
+    another family (here the small-channel kernel) any_family = 0 answers AFAN_ESHAPE where 1 launches.  Without the ReLU mask
+    any_family = 1 is the entry the ops wrapper calls (the tiled kernel declines there), any_family = 0 asks for the mask."""
     lib = pkg._lib.load()
     g = torch.Generator(device=gpu).manual_seed(7 + ci + co)
     x, wt = P._cl(P._gauss((N, ci, 17, 19), 1.0, g, gpu)), P._cl(P._gauss((co, ci, k, k), (k * k * ci) ** -0.5, g, gpu))
     coefs, alpha = _coefs(pkg, gpu, g, co), _coefs(pkg, gpu, g, ci)[2]
     ho, wo = P._out_hw(17, 19, k, st, 1)
     res = P._cl(P._gauss((N, co, ho, wo), 1.0, g, gpu))
-    want = pkg.ops.conv_fwd_affine(x, wt, st, coefs, res, True, any_kernel=True)
-    got = torch.empty_like(want)
-    rc = lib.afan_conv_fwd_affine_dil_nhwc_bf16(x.data_ptr(), wt.data_ptr(), got.data_ptr(), N, 17, 19, ci, co, k, st, 1, coefs.data_ptr(),
-                                                res.data_ptr(), 1, pkg.ops._stream(x))
-    assert rc == 0 and torch.equal(got.view(torch.int16), want.view(torch.int16))
-    dy, act = P._cl(P._gauss((N, co, ho, wo), 1.0, g, gpu)), P._cl(P._gauss((N, ci, 17, 19), 1.0, g, gpu))
-    for a in (act, None):
-        want = pkg.ops.conv_dgrad_affine(dy, P._wt(wt), (17, 19), st, alpha, a, any_kernel=True)
-        got = torch.empty((N, ci, 17, 19), dtype=torch.bfloat16, device=gpu).contiguous(memory_format=CL)
-        rc = lib.afan_conv_dgrad_affine_dil_nhwc_bf16(dy.data_ptr(), P._wt(wt).data_ptr(), got.data_ptr(), N, 17, 19, ci, co, k, st, 1,
-                                                      alpha.data_ptr(), None if a is None else a.data_ptr(), pkg.ops._stream(dy))
-        if want is None:
-            assert rc == -3                                          # (the tiled kernel without a mask: both decline)
+    tiled_shape = not (ci == 64 and co == 32)                        # (64 -> 64 at 17 x 19 is not the weights-in-registers kernel's: W = 19)
+
+    def check(call, shape, want, what):
+        """call(any_family, out) -> rc; want: the ops wrapper's result for any_kernel=True"""
+        outs = [torch.empty(shape, dtype=torch.bfloat16, device=gpu).contiguous(memory_format=CL) for _ in range(2)]
+        with pkg.ops.conv_trace() as tr:
+            rc1 = call(1, outs[1])
+        assert rc1 == 0 and torch.equal(outs[1].view(torch.int16), want.view(torch.int16)), what
+        assert len(tr.records) == 1 and tr.records[0]["kernel"].startswith("igemm_") == tiled_shape, (what, P._kernels(tr))
+        with pkg.ops.conv_trace() as tr:
+            rc0 = call(0, outs[0])
+        if tiled_shape:
+            assert rc0 == 0 and torch.equal(outs[0].view(torch.int16), outs[1].view(torch.int16)), f"{what}: any_family = 0 differs from 1"
         else:
-            assert rc == 0 and torch.equal(got.view(torch.int16), want.view(torch.int16))
+            assert rc0 == -3 and tr.records == [], f"{what}: any_family = 0 on another family's shape"
+
+    check(lambda af, out: lib.afan_conv_fwd_affine_nhwc_bf16(x.data_ptr(), wt.data_ptr(), out.data_ptr(), N, 17, 19, ci, co, k, st, 1,
+                                                             coefs.data_ptr(), res.data_ptr(), 1, af, pkg.ops._stream(x)),
+          (N, co, ho, wo), pkg.ops.conv_fwd_affine(x, wt, st, coefs, res, True, any_kernel=True), f"fwd {ci}->{co} k{k} s{st}")
+    dy, act = P._cl(P._gauss((N, co, ho, wo), 1.0, g, gpu)), P._cl(P._gauss((N, ci, 17, 19), 1.0, g, gpu))
+    wtt = P._wt(wt)
+
+    def dgrad(af, out, a):
+        return lib.afan_conv_dgrad_affine_nhwc_bf16(dy.data_ptr(), wtt.data_ptr(), out.data_ptr(), N, 17, 19, ci, co, k, st, 1,
+                                                    alpha.data_ptr(), None if a is None else a.data_ptr(), af, pkg.ops._stream(dy))
+
+    check(lambda af, out: dgrad(af, out, act), (N, ci, 17, 19),
+          pkg.ops.conv_dgrad_affine(dy, wtt, (17, 19), st, alpha, act, any_kernel=True), f"dgrad {ci}<-{co} k{k} s{st}")
+    want = pkg.ops.conv_dgrad_affine(dy, wtt, (17, 19), st, alpha, None, any_kernel=True)
+    got = torch.empty((N, ci, 17, 19), dtype=torch.bfloat16, device=gpu).contiguous(memory_format=CL)
+    rc = dgrad(1, got, None)
+    if want is None:
+        assert rc == -3 and tiled_shape                              # (the tiled kernel without a mask declines)
+    else:
+        assert rc == 0 and torch.equal(got.view(torch.int16), want.view(torch.int16))
+    assert dgrad(0, got, None) == -4                                 # (any_family = 0: the mask is required)
 
 
 @pytest.mark.gpu
@@ -195,25 +218,25 @@ def test_argument_errors_without_gpu(pkg):
     p = ctypes.cast(buf, ctypes.c_void_p)
     odd = ctypes.c_void_p(p.value + 2)
     ESHAPE, ENULL, EALIGN = -3, -4, -2
-    fwd, dgr = lib.afan_conv_fwd_affine_dil_nhwc_bf16, lib.afan_conv_dgrad_affine_dil_nhwc_bf16
-    assert fwd(p, p, p, 1, 8, 8, 256, 256, 3, 2, 2, p, None, 1, None) == ESHAPE          # dilation needs stride 1
-    assert fwd(p, p, p, 1, 8, 8, 256, 256, 1, 1, 2, p, None, 1, None) == ESHAPE          # ... and a 3x3
-    assert fwd(p, p, p, 1, 8, 8, 256, 256, 3, 1, 0, p, None, 1, None) == ESHAPE
-    assert fwd(p, p, p, 1, 8, 8, 20, 256, 3, 1, 2, p, None, 1, None) == ESHAPE           # channels no kernel takes
-    assert fwd(p, p, p, 1, 8, 8, 32, 64, 3, 1, 2, p, None, 1, None) == ESHAPE            # the small-channel kernel has no atrous form
-    assert fwd(None, p, p, 1, 8, 8, 256, 256, 3, 1, 2, p, None, 1, None) == ENULL
-    assert fwd(p, p, p, 1, 8, 8, 256, 256, 3, 1, 2, None, None, 1, None) == ENULL        # coefs
-    assert fwd(odd, p, p, 1, 8, 8, 256, 256, 3, 1, 2, p, None, 1, None) == EALIGN
-    assert fwd(p, p, p, 1, 8, 8, 256, 256, 3, 1, 2, p, odd, 1, None) == EALIGN           # residual
-    assert fwd(p, p, p, 1, 8, 8, 256, 256, 3, 1, 1, None, None, 1, None) == ENULL        # dilation 1: the _any entry's answers
-    assert dgr(p, p, p, 1, 8, 8, 256, 256, 3, 2, 2, p, p, None) == ESHAPE
-    assert dgr(p, p, p, 1, 8, 8, 256, 256, 1, 1, 2, p, p, None) == ESHAPE
-    assert dgr(p, p, p, 1, 8, 8, 256, 256, 3, 1, 2, None, p, None) == ENULL              # alpha
-    assert dgr(None, p, p, 1, 8, 8, 256, 256, 3, 1, 2, p, p, None) == ENULL
-    assert dgr(p, odd, p, 1, 8, 8, 256, 256, 3, 1, 2, p, p, None) == EALIGN
-    assert dgr(p, p, p, 1, 8, 8, 256, 256, 3, 1, 2, p, None, None) == ESHAPE             # no mask: the tiled kernel always masks
-    assert dgr(p, p, p, 1, 8, 8, 256, 256, 3, 1, 2, p, odd, None) == ESHAPE              # a misaligned mask, as in the _any entry
-    bf, bb = lib.afan_frozen_bottleneck_fwd_dil, lib.afan_frozen_bottleneck_bwd_chain_dil
+    fwd, dgr = lib.afan_conv_fwd_affine_nhwc_bf16, lib.afan_conv_dgrad_affine_nhwc_bf16          # (any_family = 1 throughout)
+    assert fwd(p, p, p, 1, 8, 8, 256, 256, 3, 2, 2, p, None, 1, 1, None) == ESHAPE       # dilation needs stride 1
+    assert fwd(p, p, p, 1, 8, 8, 256, 256, 1, 1, 2, p, None, 1, 1, None) == ESHAPE       # ... and a 3x3
+    assert fwd(p, p, p, 1, 8, 8, 256, 256, 3, 1, 0, p, None, 1, 1, None) == ESHAPE
+    assert fwd(p, p, p, 1, 8, 8, 20, 256, 3, 1, 2, p, None, 1, 1, None) == ESHAPE        # channels no kernel takes
+    assert fwd(p, p, p, 1, 8, 8, 32, 64, 3, 1, 2, p, None, 1, 1, None) == ESHAPE         # the small-channel kernel has no atrous form
+    assert fwd(None, p, p, 1, 8, 8, 256, 256, 3, 1, 2, p, None, 1, 1, None) == ENULL
+    assert fwd(p, p, p, 1, 8, 8, 256, 256, 3, 1, 2, None, None, 1, 1, None) == ENULL     # coefs
+    assert fwd(odd, p, p, 1, 8, 8, 256, 256, 3, 1, 2, p, None, 1, 1, None) == EALIGN
+    assert fwd(p, p, p, 1, 8, 8, 256, 256, 3, 1, 2, p, odd, 1, 1, None) == EALIGN        # residual
+    assert fwd(p, p, p, 1, 8, 8, 256, 256, 3, 1, 1, None, None, 1, 1, None) == ENULL     # dilation 1: the same answers
+    assert dgr(p, p, p, 1, 8, 8, 256, 256, 3, 2, 2, p, p, 1, None) == ESHAPE
+    assert dgr(p, p, p, 1, 8, 8, 256, 256, 1, 1, 2, p, p, 1, None) == ESHAPE
+    assert dgr(p, p, p, 1, 8, 8, 256, 256, 3, 1, 2, None, p, 1, None) == ENULL           # alpha
+    assert dgr(None, p, p, 1, 8, 8, 256, 256, 3, 1, 2, p, p, 1, None) == ENULL
+    assert dgr(p, odd, p, 1, 8, 8, 256, 256, 3, 1, 2, p, p, 1, None) == EALIGN
+    assert dgr(p, p, p, 1, 8, 8, 256, 256, 3, 1, 2, p, None, 1, None) == ESHAPE          # no mask: the tiled kernel always masks
+    assert dgr(p, p, p, 1, 8, 8, 256, 256, 3, 1, 2, p, odd, 1, None) == ESHAPE           # a misaligned mask, as at dilation 1
+    bf, bb = lib.afan_frozen_bottleneck_fwd, lib.afan_frozen_bottleneck_bwd
     assert bf(p, 1, 9, 9, 256, 64, 2, 2, p, p, p, p, p, p, p, p, p, p, p, p, None) == ESHAPE         # atrous 3x3: stride 1
     assert bf(p, 1, 9, 9, 256, 64, 1, 0, p, p, p, None, p, p, p, None, p, p, p, p, None) == ESHAPE
     assert bf(None, 1, 9, 9, 256, 64, 1, 2, p, p, p, None, p, p, p, None, p, p, p, p, None) == ENULL

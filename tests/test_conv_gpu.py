@@ -550,7 +550,7 @@ def test_wgrad_multi_equals_separate_launches(pkg, gpu, shapes):
                                    (1, 512, 2048, 38, 57, 1, 2), (128, 512, 512, 7, 7, 3, 1), (3, 64, 256, 20, 24, 1, 1)])
 @pytest.mark.parametrize("res,relu", [(False, True), (True, True), (False, False)])
 def test_conv_with_frozen_batchnorm_epilogue_equals_two_launches(pkg, gpu, shape, res, relu):
-    """afan_conv_fwd_affine_nhwc_bf16 (Detection's frozen bottlenecks: convolution + BatchNorm(eval) (+ residual) (+ ReLU) in one
+    """afan_conv_fwd_affine_nhwc_bf16, any_family = 0 (Detection's frozen bottlenecks: convolution + BatchNorm(eval) (+ residual) (+ ReLU) in one
     launch) against the convolution launch followed by afan_affine_apply: the same bits."""
     n, ci, co, h, w, k, st = shape
     g = torch.Generator().manual_seed(ci + co + k)
@@ -578,7 +578,7 @@ def test_conv_with_frozen_batchnorm_epilogue_declines_other_kernels_shapes(pkg, 
 @pytest.mark.parametrize("shape", [(1, 256, 1024, 38, 57, 1, 1), (1, 256, 256, 38, 57, 3, 1), (2, 512, 512, 30, 41, 3, 2), (128, 512, 2048, 7, 7, 1, 1),
                                    (1, 128, 128, 75, 113, 3, 2), (3, 64, 256, 20, 24, 1, 1)])
 def test_dgrad_with_frozen_batchnorm_backward_epilogue_equals_two_launches(pkg, gpu, shape):
-    """afan_conv_dgrad_affine_nhwc_bf16 (an input gradient + the backward of the frozen BatchNorm + ReLU in front of that convolution
+    """afan_conv_dgrad_affine_nhwc_bf16, any_family = 0 (an input gradient + the backward of the frozen BatchNorm + ReLU in front of that convolution
     in one launch, stride 1 and the four parity classes of stride 2) against afan_conv_dgrad_nhwc_bf16 followed by
     afan_affine_relu_bwd: the same bits."""
     n, ci, co, h, w, k, st = shape

@@ -437,7 +437,7 @@ def test_frozen_bottleneck_node_equals_layer_by_layer_path(pkg, gpu):
 
 def test_stage_backward_chain_equals_block_by_block(pkg, gpu):
     """det_model._stage_backward hands block i's first backward step (the gradient masked by its output, once plain and once times
-    the last BatchNorm's alpha) to the epilogue of block i + 1's last input-gradient launch (afan_frozen_bottleneck_bwd_chain);
+    the last BatchNorm's alpha) to the epilogue of block i + 1's last input-gradient launch (afan_frozen_bottleneck_bwd's pre_* / prev_* arguments);
     with one autograd node per block (`_FrozenStageFn.ON = False`) every block issues its own launch for it.  Same bits: the four
     losses of a training forward, the image gradient and every parameter gradient."""
     g = golden("det_frcnn_r101")

@@ -1,5 +1,5 @@
 """The frozen BatchNorm (+ ReLU) backward epilogue on the small-channel and 64 -> 64 weights-in-registers input-gradient kernels
-(afan_conv_dgrad_affine_any_nhwc_bf16, ops.conv_dgrad_affine(any_kernel=True)): bit for bit afan_conv_dgrad_nhwc_bf16 followed by
+(afan_conv_dgrad_affine_nhwc_bf16 with any_family = 1, ops.conv_dgrad_affine(any_kernel=True)): bit for bit afan_conv_dgrad_nhwc_bf16 followed by
 afan_affine_relu_bwd, on an instantiation of its own.  afan_conv_dgrad_affine_nhwc_bf16 keeps to the tiled kernel's shapes."""
 import pytest
 import torch

@@ -1,5 +1,5 @@
 """The frozen-BatchNorm epilogue on the small-channel, 64 -> 64 weights-in-registers and 3-channel stem kernels
-(afan_conv_fwd_affine_any_nhwc_bf16, ops.conv_fwd_affine(any_kernel=True)): bit for bit the convolution launch followed by
+(afan_conv_fwd_affine_nhwc_bf16 with any_family = 1, ops.conv_fwd_affine(any_kernel=True)): bit for bit the convolution launch followed by
 afan_affine_apply, on the kernel instantiation of its own.  afan_conv_fwd_affine_nhwc_bf16 keeps to the tiled kernel's shapes."""
 import pytest
 import torch
