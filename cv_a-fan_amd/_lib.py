@@ -136,6 +136,8 @@ SIGNATURES = {
     "afan_linear_pair_wgrad_f32": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _l, _l, _l, _l, _p, _p]),
     "afan_proposal_rows": (_i, [_p, _l, _p, _l, _p, _l, _p, _p, _p]),
     "afan_labels_limit": (_i, [_p, _l, _l, _p, _l, _p]),
+    "afan_rpn_proposals_workspace_bytes": (_l, [_l, _l]),
+    "afan_rpn_proposals": (_i, [_p, _p, _l, _l, _l, _f, _l, _p, _p, _p, _p]),
     "afan_det_loss_bwd": (_i, [_p, _p, _p, _p, _p, _p, _l, _l, _l, _l, _l, _p, _p, _p]),
     "afan_det_class_nms_supported": (_i, [_l, _l]),
     "afan_det_class_nms": (_i, [_p, _p, _p, _p, _l, _l, _l, _f, _f, _f, _f, _p, _p, _p, _p]),

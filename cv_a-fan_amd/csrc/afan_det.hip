@@ -61,11 +61,25 @@ constexpr int SC_D = AFAN_SC_D;
 // tile into bandT[COLUMN block][k = column block - row block: 0 = diagonal, 1..SC_D][column] — the comparison's wave-wide ballot
 // IS the column's word; everything the scan needs to settle column block j against the SC_D blocks before it is one contiguous
 // (SC_D + 1) x 512 bytes — and no row form: the scan reads rows only of the tiles further right.
+//
+// BATCHED (afan_rpn_proposals): blockIdx.z is the list — an image of the batch — and every pointer moves to that list's boxes,
+// order, mask and band tiles by the strides of ListStride before anything else happens; the flags are kept by POSITION in the
+// order (the caller wants the survivors in score order, not their original indices) and the diagonal tiles' waves zero them,
+// which saves the memset.  The single-list instantiation ignores the strides: the same arithmetic as before they existed.
+struct ListStride { int64_t boxes, order, mask, band, flag; };
+
+template <bool BATCHED>
 __global__ __launch_bounds__(W64) void nms_mask_kernel(const float* __restrict__ boxes, const int64_t* __restrict__ order, int n,
                                                        float thresh, int inclusive, unsigned long long* __restrict__ mask,
-                                                       unsigned long long* __restrict__ bandT, int col_blocks) {
+                                                       unsigned long long* __restrict__ bandT, int col_blocks,
+                                                       uint8_t* __restrict__ kept_flag, ListStride ls) {
     const int rb = blockIdx.y, cb = blockIdx.x;
     if (cb < rb) return;
+    if (BATCHED) {
+        const int64_t z = blockIdx.z;
+        boxes += z * ls.boxes; order += z * ls.order; mask += z * ls.mask; bandT += z * ls.band; kept_flag += z * ls.flag;
+        if (rb == cb && rb * W64 + (int)threadIdx.x < n) kept_flag[rb * W64 + threadIdx.x] = 0;
+    }
     const int row_size = min(n - rb * W64, W64), col_size = min(n - cb * W64, W64);
     __shared__ __attribute__((aligned(16))) float cbox[W64 * 4];
     __shared__ float carea[W64];
@@ -157,12 +171,19 @@ __device__ __forceinline__ unsigned long long to_scalar(unsigned long long v) {
 // no s_waitcnt between them, the round trips overlap.
 #define LDS_ORDER() asm volatile("" ::: "memory")
 
+// BATCHED: one workgroup per list (blockIdx.x), each on its own mask, band tiles and flags — and its own LDS: nothing crosses
+// workgroups, the three roles and their hand-overs are those of the single list.
+template <bool BATCHED>
 __global__ __launch_bounds__(W64 * SCAN_WAVES) void nms_scan_kernel(const unsigned long long* __restrict__ mask,
                                                                     const unsigned long long* __restrict__ bandT,
                                                                     const int64_t* __restrict__ order, int n, int col_blocks,
-                                                                    uint8_t* __restrict__ kept_flag, int max_keep) {
+                                                                    uint8_t* __restrict__ kept_flag, int max_keep, ListStride ls) {
     extern __shared__ unsigned long long removed[];
     __shared__ ScanShared S;
+    if (BATCHED) {
+        const int64_t z = blockIdx.x;
+        mask += z * ls.mask; bandT += z * ls.band; kept_flag += z * ls.flag;
+    }
     const int lane = threadIdx.x & (W64 - 1), wave = __builtin_amdgcn_readfirstlane(threadIdx.x / W64);
     for (int j = threadIdx.x; j < col_blocks; j += W64 * SCAN_WAVES) removed[j] = 0;
     if (threadIdx.x < SC_R) S.pf_ready[threadIdx.x] = 0;
@@ -318,7 +339,7 @@ __global__ __launch_bounds__(W64 * SCAN_WAVES) void nms_scan_kernel(const unsign
             if (lane == 0) lds_release(&S.work_done[wi], p + 1);
             // the flags last: the release above must not wait for these stores
             const int size = min(n - p * W64, W64);
-            if (lane < size && ((keep >> lane) & 1ULL)) kept_flag[order[p * W64 + lane]] = 1;
+            if (lane < size && ((keep >> lane) & 1ULL)) kept_flag[BATCHED ? (int64_t)(p * W64 + lane) : order[p * W64 + lane]] = 1;
         }
     }
 }
@@ -344,6 +365,35 @@ __global__ __launch_bounds__(CP_THREADS) void nms_compact_kernel(const uint8_t* 
     for (int i = lo; i < hi; ++i)
         if (kept_flag[i]) keep_out[pos++] = i;
     if (threadIdx.x == CP_THREADS - 1) count_out[0] = sums[threadIdx.x];
+}
+
+// The proposal layer's hand-over for every image of the batch (grid = images): the flags are by position in the score order, so
+// the prefix sum ranks the survivors by score; rows[b][r] = boxes[b][order[b][position of survivor r]] for r < min(count, P),
+// zero rows behind them, kept[b] = min(count, P) — what nms_compact_kernel + afan_proposal_rows leave for one image.
+__global__ __launch_bounds__(CP_THREADS) void rpn_rows_kernel(const uint8_t* __restrict__ kept_flag, const float4* __restrict__ boxes,
+                                                              const int64_t* __restrict__ order, int n, ListStride ls, int64_t P,
+                                                              float4* __restrict__ rows, int64_t* __restrict__ kept) {
+    __shared__ int sums[CP_THREADS];
+    const int64_t z = blockIdx.x;
+    kept_flag += z * ls.flag; boxes += z * (ls.boxes / 4); order += z * ls.order; rows += z * P;
+    const int per = (n + CP_THREADS - 1) / CP_THREADS;
+    const int lo = min((int)threadIdx.x * per, n), hi = min(lo + per, n);
+    int c = 0;
+    for (int i = lo; i < hi; ++i) c += kept_flag[i] ? 1 : 0;
+    sums[threadIdx.x] = c;
+    __syncthreads();
+    for (int o = 1; o < CP_THREADS; o <<= 1) {
+        const int v = (int)threadIdx.x >= o ? sums[threadIdx.x - o] : 0;
+        __syncthreads();
+        sums[threadIdx.x] += v;
+        __syncthreads();
+    }
+    int64_t pos = sums[threadIdx.x] - c;
+    for (int i = lo; i < hi && pos < P; ++i)
+        if (kept_flag[i]) rows[pos++] = boxes[order[i]];
+    const int64_t total = sums[CP_THREADS - 1], cnt = total < P ? total : P;
+    for (int64_t j = cnt + threadIdx.x; j < P; j += CP_THREADS) rows[j] = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (threadIdx.x == 0) kept[z] = cnt;
 }
 
 // ---- ROIAlign ---------------------------------------------------------------------------------------------------------------
@@ -763,16 +813,68 @@ static int nms_impl(const float* boxes, const int64_t* order, int64_t n, float t
     if (e != hipSuccess) return (int)e;
     AFAN_PROF("nms_kernel", 16.0 * n + 8.0 * n * cb, st);
     unsigned long long* bandT = (unsigned long long*)(flag + ((n + 7) & ~(int64_t)7));
-    nms_mask_kernel<<<dim3(cb, cb), W64, 0, st>>>(boxes, order, (int)n, threshold, inclusive, mask, bandT, cb);
+    nms_mask_kernel<false><<<dim3(cb, cb), W64, 0, st>>>(boxes, order, (int)n, threshold, inclusive, mask, bandT, cb, flag, ListStride{});
     AFAN_LAUNCH_CHECK();
     const int mk = (int)(max_keep > 0x7fffffffLL ? 0 : max_keep);
     if ((size_t)cb * 8 > 8 * 1024) {                               // the static ring + removed[] pass the default 64 KB of LDS
-        static const hipError_t attr = hipFuncSetAttribute((const void*)nms_scan_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
+        static const hipError_t attr = hipFuncSetAttribute((const void*)nms_scan_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
         if (attr != hipSuccess) return (int)attr;
     }
-    nms_scan_kernel<<<1, W64 * SCAN_WAVES, (size_t)cb * 8, st>>>(mask, bandT, order, (int)n, cb, flag, mk);
+    nms_scan_kernel<false><<<1, W64 * SCAN_WAVES, (size_t)cb * 8, st>>>(mask, bandT, order, (int)n, cb, flag, mk, ListStride{});
     AFAN_LAUNCH_CHECK();
     nms_compact_kernel<<<1, CP_THREADS, 0, st>>>(flag, (int)n, keep_out, count_out);
+    AFAN_LAUNCH_CHECK();
+    return AFAN_OK;
+}
+
+// ---- the proposal layer's NMS for all images of a batch ------------------------------------------------------------------
+// Per image: mask words (n x cb), band tiles, flags — each block 8-byte aligned; the images' blocks lie one behind another.
+constexpr int RPN_MAX_B = 64;
+static ListStride rpn_strides(int64_t a, int64_t n) {
+    const int64_t cb = (n + W64 - 1) / W64;
+    return ListStride{a * 4, a, n * cb, cb * (SC_D + 1) * W64, (n + 7) & ~(int64_t)7};
+}
+
+int64_t afan_rpn_proposals_workspace_bytes(int64_t b, int64_t n) {
+    if (b <= 0 || n <= 0) return 0;
+    const ListStride ls = rpn_strides(0, n);
+    return b * (ls.mask * 8 + ls.band * 8 + ls.flag);
+}
+
+// boxes [B, A, 4] fp32 (decoded and clipped), order [B, A] int64 = each image's indices by DESCENDING score.  Per image the
+// candidates are boxes[b][order[b][i]], i < min(pre_n, a); greedy NMS at IoU > threshold with afan_nms_top's early stop at top_n
+// survivors; padded [B, top_n, 4]: the first min(count, top_n) survivors in score order, zero rows behind; kept [B] their number.
+// Three launches whatever B is (B <= 64).  ws: afan_rpn_proposals_workspace_bytes(b, min(pre_n, a)), 8-byte aligned.
+int afan_rpn_proposals(const float* boxes, const int64_t* order, int64_t b, int64_t a, int64_t pre_n, float threshold, int64_t top_n,
+                       void* ws, float* padded, int64_t* kept, afan_stream_t stream) {
+    if (b < 0 || b > RPN_MAX_B || a < 0 || pre_n < 0 || top_n < 0 || top_n > 0x7fffffffLL) return AFAN_ESHAPE;
+    const int64_t n = pre_n < a ? pre_n : a;
+    if (n > (1 << 24)) return AFAN_ESHAPE;
+    if (b == 0) return AFAN_OK;
+    if (!kept || (top_n > 0 && !padded)) return AFAN_ENULL;
+    if (!aligned(padded, 16)) return AFAN_EALIGN;
+    hipStream_t st = (hipStream_t)stream;
+    const int cb = (int)((n + W64 - 1) / W64);
+    if ((size_t)cb * 8 > 64 * 1024) return AFAN_ESHAPE;
+    const ListStride ls = rpn_strides(a, n);
+    uint8_t* flag = nullptr;
+    if (n > 0) {
+        if (!boxes || !order || !ws) return AFAN_ENULL;
+        if (!aligned(ws, 8) || !aligned(boxes, 16)) return AFAN_EALIGN;
+        unsigned long long* mask = (unsigned long long*)ws;
+        unsigned long long* bandT = mask + b * ls.mask;
+        flag = (uint8_t*)(bandT + b * ls.band);
+        AFAN_PROF("rpn_proposals_kernel", (double)b * (16.0 * n + 8.0 * n * cb), st);
+        nms_mask_kernel<true><<<dim3(cb, cb, (unsigned)b), W64, 0, st>>>(boxes, order, (int)n, threshold, 0, mask, bandT, cb, flag, ls);
+        AFAN_LAUNCH_CHECK();
+        if ((size_t)cb * 8 > 8 * 1024) {
+            static const hipError_t attr = hipFuncSetAttribute((const void*)nms_scan_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
+            if (attr != hipSuccess) return (int)attr;
+        }
+        nms_scan_kernel<true><<<(unsigned)b, W64 * SCAN_WAVES, (size_t)cb * 8, st>>>(mask, bandT, order, (int)n, cb, flag, (int)top_n, ls);
+        AFAN_LAUNCH_CHECK();
+    }
+    rpn_rows_kernel<<<(unsigned)b, CP_THREADS, 0, st>>>(flag, (const float4*)boxes, order, (int)n, ls, top_n, (float4*)padded, kept);
     AFAN_LAUNCH_CHECK();
     return AFAN_OK;
 }

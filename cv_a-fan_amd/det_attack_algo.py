@@ -254,3 +254,107 @@ def det_train_phases(model, optimizer, image_batch, bboxes_batch, labels_batch, 
         optimizer.step()
     out.update({"loss": loss.detach(), "losses": torch.stack(L).detach(), "adv_image": adv_image.detach(), "adv1": adv1.detach(),
                 "adv2": adv2.detach(), "adv3": adv3.detach(), "adv_sd": adv_sd.detach(), "fm3": fm[2], "cuts": len(cuts)})
+
+
+def parse_mix_layer(mix_layer):
+    """`--mix_layer` of Detection/train_aug_final.py:67-68: four 0/1 digits, one per sample point 1..4."""
+    s = str(mix_layer)
+    if len(s) != 4 or any(c not in "01" for c in s):
+        raise ValueError(f"mix_layer: four 0/1 digits, one per sample point (train_aug_final.py:67-68), not {mix_layer!r}")
+    return tuple(c == "1" for c in s)
+
+
+def det_final_step(model, optimizer, image_batch, bboxes_batch, labels_batch, **settings):
+    """One iteration of Detection/train_aug_final.py:78-163 (see det_final_phases)."""
+    out = {}
+    for _ in det_final_phases(model, optimizer, image_batch, bboxes_batch, labels_batch, out, **settings):
+        pass
+    return out
+
+
+def det_final_phases(model, optimizer, image_batch, bboxes_batch, labels_batch, out, *, pertub_idx_se, mix_layer, gamma_se=0.5, gamma_sd=0.1,
+                     sd_adv_loss_weight=0.5, only_roi_sd=False, mix_sd=False, noise_sd=0, randinit=False, clip=False, defer_step=False):
+    """One iteration of Detection/train_aug_final.py:78-163 — the reference README's recipe — as a generator (it yields nothing: the
+    two-part backward of det_train_phases is not built for it): the backbone feature map behind layer `pertub_idx_se` and the ROI dict
+    (:78-85), a one-step feature PGD (eps 2/255, gamma_se/255, :87-95), a one-step ROI-feature PGD (gamma_sd/255, the two proposal
+    losses or all four, :97-107), optionally mix_feature and noise (2u - 1) * gamma_sd * noise_sd on it (:111-114, u drawn from the host
+    generator there), five sample points with points 1..4 re-normalised where the `mix_layer` digit is set (:117-126, one fused
+    launch), six forwards (:128-146) and loss = (L0 + .. + L4) / 3 * (1 - w) + L5 / 3 * w (:156).  The host generator's draws come in
+    the reference's order, pass by pass.  The sharing forms are det_train_phases', behind the same switches: the head pass's value
+    from the clean ROI-head pass (`collect`) or head_features; layer3 once for the clean pass and the tails entering behind layer 1 or
+    2 (BATCH_LAYER3); the ROI heads of the five passes in front of the ROI-tail pass as one (BATCH_ROI_HEAD)."""
+    if pertub_idx_se not in (1, 2, 3):
+        raise ValueError(f"pertub_idx_se: a backbone layer 1..3, not {pertub_idx_se!r}")
+    idx = int(pertub_idx_se)
+    mix = parse_mix_layer(mix_layer)
+    y = {"bb": bboxes_batch, "lb": labels_batch}
+    fwd = lambda d: model.train().forward(d, bboxes_batch, labels_batch)
+    if hasattr(model, "begin_iteration"):
+        model.begin_iteration()
+    if getattr(model, "collects_head_features", False):
+        col = {}
+        rr = fwd({"x": image_batch, "adv": None, "out_idx": "roi_head", "flag": "clean", "collect": col})
+        fm_se = col[idx]
+    else:
+        if hasattr(model, "head_features"):
+            fm_se = model.train().head_features(image_batch, (idx,))[0]
+        else:
+            fm_se = fwd({"x": image_batch, "adv": None, "out_idx": idx, "flag": "head"}).detach()
+        rr = fwd({"x": image_batch, "adv": None, "out_idx": "roi_head", "flag": "clean"})
+    clean_sd = rr["roi_output_dict"]["roi_feature_map"].detach()
+    adv_se = PGD(fm_se, image_batch, y=y, model=model, steps=1, eps=(2.0 / 255), gamma=(gamma_se / 255), idx=idx, randinit=randinit, clip=clip)
+    adv_rr = rpn_roi_PGD(layer="roi", rpn_roi_output_dict=rr, y=y, model=model, steps=1, eps=(2.0 / 255), gamma=(gamma_sd / 255),
+                         randinit=randinit, clip=clip, only_roi_loss=only_roi_sd)
+    adv_sd = adv_rr["roi_output_dict"]["roi_feature_map"].detach()
+    if mix_sd:
+        adv_sd = mix_feature(clean_sd.float(), adv_sd)
+    if noise_sd != 0:
+        if not mix_sd:
+            adv_sd = adv_sd.clone()
+        ops.axpy_noise_(adv_sd, torch.rand(adv_sd.shape).to(adv_sd.device, non_blocking=True), gamma_sd * noise_sd)
+    adv_rr["roi_output_dict"]["roi_feature_map"] = adv_sd
+    pts = sample_points_mixed(fm_se.float(), adv_se.detach(), 5, mix)                     # :117-126 in one launch
+    dicts = [{"x": image_batch, "adv": None, "out_idx": 0, "flag": "clean"}] + \
+            [{"x": image_batch, "adv": pts[j], "out_idx": idx, "flag": "tail"} for j in (1, 2, 3, 4)] + \
+            [{"adv": adv_rr, "out_idx": "roi_tail", "flag": "clean"}]
+    if idx in (1, 2) and BATCH_LAYER3 and hasattr(getattr(model, "features", None), "forward_many"):
+        f3 = model.train().features.forward_many(dicts[:5])
+        if f3 is not None:
+            dicts[:5] = [{"x": image_batch, "adv": f, "out_idx": 3, "flag": "tail"} for f in f3]
+    if BATCH_ROI_HEAD and hasattr(model, "forward_heads_many"):
+        L = [compute_loss(*o) for o in model.train().forward_heads_many(dicts[:5], bboxes_batch, labels_batch)] + [compute_loss(*fwd(dicts[5]))]
+    else:
+        L = [compute_loss(*fwd(d)) for d in dicts]
+    w = sd_adv_loss_weight
+    loss = ((L[0] + L[1] + L[2] + L[3] + L[4]) / 3.0) * (1 - w) + (L[5] / 3.0) * w
+    optimizer.zero_grad()
+    loss.backward()
+    if not defer_step:
+        optimizer.step()
+    out.update({"loss": loss.detach(), "losses": torch.stack(L).detach(), "adv_se": adv_se.detach(), "adv_sd": adv_sd.detach(), "fm_se": fm_se})
+    return
+    yield
+
+
+def det_base_step(model, optimizer, image_batch, bboxes_batch, labels_batch):
+    """One iteration of Detection/train_baseline.py:76-89 (see det_base_phases)."""
+    out = {}
+    for _ in det_base_phases(model, optimizer, image_batch, bboxes_batch, labels_batch, out):
+        pass
+    return out
+
+
+def det_base_phases(model, optimizer, image_batch, bboxes_batch, labels_batch, out, *, defer_step=False):
+    """One iteration of Detection/train_baseline.py:76-89 as a generator (it yields nothing): one clean forward, the sum of the four
+    losses' means, backward, the step."""
+    if hasattr(model, "begin_iteration"):
+        model.begin_iteration()
+    four = model.train().forward({"x": image_batch, "adv": None, "out_idx": 0, "flag": "clean"}, bboxes_batch, labels_batch)
+    loss = compute_loss(*four)
+    optimizer.zero_grad()
+    loss.backward()
+    if not defer_step:
+        optimizer.step()
+    out.update({"loss": loss.detach(), "losses": torch.stack([t.detach().mean() for t in four])})
+    return
+    yield

@@ -55,6 +55,12 @@ def get_argparser():
     parser.add_argument('--clip', action="store_true", help="whether using apex")
 
     parser.add_argument('--loss_settings', default=0, type=int, help='loss setting')
+    return _common_flags(parser)
+
+
+def _common_flags(parser):
+    """The flags the three Detection training parsers end with (train_aug_sat_muti_advt.py:230-256 == train_aug_final.py:213-238 ==
+    train_baseline.py:140-165)."""
     parser.add_argument('-s', '--dataset', type=str, choices=DATASET_OPTIONS, required=True, help='name of dataset')
     parser.add_argument('-b', '--backbone', type=str, choices=BACKBONE_OPTIONS, required=True, help='name of backbone model')
     parser.add_argument('-d', '--data_dir', type=str, default='./data', help='path to data directory')
@@ -83,11 +89,45 @@ def get_argparser():
     return parser
 
 
+def get_final_argparser():
+    """train_aug_final.py:196-238, flag for flag."""
+    parser = argparse.ArgumentParser()
+    # se settings
+    parser.add_argument('--steps', default=1, type=int, help='PGD-steps')
+    parser.add_argument('--pertub_idx_se', help='index of perturb layers', default=None, type=int)
+    parser.add_argument('--pertub_idx_sd', help='index of perturb layers', default='roi', type=str)
+    parser.add_argument('--gamma_se', help='index of PGD gamma', default=0.5, type=float)
+    parser.add_argument('--gamma_sd', help='index of PGD gamma', default=0.1, type=float)
+    parser.add_argument('--eps', default=2, type=float)
+    parser.add_argument('--randinit', action="store_true", help="whether using apex")
+    parser.add_argument('--clip', action="store_true", help="whether using apex")
+    parser.add_argument('--mix_layer', type=str, help="")
+    # sd settings
+    parser.add_argument('--noise_sd', help='if use noise', default=0, type=float)
+    parser.add_argument('--only_roi_sd', action="store_true", help="whether only using roi loss")
+    parser.add_argument('--mix_sd', action="store_true", help="whether using mix")
+    parser.add_argument('--sd_adv_loss_weight', help='loss', default=0.5, type=float)
+    return _common_flags(parser)
+
+
+def get_base_argparser():
+    """train_baseline.py:132-165, flag for flag (its PGD flags are parsed and never read)."""
+    parser = argparse.ArgumentParser()
+    # PGD Setting
+    parser.add_argument('--steps', default=1, type=int, help='PGD-steps')
+    parser.add_argument('--pertub_idx', help='index of perturb layers', default=3, type=int)
+    parser.add_argument('--gamma', help='index of PGD gamma', default=0.5, type=float)
+    parser.add_argument('--eps', default=2, type=float)
+    parser.add_argument('--randinit', action="store_true", help="whether using apex")
+    parser.add_argument('--clip', action="store_true", help="whether using apex")
+    return _common_flags(parser)
+
+
 ADDITIONS = ("synthetic", "dtype", "layout", "seed")
 
 
-def get_full_argparser():
-    parser = get_argparser()
+def get_full_argparser(parser=None):
+    parser = parser if parser is not None else get_argparser()
     parser.add_argument("--synthetic", type=int, default=0, help="train on N synthetic images with boxes instead of VOC")
     parser.add_argument("--dtype", default="bf16", choices=["bf16", "fp32"], help="backbone compute dtype")
     parser.add_argument("--layout", default="nhwc", choices=["nhwc", "nchw"], help="internal activation / weight layout")
@@ -132,12 +172,60 @@ def checkpoints_dir(args):
     return os.path.join(args.outputs_dir, 'ckpt-{:s}-{:s}-{:s}'.format(exp_name(args), args.dataset, args.backbone))
 
 
-def check_unbuilt(args):
-    """The reference's choices this build has nothing behind: raise before any work is done."""
+def final_exp_name(args):
+    """train_aug_final.py:245-247"""
+    name = ("s" + str(args.steps) + "se_" + str(args.pertub_idx_se) + "_sd_" + str(args.pertub_idx_sd) + "_g" + str(args.gamma_se) + "e" +
+            str(args.eps) + "_MIX" + args.mix_layer)
+    if args.randinit:
+        name += "_rand"
+    if args.clip:
+        name += "_clip"
+    return name
+
+
+def final_checkpoints_dir(args):
+    """train_aug_final.py:253-254"""
+    return os.path.join(args.outputs_dir, 'ckpt-{:s}-{:s}-{:s}'.format(final_exp_name(args), args.dataset, args.backbone))
+
+
+def base_checkpoints_dir(args):
+    """train_baseline.py:176-177"""
+    return os.path.join(args.outputs_dir, 'checkpoints-{:s}-{:s}_baseline'.format(args.dataset, args.backbone))
+
+
+def check_unbuilt_model(args):
     if args.backbone in REFUSED_BACKBONES:
         raise NotImplementedError(REFUSED_BACKBONES[args.backbone])
     if args.dataset in REFUSED_DATASETS:
         raise NotImplementedError(REFUSED_DATASETS[args.dataset])
+
+
+def check_unbuilt_final(args):
+    """train_aug_final.py: the choices nothing stands behind — here or in the reference — raise before any work is done.  (--clip is
+    none of them: it runs into the reference's own NameError inside rpn_roi_PGD, attack_algo.py:110, in the first iteration.)"""
+    check_unbuilt_model(args)
+    if args.pertub_idx_se not in (1, 2, 3):
+        raise ValueError(f"--pertub_idx_se {args.pertub_idx_se}: the feature map behind backbone layer 1, 2 or 3 is perturbed (the reference's "
+                         "default of None fails in its first forward, backbone/resnet101_ori.py:203-262)")
+    s = args.mix_layer
+    if s is None or len(s) != 4 or any(c not in "01" for c in s):
+        raise ValueError(f"--mix_layer {s}: four 0/1 digits, one per sample point 1..4 (the reference's default of None fails when it is "
+                         "unpacked, train_aug_final.py:67)")
+    if args.pertub_idx_sd != "roi":
+        raise ValueError(f"--pertub_idx_sd {args.pertub_idx_sd}: only 'roi' (the reference reads ['roi_output_dict'] at train_aug_final.py:85, "
+                         "which the dict of no other head pass holds)")
+
+
+def final_settings(args):
+    """The keyword settings of det_attack_algo.det_final_phases from the parsed flags."""
+    return dict(pertub_idx_se=args.pertub_idx_se, mix_layer=args.mix_layer, gamma_se=args.gamma_se, gamma_sd=args.gamma_sd,
+                sd_adv_loss_weight=args.sd_adv_loss_weight, only_roi_sd=args.only_roi_sd, mix_sd=args.mix_sd, noise_sd=args.noise_sd,
+                randinit=args.randinit, clip=args.clip)
+
+
+def check_unbuilt(args):
+    """The reference's choices this build has nothing behind: raise before any work is done."""
+    check_unbuilt_model(args)
     if args.loss_settings not in (1, 2, 3, 4):
         raise ValueError(f"--loss_settings {args.loss_settings}: the iteration knows settings 1 to 4 (the reference's default of 0 "
                          "asserts in its first iteration, train_aug_sat_muti_advt.py:165)")
@@ -243,16 +331,21 @@ def _step_seed(seed, step):
     return (int(seed) * 1000003 + int(step)) % (1 << 62)
 
 
-def train(model, loader, cfg, path_to_checkpoints_dir, log=None, path_to_resuming_checkpoint=None, loss_settings=1, seed=None):
+def train(model, loader, cfg, path_to_checkpoints_dir, log=None, path_to_resuming_checkpoint=None, loss_settings=1, seed=None, trainer=None):
     """train_aug_sat_muti_advt.py:45-211 around det_trainer.DetTrainer.step.  The learning rate of iteration t (t completed before it)
     is warmup_multistep_lr(t), written into optimizer.param_groups[0]["lr"] before the step.  The loss stays on the device until a
     `[Step s] Avg. Loss = ...` line needs the last 100.  A checkpoint every num_steps_to_snapshot steps and at the end; -r loads one
     and continues from its step, with the loader fast-forwarded to the epoch and batch that step stands at.  With a seed, the host
     and device generators are seeded from (seed, step) before every iteration, so a resumed run draws what the uninterrupted one
-    drew (and DetTrainer draws no noise ahead of its iteration).  -> {"step", "lrs", "losses" (device tensors), "trainer"}."""
+    drew (and DetTrainer draws no noise ahead of its iteration).  trainer: a det_trainer.DetTrainer on `model`, or a factory
+    `trainer(model, cfg)` of one (train_aug_final.py and train_baseline.py: the same loop around another iteration); None: the
+    multi-layer SAT iteration at `loss_settings`.  -> {"step", "lrs", "losses" (device tensors), "trainer"}."""
     log = log or Log()
-    trainer = det_trainer.DetTrainer(model, lr=cfg["learning_rate"], momentum=cfg["momentum"], weight_decay=cfg["weight_decay"],
-                                     loss_settings=loss_settings, noise_ahead=seed is None)
+    if trainer is None:
+        trainer = det_trainer.DetTrainer(model, lr=cfg["learning_rate"], momentum=cfg["momentum"], weight_decay=cfg["weight_decay"],
+                                         loss_settings=loss_settings, noise_ahead=seed is None)
+    elif not hasattr(trainer, "step"):
+        trainer = trainer(model, cfg)
     optimizer = trainer.optimizer
     step = 0
     time_checkpoint = time.time()
@@ -309,16 +402,11 @@ def train(model, loader, cfg, path_to_checkpoints_dir, log=None, path_to_resumin
     return {"step": step, "lrs": lrs, "losses": all_losses, "trainer": trainer}
 
 
-def main(program, argv=None):
-    args = get_full_argparser().parse_args(argv)
-    print_args(args, 100)
-    check_unbuilt(args)
-    cfg = config(args)
+def _run(program, args, cfg, path_to_checkpoints_dir, banner, trainer=None, loss_settings=1, first_line=None):
+    """What the three programs do between their refusals and `FINISL!`: device, directory, train.log, banner, data, model, train()."""
     device = setup_device(program)
     if args.seed is not None:
         torch.manual_seed(args.seed)
-
-    path_to_checkpoints_dir = checkpoints_dir(args)
     if not os.path.exists(path_to_checkpoints_dir):
         print("create dir:[{}]".format(path_to_checkpoints_dir))
         os.makedirs(path_to_checkpoints_dir)
@@ -327,18 +415,62 @@ def main(program, argv=None):
     for k, v in vars(args).items():
         log.i(f'\t{k} = {v}')
     log.i(describe(cfg))
-    print("-" * 100)
-    print("INFO: PID   : [{}]".format(os.getpid()))
-    print("-" * 100)
-
-    print("DATASET:[{}] DIR:[{}]".format(args.dataset, args.data_dir))
+    for line in banner:
+        print(line)
+    print(first_line if first_line is not None else "DATASET:[{}] DIR:[{}]".format(args.dataset, args.data_dir))
     images, boxes, classes, num_classes = build_split(args, cfg)
     loader = det_data.DetDeviceLoader(images, boxes, classes, cfg["batch_size"], device, True, cfg["image_min_side"], cfg["image_max_side"],
                                       seed=args.seed)
     log.i('Found {:d} samples'.format(len(images)))
     model = build_model(args, cfg, num_classes).to(device).train()
-    out = train(model, loader, cfg, path_to_checkpoints_dir, log, args.resume_checkpoint, args.loss_settings, args.seed)
+    out = train(model, loader, cfg, path_to_checkpoints_dir, log, args.resume_checkpoint, loss_settings, args.seed, trainer=trainer)
     print("=" * 100)
     print("FINISL!")
     print("=" * 100)
     return out
+
+
+def trainer_factory(phases, final=None):
+    return lambda model, cfg: det_trainer.DetTrainer(model, lr=cfg["learning_rate"], momentum=cfg["momentum"], weight_decay=cfg["weight_decay"],
+                                                     phases=phases, final=final)
+
+
+def main(program, argv=None):
+    args = get_full_argparser().parse_args(argv)
+    print_args(args, 100)
+    check_unbuilt(args)
+    cfg = config(args)
+    banner = ["-" * 100, "INFO: PID   : [{}]".format(os.getpid()), "-" * 100]
+    return _run(program, args, cfg, checkpoints_dir(args), banner, loss_settings=args.loss_settings)
+
+
+def final_banner(args, path_to_checkpoints_dir):
+    """train_aug_final.py:273-283"""
+    return ["-" * 100, "INFO: PID   : [{}]".format(os.getpid()),
+            "EXP: [SE + SAT + MIX + SD] Dataset: [{}]".format(args.dataset),
+            "SE : Layer:[{}]  MIX:[{}]  Gamma:[{}]  Eps:[{}]  Randinit:[{}] Clip:[{}]"
+            .format(args.pertub_idx_se, args.mix_layer, args.gamma_se, args.eps, args.randinit, args.clip),
+            "SD : Layer:[{}]  MIX:[{}]  Gamma:[{}]  AdvWeight:[{}] Noise:[{}] ROI:[{}]"
+            .format(args.pertub_idx_sd, args.mix_sd, args.gamma_sd, args.sd_adv_loss_weight, args.noise_sd, args.only_roi_sd),
+            "DIR:[{}]".format(path_to_checkpoints_dir), "-" * 100]
+
+
+def main_final(program, argv=None):
+    """train_aug_final.py:194-286"""
+    args = get_full_argparser(get_final_argparser()).parse_args(argv)
+    print_args(args, 100)
+    check_unbuilt_final(args)
+    cfg = config(args)
+    d = final_checkpoints_dir(args)
+    return _run(program, args, cfg, d, final_banner(args, d), trainer=trainer_factory("final", final_settings(args)))
+
+
+def main_base(program, argv=None):
+    """train_baseline.py:130-194"""
+    args = get_full_argparser(get_base_argparser()).parse_args(argv)
+    print_args(args, 100)
+    print("INFO: PID   : [{}]".format(os.getpid()))
+    check_unbuilt_model(args)
+    cfg = config(args)
+    return _run(program, args, cfg, base_checkpoints_dir(args), [], trainer=trainer_factory("base"),
+                first_line="Training Baseline ! DATASET:[{}] DIR:[{}]".format(args.dataset, args.data_dir))

@@ -25,7 +25,7 @@ import torch.nn.functional as F
 from . import ops
 from .deeplab import MaxPool2d, StemConv, _MaxPoolFn, _enter
 from .det_ops import (box_assign, box_decode_clip, class_nms, class_nms_supported, fg_bg_draw, fg_bg_sample, labels_limit_, nms,
-                      per_image_losses, proposal_rows, roi_align, sample_lists)
+                      per_image_losses, proposal_rows, roi_align, rpn_proposals, sample_lists, RPN_PROPOSALS_MAX_BATCH)
 from .resnet_s import (Conv2d, NormalizeByChannelMeanStd, _accumulates_in_place, _ConvFn, _dense, _Flags, _FrozenBlockFn, _like_layout, _linear,
                        dgrad_only, _own_conv_ok, _to_compute, _WgradStream)
 
@@ -621,6 +621,7 @@ def _early_wait(slot):
 BATCH_RPN_TRUNK = os.environ.get("AFAN_DET_BATCH_RPN", "1") != "0"   # 0: forward_heads_many runs the RPN trunk and heads pass by pass (A/B, tests)
 ANCHOR_LABEL_CACHE = os.environ.get("AFAN_DET_LABEL_CACHE", "1") != "0"   # 0: every pass labels the anchors and reads the list lengths itself (A/B, tests)
 LINEAR_PAIR = os.environ.get("AFAN_DET_LINEAR_PAIR", "1") != "0"      # 0: each head layer on the general fp32 kernels (A/B, tests)
+BATCH_PROPOSALS = os.environ.get("AFAN_DET_BATCH_PROPOSALS", "1") != "0"   # 0: the proposal layer's NMS image by image at every batch size (A/B, tests)
 
 
 class _LinearPairFn(torch.autograd.Function):
@@ -792,30 +793,44 @@ class RegionProposalNetwork(nn.Module):
         boxes = box_decode_clip(anchor_bboxes, transformers.float(), image_width, image_height)
         probs = F.softmax(objectnesses.float()[:, :, 1], dim=-1)
         _, order = torch.sort(probs, dim=-1, descending=True)
-        cand, keeps = [], []
-        for b in range(anchor_bboxes.shape[0]):
-            sb = boxes[b][order[b][:self._pre_nms_top_n]]
-            keeps.append(nms(sb, None, 0.7, max_keep=self._post_nms_top_n, presorted=True, padded=True))
-            cand.append(sb)
-        roi_pend, nb_img = None, len(keeps)
+        nb_img = anchor_bboxes.shape[0]
+        batched = BATCH_PROPOSALS and 2 <= nb_img <= RPN_PROPOSALS_MAX_BATCH
+        roi_pend = None
+        if batched:
+            # two images or more: every image's NMS and row block in three launches (det_ops.rpn_proposals: the candidates read through
+            # `order`, one scan workgroup per image) where the loop below issues seven per image; `kept_n` [B] — min(count, top_n), the
+            # length the loop's `[:post_nms_top_n]` leaves — travels in place of the B raw counts.  Same rows, same draws in the same order
+            padded, kept_n = rpn_proposals(boxes, order, self._pre_nms_top_n, 0.7, self._post_nms_top_n)
+            nms_counts = [kept_n]
+        else:
+            cand, keeps = [], []
+            for b in range(nb_img):
+                sb = boxes[b][order[b][:self._pre_nms_top_n]]
+                keeps.append(nms(sb, None, 0.7, max_keep=self._post_nms_top_n, presorted=True, padded=True))
+                cand.append(sb)
+            nms_counts = [c for _, c in keeps]
+            if roi_targets is not None:
+                padded, kept_n = proposal_rows(cand, keeps, self._post_nms_top_n)     # (the scan may report up to 63 survivors more: clamped there)
         if roi_targets is not None:
-            padded, kept_n = proposal_rows(cand, keeps, self._post_nms_top_n)     # (the scan may report up to 63 survivors more: clamped there)
             roi_pend = roi_targets(padded, kept_n)
         if early is not None or known is not None:
             nf, nb_ = known if known is not None else _early_wait(early)
             ce, sl1 = self._losses_finish(pend, nf, nb_)                      # host draws + launches while the NMS is still running
-            counts = [nf, nb_] + torch.cat([c for _, c in keeps] + ([roi_pend.counts] if roi_pend is not None else [])).tolist()
+            counts = [nf, nb_] + torch.cat(nms_counts + ([roi_pend.counts] if roi_pend is not None else [])).tolist()
         else:
-            counts = torch.cat([pend[0][2]] + [c for _, c in keeps] + ([roi_pend.counts] if roi_pend is not None else [])).tolist()   # the one read
+            counts = torch.cat([pend[0][2]] + nms_counts + ([roi_pend.counts] if roi_pend is not None else [])).tolist()   # the one read
             ce, sl1 = self._losses_finish(pend, counts[0], counts[1])
         if ANCHOR_LABEL_CACHE and lc is not None and lc[1] is pend[0] and lc[5] is None:
             lc[5] = (counts[0], counts[1])
-        kept = [sb[k[:n]][:self._post_nms_top_n] for sb, (k, _), n in zip(cand, keeps, counts[2:2 + nb_img])]
-        if len(kept) == 1:
-            proposals = kept[0].unsqueeze(0)
+        if batched:
+            proposals = padded[:, :max(counts[2:2 + nb_img])]
         else:
-            longest = max(len(k) for k in kept)
-            proposals = torch.stack([torch.cat([k, torch.zeros(longest - len(k), 4).to(k)]) for k in kept], dim=0)
+            kept = [sb[k[:n]][:self._post_nms_top_n] for sb, (k, _), n in zip(cand, keeps, counts[2:2 + nb_img])]
+            if len(kept) == 1:
+                proposals = kept[0].unsqueeze(0)
+            else:
+                longest = max(len(k) for k in kept)
+                proposals = torch.stack([torch.cat([k, torch.zeros(longest - len(k), 4).to(k)]) for k in kept], dim=0)
         roi_t = roi_pend.finish(counts[2 + nb_img], counts[3 + nb_img]) if roi_pend is not None else None
         if share is not None and (roi_pend is not None) == (roi_targets is not None):
             share["state"] = (pend[:6] + (None, None, pend[8]), counts, proposals.detach(), roi_pend, nb_img)

@@ -179,6 +179,32 @@ def proposal_rows(cands, keeps, top_n):
     return padded, kept
 
 
+RPN_PROPOSALS_MAX_BATCH = 64
+
+
+def rpn_proposals(boxes, order, pre_n, threshold, top_n):
+    """The proposal layer's NMS for ALL images of a batch (afan_rpn_proposals: three launches whatever B is, nothing read): boxes
+    [B, A, 4] decoded and clipped, order [B, A] int64 = each image's indices by descending score.  Per image the candidates are
+    boxes[b][order[b][:pre_n]] — read through `order`, no gathered copy —, greedy NMS at IoU > threshold, stopped at top_n survivors.
+    Returns (padded [B, top_n, 4] fp32: the first min(count, top_n) survivors in score order, zero rows behind them; kept [B] int64:
+    that number), both on the device — what nms(..., max_keep=top_n, presorted=True, padded=True) + proposal_rows give image by image."""
+    boxes = _f32c(boxes, "rpn_proposals")
+    if boxes.dim() != 3 or boxes.shape[-1] != 4:
+        raise ValueError("rpn_proposals: boxes [B, A, 4]")
+    B, A, _ = boxes.shape
+    if order.dtype != torch.int64 or tuple(order.shape) != (B, A) or order.device != boxes.device:
+        raise ValueError("rpn_proposals: order [B, A] int64 on the boxes' device")
+    order = order.detach().contiguous()
+    pre_n, top_n = int(pre_n), int(top_n)
+    lib, dev = _lib.load(), boxes.device
+    padded = torch.empty((B, top_n, 4), dtype=torch.float32, device=dev)
+    kept = torch.empty(B, dtype=torch.int64, device=dev)
+    ws = _workspace_bytes(dev, lib.afan_rpn_proposals_workspace_bytes(B, min(max(pre_n, 0), A))) if B <= RPN_PROPOSALS_MAX_BATCH else None
+    check(lib.afan_rpn_proposals(_ptr(boxes), _ptr(order), B, A, pre_n, float(threshold), top_n, _ptr(ws), _ptr(padded), _ptr(kept), _stream(dev)),
+          "afan_rpn_proposals")
+    return padded, kept
+
+
 def labels_limit_(labels, kept):
     """labels [B, N] int64 in place: columns >= max(kept) become -1 (kept [B] int64 on the device, never read)."""
     if labels.dtype != torch.int64 or kept.dtype != torch.int64 or not labels.is_contiguous() or labels.dim() != 2:

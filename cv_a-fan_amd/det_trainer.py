@@ -12,7 +12,7 @@ config/train_config.py; the learning-rate schedule (WarmUpMultiStepLR, :48) step
 import torch
 
 from .arena import ArenaSGD, ParamArena
-from .det_attack_algo import det_train_phases
+from .det_attack_algo import det_base_phases, det_final_phases, det_train_phases, parse_mix_layer
 from .train_step import StepTrainer
 
 # everything behind the conv4 feature map: layer4 (= detection.hidden), the RPN and the two heads.  The backbone's unused ImageNet
@@ -27,8 +27,22 @@ class DetTrainer(StepTrainer):
     """Of StepTrainer only the exchange set-up: frozen BatchNorm (no grid barrier on this path: flush_guard() is the uniform no-op),
     no graph of its own, and a step of three inputs."""
 
+    PHASES = ("sat", "final", "base")
+
     def __init__(self, model, *, lr=0.001, momentum=0.9, weight_decay=0.0005, loss_settings=1, group=None, allreduce_chunks=4,
-                 segmented=None, arena=None, noise_ahead=False):
+                 segmented=None, arena=None, noise_ahead=False, phases="sat", final=None):
+        """phases: which iteration step() runs on the same arena, SGD and exchange — "sat" (train_aug_sat_muti_advt.py, the default),
+        "final" (train_aug_final.py:78-163 with the keyword settings of det_attack_algo.det_final_phases in `final`) or "base"
+        (train_baseline.py:76-89).  The two new ones run their backward in one part: with a process group the whole arena is
+        reduced at finish()."""
+        if phases not in self.PHASES:
+            raise ValueError(f"phases: one of {self.PHASES}, not {phases!r}")
+        self.phases = phases
+        self.final = dict(final or {})
+        if phases == "final":
+            if self.final.get("pertub_idx_se") not in (1, 2, 3):
+                raise ValueError(f"final['pertub_idx_se']: a backbone layer 1..3, not {self.final.get('pertub_idx_se')!r}")
+            parse_mix_layer(self.final.get("mix_layer"))
         self.loss_settings = int(loss_settings)
         self.arena = arena if arena is not None else ParamArena(model, skip=UNUSED_PARAMS)
         self.optimizer = ArenaSGD(self.arena, lr, momentum, weight_decay)
@@ -49,6 +63,18 @@ class DetTrainer(StepTrainer):
         return self.segmented or self.reducer is not None
 
     def step(self, images, bboxes, labels):
+        if self.phases != "sat":
+            out = {}
+            if self.reducer is not None:
+                self.reducer.begin(explicit=True)
+            gen = (det_final_phases(self.model, self.optimizer, images, bboxes, labels, out, defer_step=True, **self.final)
+                   if self.phases == "final" else det_base_phases(self.model, self.optimizer, images, bboxes, labels, out, defer_step=True))
+            for _ in gen:
+                pass
+            if self.reducer is not None:
+                self.reducer.finish()      # nothing was announced: the whole arena is reduced here
+            self.optimizer.step()
+            return out
         out, rng = {}, self.tail_range()
         cut = self._phased() and rng is not None and hasattr(self.model, "cut_features")
         if self.reducer is not None:

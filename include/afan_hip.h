@@ -698,6 +698,16 @@ int afan_linear_pair_wgrad_f32(const float* g1, const float* g2, const float* x,
 int afan_proposal_rows(const float* cand, int64_t n_cand, const int64_t* keep, int64_t n_keep, const int64_t* count, int64_t P,
                        float* rows, int64_t* kept, afan_stream_t stream);
 int afan_labels_limit(int64_t* labels, int64_t B, int64_t N, const int64_t* kept, int64_t n_kept, afan_stream_t stream);
+/* afan_rpn_proposals — the proposal layer's NMS and row block (Detection/rpn/region_proposal_network.py:240-270) for ALL images of a
+ * batch in three launches whatever B is: the overlap tiles with the image in the grid's third dimension, the greedy scan with one
+ * workgroup per image, the survivors' rows.  boxes [B,A,4] decoded and clipped, order [B,A] int64 = each image's anchor indices by
+ * DESCENDING score (read through, no gathered copy).  Per image the candidates are boxes[b][order[b][i]], i < min(pre_n, a); greedy
+ * NMS at IoU > threshold with afan_nms_top's early stop at top_n survivors; padded [B,top_n,4]: the first min(count, top_n) survivors
+ * in score order, zero rows behind them; kept [B]: that number — what afan_nms_top + afan_proposal_rows leave image by image, bit for
+ * bit.  ws: afan_rpn_proposals_workspace_bytes(b, min(pre_n, a)) bytes, 8-byte aligned.  B <= 64 (AFAN_ESHAPE beyond). */
+int64_t afan_rpn_proposals_workspace_bytes(int64_t b, int64_t n);
+int afan_rpn_proposals(const float* boxes, const int64_t* order, int64_t b, int64_t a, int64_t pre_n, float threshold, int64_t top_n,
+                       void* ws, float* padded, int64_t* kept, afan_stream_t stream);
 int afan_det_loss_bwd(const float* g_ce, const float* g_sl1, const float* save, const int64_t* rows, const int64_t* gt_labels,
                       const int64_t* batch, int64_t S, int64_t B, int64_t C, int64_t K, int64_t R, float* d_logits, float* d_deltas,
                       afan_stream_t stream);
