@@ -19,8 +19,8 @@ import os
 import torch
 import torch.nn as nn
 
-from . import ops
-from .resnet_s import (BatchNorm2d, Conv2d, NormalizeByChannelMeanStd, _BlockFn, _ConvFn, _Flags, _FrozenBlockFn, _WgradStream,
+from . import frozen, ops
+from .resnet_s import (BatchNorm2d, Conv2d, NormalizeByChannelMeanStd, _BlockFn, _ConvFn, _Flags, _WgradStream,
                        _accumulates_in_place, _block_fast_path_ok, _block_params, _dense, _like_layout, _own_conv_ok, _to_compute)
 
 __all__ = ["deeplabv3plus_resnet50", "deeplabv3plus_resnet101", "deeplabv3_resnet50", "deeplabv3_resnet101", "DeepLabV3",
@@ -412,31 +412,14 @@ def _enter(x, dtype, channels_last):
 # at call time (tests flip it); training mode, fp32, NCHW and BatchNorms with their auxiliary (--dual_bn) set swapped in never come here.
 FROZEN_EVAL = os.environ.get("AFAN_SEG_FROZEN_EVAL", "1") != "0"
 # The BatchNorms are not frozen for good (training continues between validations): coefficient blocks and block plans are kept per
-# module and rebuilt when a tensor behind them changed (_version, address), the weights moved (_Flags.weight_epoch) or any BatchNorm
-# was in training mode in between (_Flags.bn_epoch).  0: rebuilt at every call (A/B, tools/probe/seg_pgd_val_time.py).
+# module and rebuilt when what they were read from changed (frozen.bn_coefs, frozen.block_plan).  0: rebuilt at every call (A/B,
+# tools/probe/seg_pgd_val_time.py).
 COEF_CACHE = os.environ.get("AFAN_SEG_COEF_CACHE", "1") != "0"
 
 
 def _bn_frozen(bn):
     return (not bn.training) and bn.track_running_stats and getattr(bn, "_branch", "main") == "main" and bn.weight is not None \
         and bn.weight.dtype == torch.float32
-
-
-def _bn_key(bn):
-    ts = (bn.running_mean, bn.running_var, bn.weight, bn.bias)
-    return tuple(t._version for t in ts) + tuple(t.data_ptr() for t in ts) + (_Flags.bn_epoch,)
-
-
-def _bn_coefs(bn):
-    """The afan_affine_coefs block [4, C] of an eval-mode BatchNorm, by BatchNorm2d.fused's expressions (the same values)."""
-    key = _bn_key(bn) if COEF_CACHE else None
-    hit = bn.__dict__.get("_frozen_coefs")
-    if key is not None and hit is not None and hit[0] == key:
-        return hit[1]
-    with torch.no_grad():
-        coefs = ops.affine_coefs(bn.running_mean, torch.rsqrt(bn.running_var + bn.eps), bn.weight.detach(), bn.bias.detach())
-    bn.__dict__["_frozen_coefs"] = (key, coefs)
-    return coefs
 
 
 def _frozen_conv_ok(conv, x):
@@ -484,62 +467,15 @@ def _cbr(conv, bn, x, relu=True):
     if FROZEN_EVAL and _bn_frozen(bn) and conv.compute_dtype == torch.bfloat16:
         xc = _to_compute(x, conv.compute_dtype)
         if _frozen_input_ok(xc) and _frozen_conv_ok(conv, xc):
-            return _FrozenCbrFn.apply(xc, conv, _bn_coefs(bn), relu)
+            return _FrozenCbrFn.apply(xc, conv, frozen.bn_coefs(bn, COEF_CACHE), relu)
     out, st = conv.forward_with_stats(x, bn)
     return bn.fused(out, None, relu, st)
 
 
-def _frozen_block_plan(blk, x):
-    """The eval-mode Bottleneck's ops.FrozenBlockPlan for this input (dilation of its 3x3 included, no weight gradients), or None
-    where the one-node form does not apply — then the layers run as they always did."""
-    convs = [blk.conv1, blk.conv2, blk.conv3] + ([blk.downsample[0]] if blk.downsample is not None else [None])
-    bns = [blk.bn1, blk.bn2, blk.bn3] + ([blk.downsample[1]] if blk.downsample is not None else [])
-    if not all(_bn_frozen(b) for b in bns):
-        return None
-    key = None
-    if COEF_CACHE:
-        key = (tuple(x.shape), x.device.index, _Flags.weight_epoch) + tuple(v for b in bns for v in _bn_key(b)) + \
-            tuple(v for c in convs if c is not None for v in (c.weight._version, c.lp_weight().data_ptr()))
-        hit = blk.__dict__.get("_frozen_plan")
-        if hit is not None and hit[0] == key:
-            return hit[1]
-    plan = None
-    c2 = blk.conv2
-    ok = all(c is None or (c.bias is None and c.compute_dtype == torch.bfloat16) for c in convs) and \
-        tuple(c2.padding) == tuple(c2.dilation) and (c2.dilation[0] == 1 or c2.stride[0] == 1)
-    if ok:
-        n, _, h, w = x.shape
-        ho, wo = (h - 1) // c2.stride[0] + 1, (w - 1) // c2.stride[0] + 1
-        probes = [x, _Probe((n, c2.in_channels, h, w), x), _Probe((n, blk.conv3.in_channels, ho, wo), x), x]
-        ok = all(c is None or _own_conv_ok(t, c.lp_weight(), c.stride, c.padding, c.dilation) for c, t in zip(convs, probes))
-    if ok:
-        ks = tuple(_bn_coefs(b) for b in bns) + ((None,) if convs[3] is None else ())
-        plan = ops.frozen_bottleneck_plan(x, blk.conv1.out_channels, c2.stride[0],
-                                          tuple(None if c is None else c.lp_weight().detach() for c in convs), ks,
-                                          tuple(None if c is None else c.lp_weight_t() for c in convs),
-                                          tuple(None if k is None else k[2] for k in ks), (None, None, None, None), dilation=c2.dilation[0])
-    blk.__dict__["_frozen_plan"] = (key, plan)
-    return plan
-
-
-class _Probe:
-    """What _own_conv_ok looks at of a map that does not exist yet (a block's inner activations)."""
-    __slots__ = ("shape", "device", "dtype", "is_cuda")
-
-    def __init__(self, shape, like):
-        self.shape, self.device, self.dtype, self.is_cuda = torch.Size(shape), like.device, like.dtype, like.is_cuda
-
-    def dim(self):
-        return len(self.shape)
-
-    def is_contiguous(self, memory_format=None):
-        return True
-
-
-class Bottleneck(nn.Module):
+class Bottleneck(frozen.FrozenBottleneck):
     """backbone/resnet.py:76-119: 1x1 -> 3x3 (stride, dilation) -> 1x1 x4, `downsample` = 1x1 conv + BN when the shape
-    changes.  One autograd node on the bf16 channels-last path (resnet_s._BlockFn)."""
-    expansion = 4
+    changes.  One autograd node on the bf16 channels-last path (resnet_s._BlockFn; in eval mode frozen._FrozenBlockFn)."""
+    norm = BatchNorm2d
     # True: the block's input is read outside the block too (ResNet sets it on layer2's first block: the decoder reads the low-level
     # feature).  The one-node eval form adds the block's own two input gradients inside a launch, a + b, before autograd adds the
     # other reader's c; the layer-by-layer nodes hand them over one by one, (c + b) + a.  bf16 sums of three do not reorder, so such
@@ -547,16 +483,7 @@ class Bottleneck(nn.Module):
     shared_input = False
 
     def __init__(self, inplanes, planes, stride=1, downsample=None, dilation=1):
-        super().__init__()
-        self.conv1 = Conv2d(inplanes, planes, kernel_size=1, stride=1, bias=False)
-        self.bn1 = BatchNorm2d(planes)
-        self.conv2 = Conv2d(planes, planes, kernel_size=3, stride=stride, padding=dilation, dilation=dilation, bias=False)
-        self.bn2 = BatchNorm2d(planes)
-        self.conv3 = Conv2d(planes, planes * 4, kernel_size=1, stride=1, bias=False)
-        self.bn3 = BatchNorm2d(planes * 4)
-        self.relu = nn.ReLU(inplace=True)
-        self.downsample = downsample
-        self.stride = stride
+        super().__init__(inplanes, planes, stride, downsample, dilation)
         self._sc_kind = "conv" if downsample is not None else "identity"
 
     @property
@@ -566,20 +493,14 @@ class Bottleneck(nn.Module):
     def _chain(self):
         return [(self.conv1, self.bn1), (self.conv2, self.bn2), (self.conv3, self.bn3)]
 
-    def __getstate__(self):
-        # (the eval-mode launch plan holds ctypes pointer objects: a deepcopy / torch.save of the module starts without it)
-        d = dict(self.__dict__)
-        d.pop("_frozen_plan", None)
-        return d
-
     def forward(self, x):
         x = _to_compute(x, self.conv1.compute_dtype)
         if _Flags.block_fusion and _block_fast_path_ok(self, x):
             return _BlockFn.apply(x, self, _Flags.param_grads, *_block_params(self))
         if not self.bn1.training and not self.shared_input and _frozen_input_ok(x):
-            plan = _frozen_block_plan(self, x)
+            plan = frozen.block_plan(self, x, bn_ok=_bn_frozen, cache=COEF_CACHE)      # (input gradients only, the 3x3's own dilation)
             if plan is not None:
-                return _FrozenBlockFn.apply(x, self, plan)
+                return frozen._FrozenBlockFn.apply(x, self, plan)
         out = _cbr(self.conv1, self.bn1, x)
         out = _cbr(self.conv2, self.bn2, out)
         out, st = self.conv3.forward_with_stats(out, self.bn3)
@@ -587,47 +508,59 @@ class Bottleneck(nn.Module):
         return self.bn3.fused(out, res, True, st)
 
 
-class ResNet(nn.Module):
-    """backbone/resnet.py:109-304 (Bottleneck variants): atrous ResNet with the head / tail / clean dispatch."""
+class BottleneckResNet(nn.Module):
+    """The Bottleneck ResNet skeleton both families build (backbone/resnet.py:109-304, Detection/backbone/resnet101_ori.py:130-262):
+    normaliser, 7x7 stem, BatchNorm, max pool and four stages of `block` (a frozen.FrozenBottleneck; its `norm` is the BatchNorm
+    class throughout).  A subclass adds its own modules behind them, calls `_init_weights()` last and keeps its own forward protocol."""
 
-    def __init__(self, layers, replace_stride_with_dilation=(False, False, False)):
+    def __init__(self, block, layers, replace_stride_with_dilation=(False, False, False)):
         super().__init__()
         self.normal = NormalizeByChannelMeanStd(mean=[0.485, 0.456, 0.406], std=[0.229, 0.224, 0.225])
         self.inplanes, self.dilation = 64, 1
         self.conv1 = StemConv(3, 64, kernel_size=7, stride=2, padding=3, bias=False)
-        self.bn1 = BatchNorm2d(64)
+        self.bn1 = block.norm(64)
         self.relu = nn.ReLU(inplace=True)
         self.maxpool = MaxPool2d(kernel_size=3, stride=2, padding=1)
-        self.layer1 = self._make_layer(64, layers[0])
-        self.layer2 = self._make_layer(128, layers[1], stride=2, dilate=replace_stride_with_dilation[0])
-        self.layer3 = self._make_layer(256, layers[2], stride=2, dilate=replace_stride_with_dilation[1])
-        self.layer4 = self._make_layer(512, layers[3], stride=2, dilate=replace_stride_with_dilation[2])
-        self.layer2[0].shared_input = True                     # (`low_level`, forward(): layer1's output goes to the decoder as well)
-        for m in self.modules():                               # backbone/resnet.py:160-165
+        self.layer1 = self._make_layer(block, 64, layers[0])
+        self.layer2 = self._make_layer(block, 128, layers[1], stride=2, dilate=replace_stride_with_dilation[0])
+        self.layer3 = self._make_layer(block, 256, layers[2], stride=2, dilate=replace_stride_with_dilation[1])
+        self.layer4 = self._make_layer(block, 512, layers[3], stride=2, dilate=replace_stride_with_dilation[2])
+
+    def _init_weights(self):                                   # backbone/resnet.py:160-165
+        for m in self.modules():
             if isinstance(m, nn.Conv2d):
                 nn.init.kaiming_normal_(m.weight, mode="fan_out", nonlinearity="relu")
             elif isinstance(m, nn.BatchNorm2d):
                 nn.init.constant_(m.weight, 1)
                 nn.init.constant_(m.bias, 0)
 
-    def _make_layer(self, planes, blocks, stride=1, dilate=False):
+    def _make_layer(self, block, planes, blocks, stride=1, dilate=False):
         downsample, previous_dilation = None, self.dilation
         if dilate:
             self.dilation *= stride
             stride = 1
         if stride != 1 or self.inplanes != planes * 4:
             downsample = nn.Sequential(Conv2d(self.inplanes, planes * 4, kernel_size=1, stride=stride, bias=False),
-                                       BatchNorm2d(planes * 4))
-        layers = [Bottleneck(self.inplanes, planes, stride, downsample, previous_dilation)]
+                                       block.norm(planes * 4))
+        layers = [block(self.inplanes, planes, stride, downsample, previous_dilation)]
         self.inplanes = planes * 4
         for _ in range(1, blocks):
-            layers.append(Bottleneck(self.inplanes, planes, dilation=self.dilation))
+            layers.append(block(self.inplanes, planes, dilation=self.dilation))
         return nn.Sequential(*layers)
 
     def _stem(self, x):
         x = self.normal(x)
         x = self.bn1.fused(self.conv1(x), None, True)
         return self.maxpool(x)
+
+
+class ResNet(BottleneckResNet):
+    """backbone/resnet.py:109-304 (Bottleneck variants): atrous ResNet with the head / tail / clean dispatch."""
+
+    def __init__(self, layers, replace_stride_with_dilation=(False, False, False)):
+        super().__init__(Bottleneck, layers, replace_stride_with_dilation)
+        self.layer2[0].shared_input = True                     # (`low_level`, forward(): layer1's output goes to the decoder as well)
+        self._init_weights()
 
     def forward(self, input_dict):
         stages = [self.layer1, self.layer2, self.layer3, self.layer4]

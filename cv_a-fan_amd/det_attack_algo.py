@@ -17,7 +17,7 @@ import os
 
 import torch
 
-from . import ops, pgd
+from . import frozen, ops, pgd
 from .attack_algo import get_sample_points, linfball_proj, mix_feature, sample_points_mixed, tensor_clamp  # noqa: F401
 from .det_ops import PGD, sum_of_means  # noqa: F401  (Detection/attack_algo.py:48-74)
 
@@ -56,18 +56,17 @@ def _pgd1_from_clean(model, col, idx, image_batch, y, eps, gamma):
     its one forward runs the backbone's remaining stages on the CLEAN feature map — the numbers the clean ROI-head pass already
     computed — so only the part behind the backbone is run again (RPN, proposals, ROI head: their sampling draws are this call's
     own, as in the reference), and its gradient is carried back through the clean pass's stored activations with the
-    input-gradient-only launches (det_model.stage_input_gradient).  Same values as PGD(); None where the stages did not run in the
+    input-gradient-only launches (frozen.stage_input_gradient).  Same values as PGD(); None where the stages did not run in the
     one-node form (fp32, NCHW: PGD() itself then runs)."""
-    from . import det_model
     stages = [model.features.layer1, model.features.layer2, model.features.layer3]
     outs = [col.get(("out", i)) for i in (1, 2, 3)]
-    if not all(det_model.stage_input_gradient(stages[i - 1], outs[i - 1]) for i in range(idx + 1, 4)):
+    if not all(frozen.stage_input_gradient(stages[i - 1], outs[i - 1]) for i in range(idx + 1, 4)):
         return None                  # (decided before anything is drawn from the host generator)
     x, x_adv = pgd.start(col[idx], eps, False)
     g = pgd.input_gradient(lambda t: sum_of_means(*model.train().forward({"x": image_batch, "adv": t, "out_idx": 3, "flag": "tail"}, y["bb"], y["lb"])),
                            col[3].detach().requires_grad_(True))
     for i in range(3, idx, -1):
-        g = det_model.stage_input_gradient(stages[i - 1], outs[i - 1], g)
+        g = frozen.stage_input_gradient(stages[i - 1], outs[i - 1], g)
     pgd.step(x_adv, g, gamma, x, eps, False)
     return x_adv.requires_grad_(True)
 
@@ -80,12 +79,11 @@ def _pgd_three_from_clean(model, col, image_batch, y, specs, share=None):
     reference's order), one backward of the three losses' sum gives each leaf its own gradient (a pass's loss depends on its leaf only),
     and the first two are carried back through the clean pass's stored activations as in _pgd1_from_clean.  specs: [(idx, eps, gamma)]
     for idx 1, 2, 3.  None where the one-node stages or forward_heads_many are not there (the caller runs the three calls)."""
-    from . import det_model
     if not hasattr(model, "forward_heads_many"):
         return None
     stages = [model.features.layer1, model.features.layer2, model.features.layer3]
     outs = [col.get(("out", i)) for i in (1, 2, 3)]
-    if not all(det_model.stage_input_gradient(stages[i - 1], outs[i - 1]) for i in (2, 3)):
+    if not all(frozen.stage_input_gradient(stages[i - 1], outs[i - 1]) for i in (2, 3)):
         return None                  # (decided before anything is drawn from the host generator)
     def loss_of(xins):
         res = model.train().forward_heads_many([{"x": image_batch, "adv": xi, "out_idx": 3, "flag": "tail"} for xi in xins], y["bb"], y["lb"],
@@ -99,7 +97,7 @@ def _pgd_three_from_clean(model, col, image_batch, y, specs, share=None):
     advs = []
     for (idx, eps, gamma), g in zip(specs, grads):
         for i in range(3, idx, -1):
-            g = det_model.stage_input_gradient(stages[i - 1], outs[i - 1], g)
+            g = frozen.stage_input_gradient(stages[i - 1], outs[i - 1], g)
         x, x_adv = pgd.start(col[idx], eps, False)
         pgd.step(x_adv, g, gamma, x, eps, False)
         advs.append(x_adv.requires_grad_(True))

@@ -22,12 +22,12 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import ops
-from .deeplab import MaxPool2d, StemConv, _MaxPoolFn, _enter
+from . import frozen, ops
+from .deeplab import BottleneckResNet, _MaxPoolFn, _enter
 from .det_ops import (box_assign, box_decode_clip, class_nms, class_nms_supported, fg_bg_draw, fg_bg_sample, labels_limit_, nms,
                       per_image_losses, proposal_rows, roi_align, rpn_proposals, sample_lists, RPN_PROPOSALS_MAX_BATCH)
-from .resnet_s import (Conv2d, NormalizeByChannelMeanStd, _accumulates_in_place, _ConvFn, _dense, _Flags, _FrozenBlockFn, _like_layout, _linear,
-                       dgrad_only, _own_conv_ok, _to_compute, _WgradStream)
+from .frozen import _FrozenBlockFn, _FrozenStageFn, _run_stage, _StageGraphs, stage_input_gradient      # (Detection's names for them: tests, bench.py)
+from .resnet_s import Conv2d, NormalizeByChannelMeanStd, _accumulates_in_place, _ConvFn, _dense, _Flags, _like_layout, _linear, _to_compute
 
 __all__ = ["Model", "ResNet101", "RegionProposalNetwork", "FrozenBatchNorm2d", "fasterrcnn_resnet101"]
 
@@ -102,16 +102,8 @@ class _AffineFn(torch.autograd.Function):
 class FrozenBatchNorm2d(nn.BatchNorm2d):
     """nn.BatchNorm2d's parameters and buffers (same state_dict keys), always normalising with the running statistics:
     Detection/model.py:46-47 puts every BatchNorm in eval mode at each forward and :31-35 switches their gradients off."""
-    _coef = None
-
     def _coefs(self):
-        ts = (self.running_var, self.running_mean, self.weight, self.bias)
-        key = tuple(t._version for t in ts) + tuple(t.data_ptr() for t in ts)
-        if self._coef is None or self._coef[0] != key:
-            invstd = torch.rsqrt(self.running_var.float() + self.eps)
-            self._coef = (key, ops.affine_coefs(self.running_mean.float().contiguous(), invstd, self.weight.detach().float().contiguous(),
-                                                self.bias.detach().float().contiguous()))
-        return self._coef[1]
+        return frozen.bn_coefs(self)
 
     def fused(self, x, residual=None, relu=False, conv_stats=None):
         return _AffineFn.apply(x, self._coefs(), residual, relu, (self.weight.detach(), self.bias.detach()))
@@ -178,302 +170,10 @@ class _GlobalMaxFn(torch.autograd.Function):
 
 
 # ------------------------------------------------------------------------------------------------------------- backbone
-def _block_plan(blk, x):
-    """The block's cached ops.FrozenBlockPlan for this input shape and autograd mode, or False where the one-node form does not
-    apply (then the layer-by-layer modules run).  Valid for one weight epoch (an optimizer step or a shadow refresh bumps
-    _Flags.weight_epoch: low-precision copies, transposed copies and coefficient rows are re-read then)."""
-    if blk._plan_epoch != _Flags.weight_epoch:
-        blk._plans, blk._plan_epoch = {}, _Flags.weight_epoch
-    pg = bool(_Flags.param_grads and torch.is_grad_enabled())
-    if blk._ver is None:      # tensors whose in-place edits (load_state_dict, manual surgery) must invalidate the cached pointers
-        blk._ver = [t for m in blk.modules() if isinstance(m, (nn.Conv2d, nn.BatchNorm2d))
-                    for t in ((m.weight,) if isinstance(m, nn.Conv2d) else (m.weight, m.bias, m.running_mean, m.running_var))]
-    key = (tuple(x.shape), x.device.index, pg, _Flags.wgrad_stash, _WgradStream.ON, _FrozenBlockFn.ON,
-           sum(t._version for t in blk._ver), blk._ver[0].data_ptr())
-    plan = blk._plans.get(key)
-    if plan is None:
-        plan = False
-        if _frozen_block_ok(blk, x):
-            convs = [blk.conv1, blk.conv2, blk.conv3, blk.downsample[0] if blk.downsample is not None else None]
-            ks = (blk.bn1._coefs(), blk.bn2._coefs(), blk.bn3._coefs(), blk.downsample[1]._coefs() if convs[3] is not None else None)
-            gws = [c.weight.grad if (c is not None and pg and c.weight.requires_grad) else None for c in convs]
-            plan = ops.frozen_bottleneck_plan(x, blk.conv1.out_channels, blk.conv2.stride[0],
-                                              tuple(None if c is None else c.lp_weight() for c in convs), ks,
-                                              tuple(None if c is None else c.lp_weight_t() for c in convs),
-                                              tuple(None if k is None else k[2] for k in ks), gws)
-        blk._plans[key] = plan
-    return plan
-
-
-def _stage_backward(plans, saved, g, want_dx):
-    """The blocks of a stage backwards.  Block i + 1's input is block i's output, so the first step of block i's backward — the
-    gradient masked by that output's ReLU, once as it is (the shortcut's share) and once times the last BatchNorm's alpha — rides in
-    the epilogue of block i + 1's last input-gradient launch (ops.frozen_bottleneck_bwd_plan `prev`): no launch of its own."""
-    pre = None
-    for i in range(len(plans) - 1, -1, -1):
-        x, a1, a2, out = saved[4 * i:4 * i + 4]
-        res = ops.frozen_bottleneck_bwd_plan(g if pre is None else None, x, a1, a2, out, plans[i], i > 0 or want_dx, pre=pre,
-                                             prev=plans[i - 1] if i > 0 else None)
-        if i > 0:
-            pre = res
-        else:
-            g = res
-    return g
-
-
-def _dgrad_plans(stage, out):
-    """The input-gradient-only launch plans of `stage` for the activations a one-node forward left on `out`, or None."""
-    saved = getattr(out, "_afan_stage_saved", None)
-    if saved is None or len(saved) != 4 * len(stage) - 1:          # (every activation but `out` itself: no reference cycle)
-        return None
-    with dgrad_only():
-        plans, probe = [], saved[0]
-        for blk in stage:
-            plan = _block_plan(blk, probe)
-            if not plan:
-                return None
-            plans.append(plan)
-            probe = _ShapeOnly((plan.n, plan.co, plan.ho, plan.wo), saved[0])
-    return plans
-
-
-def stage_input_gradient(stage, out, g=None):
-    """d(loss)/d(stage input) from g = d(loss)/d(stage output) and the activations a forward of `stage` left on its output tensor
-    `out` (`_FrozenStageFn`), with no parameter gradient touched (the dgrad-only launch plans) — what back-propagating g through
-    a SECOND forward of the same stage on the same input under `resnet_s.dgrad_only()` would give, bit for bit, without that
-    forward.  g None: only answers whether that is possible (True / False); None when it is not."""
-    plans = _dgrad_plans(stage, out)
-    if g is None:
-        return plans is not None
-    if plans is None:
-        return None
-    saved = out._afan_stage_saved + (out,)
-    last = saved[-1]
-    g = _like_layout(g, last)
-    if g.dtype != last.dtype:
-        g = g.to(last.dtype)
-    with torch.no_grad():
-        return _stage_backward(plans, saved, g, True)
-
-
-class _FrozenStageFn(torch.autograd.Function):
-    """A whole stage (layer1 .. layer4: 3 / 4 / 23 / 3 frozen-BatchNorm bottlenecks) as ONE autograd node: the same native calls
-    as one `_FrozenBlockFn` per block, issued in a loop — the per-node cost of `Function.apply` and of the engine's scheduling
-    (~50 us a block and direction on this host) is paid once per stage instead of 33 times per backbone pass, 27 passes per
-    Detection iteration."""
-
-    @staticmethod
-    def forward(ctx, x, plans, *params):
-        saved = []
-        for plan in plans:
-            out, a1, a2 = ops.frozen_bottleneck_fwd_plan(x, plan)
-            saved += [x, a1, a2, out]
-            x = out
-        ctx.plans = plans
-        ctx.save_for_backward(*saved)
-        if any(ctx.needs_input_grad):             # (references only, and only where a graph keeps them alive anyway:
-            # stage_input_gradient reuses a clean pass's activations.)  Everything BUT the output itself: a tuple holding
-            # `x` on `x.__dict__` is a cycle that only the cyclic collector frees — the stage's activations would outlive
-            # their graph by however long that takes (ADVICE round 4: ~4 GB resident in a CPU simulation)
-            x._afan_stage_saved = tuple(saved[:-1])
-        return x
-
-    @staticmethod
-    def backward(ctx, g):
-        saved, plans = ctx.saved_tensors, ctx.plans
-        last = saved[-1]
-        g = _like_layout(g, last)
-        if g.dtype != last.dtype:
-            g = g.to(last.dtype)
-        g = _stage_backward(plans, saved, g, ctx.needs_input_grad[0])
-        return (g, None) + (None,) * (len(ctx.needs_input_grad) - 2)
-
-
-class _StageInst:
-    __slots__ = ("x", "out", "saved", "fwd", "bwd", "g", "dx", "busy", "plans", "want_dx")
-
-
-class _StageGraphs:
-    """Captured hipGraphs of whole backbone stages (forward, and backward on first use) per (stage, input shape, plan signature,
-    gradient mode): the Detection iteration is shaped by its proposals everywhere EXCEPT in the backbone, whose 27 passes per
-    iteration issue the same ~30 native calls each from Python — replayed here as one graph launch each way.  An instance owns
-    its activations (static buffers of the graph's pool), so a forward whose backward is still pending keeps its instance
-    busy and the next forward of the same kind takes (or captures) another; `begin_iteration()` frees them all (forwards whose
-    graph autograd never walks back: the detached head passes, the ROI dict's pass).  More than MAX_INST busy instances of one
-    kind (a caller that never calls begin_iteration): the eager stage node runs instead."""
-    # Measured (MI355X, 600 x 904, 20 iterations, interleaved): 123.7 / 120.4 ms replayed against 119.9 / 111.9 ms eager, losses
-    # identical — after the per-block launch plans the backbone's launch cost is no longer what the iteration waits for (its ~50
-    # host reads of proposal / sample counts are): OFF by default, AFAN_DET_GRAPHS=1 switches it on.
-    ON = os.environ.get("AFAN_DET_GRAPHS", "0") == "1"
-    MAX_INST = 12
-    cache = {}
-    warm = {}                                  # key -> eager runs seen (workspaces must exist before a capture)
-
-    @classmethod
-    def begin_iteration(cls):
-        for insts in cls.cache.values():
-            for it in insts:
-                it.busy = False
-
-    @classmethod
-    def get(cls, stage, x, plans, want_dx):
-        key = (id(stage), want_dx, tuple(p.sig for p in plans))
-        if cls.warm.get(key, 0) < 2:           # two eager passes first
-            cls.warm[key] = cls.warm.get(key, 0) + 1
-            return None
-        insts = cls.cache.setdefault(key, [])
-        for it in insts:
-            if not it.busy:
-                return it
-        if len(insts) >= cls.MAX_INST or torch.cuda.is_current_stream_capturing():
-            return None
-        it = cls._capture_fwd(x, plans, want_dx)
-        insts.append(it)
-        return it
-
-    @classmethod
-    def _capture_fwd(cls, x, plans, want_dx):
-        it = _StageInst()
-        it.plans, it.want_dx, it.busy, it.bwd, it.g, it.dx = plans, want_dx, False, None, None, None
-        it.x = torch.empty_like(x)
-        torch.cuda.synchronize(x.device)
-        g = torch.cuda.CUDAGraph()
-        # A PRIVATE memory pool per graph: instances are replayed in any order and keep their activations from forward to backward,
-        # so a temporary freed inside one capture must never be handed to another graph as something long-lived (a shared pool
-        # assumes graphs replay in capture order).
-        with torch.no_grad(), ops.capturing(g):
-            cur, saved = it.x, []
-            for plan in plans:
-                out, a1, a2 = ops.frozen_bottleneck_fwd_plan(cur, plan)
-                saved += [cur, a1, a2, out]
-                cur = out
-        it.saved, it.out, it.fwd = saved, cur, g
-        return it
-
-    @classmethod
-    def capture_bwd(cls, it):
-        it.g = torch.empty_like(it.out)
-        torch.cuda.synchronize(it.out.device)
-        g = torch.cuda.CUDAGraph()
-        with torch.no_grad(), ops.capturing(g):       # (runs on the engine's thread; private pool)
-            cur = _stage_backward(it.plans, it.saved, it.g, it.want_dx)
-        it.dx, it.bwd = cur, g
-
-
-class _GraphedStageFn(torch.autograd.Function):
-    """`_FrozenStageFn` as two graph replays (see _StageGraphs)."""
-
-    @staticmethod
-    def forward(ctx, x, inst, *params):
-        inst.x.copy_(x, non_blocking=True)
-        inst.fwd.replay()
-        inst.busy = True
-        ctx.inst = inst
-        return inst.out.detach()
-
-    @staticmethod
-    def backward(ctx, g):
-        it = ctx.inst
-        if it.bwd is None:
-            _StageGraphs.capture_bwd(it)
-        it.g.copy_(g, non_blocking=True)          # (any dtype / layout of g: copy_ converts)
-        it.bwd.replay()
-        it.busy = False
-        dx = it.dx.detach() if (it.want_dx and it.dx is not None) else None
-        return (dx, None) + (None,) * (len(ctx.needs_input_grad) - 2)
-
-
-def _run_stage(stage, x):
-    """`stage(x)` for an nn.Sequential of Bottlenecks: one `_FrozenStageFn` node when every block takes the one-call form at the
-    shape it will see, else block by block."""
-    if not (_FrozenStageFn.ON and x.dtype == torch.bfloat16 and x.dim() == 4 and x.is_cuda and x.is_contiguous(memory_format=torch.channels_last)):
-        return stage(x)
-    plans, shape_probe = [], x
-    for blk in stage:
-        plan = _block_plan(blk, shape_probe)
-        if not plan:
-            return stage(x)
-        plans.append(plan)
-        shape_probe = _ShapeOnly((plan.n, plan.co, plan.ho, plan.wo), x)
-    params = getattr(stage, "_stage_params", None)
-    if params is None:
-        params = stage._stage_params = tuple(p for blk in stage for p in blk._block_params())
-    if _StageGraphs.ON:
-        grad_on = torch.is_grad_enabled()
-        inst = _StageGraphs.get(stage, x, plans, bool(grad_on and x.requires_grad))
-        if inst is not None:
-            if not grad_on:                          # (no graph to build: replay and hand the buffer out; freed by begin_iteration)
-                inst.x.copy_(x, non_blocking=True)
-                inst.fwd.replay()
-                inst.busy = True
-                return inst.out.detach()
-            return _GraphedStageFn.apply(x, inst, *params)
-    return _FrozenStageFn.apply(x, tuple(plans), *params)
-
-
-class _ShapeOnly:
-    """What `_block_plan` / `_frozen_block_ok` look at of a block's input, for a tensor that does not exist yet (the previous
-    block's output inside a stage node)."""
-    __slots__ = ("shape", "device", "dtype", "is_cuda")
-
-    def __init__(self, shape, like):
-        self.shape, self.device, self.dtype, self.is_cuda = torch.Size(shape), like.device, like.dtype, like.is_cuda
-
-    def dim(self):
-        return len(self.shape)
-
-    def is_contiguous(self, memory_format=None):
-        return True
-
-
-_FrozenStageFn.ON = os.environ.get("AFAN_DET_STAGE_NODE", "1") != "0"      # 0: one node per block (A/B)
-
-
-def _frozen_block_ok(blk, x):
-    """bf16 channels-last map, every convolution of the block on the tuned kernels, trainable weights owned by the arena."""
-    if not (_FrozenBlockFn.ON and x.is_cuda and x.dtype == torch.bfloat16 and x.dim() == 4
-            and x.is_contiguous(memory_format=torch.channels_last) and blk.conv1.compute_dtype == torch.bfloat16):
-        return False
-    convs = [blk.conv1, blk.conv2, blk.conv3] + ([blk.downsample[0]] if blk.downsample is not None else [])
-    for c in convs:
-        if c.bias is not None or not _own_conv_ok(x, c.lp_weight(), c.stride, c.padding, c.dilation):
-            return False
-        if not ops.conv_wgrad_supported(c.in_channels, c.out_channels, c.kernel_size[0], c.stride[0]):
-            return False
-        if _Flags.param_grads and torch.is_grad_enabled() and c.weight.requires_grad and not (
-                _accumulates_in_place(c.weight) and (c.weight.grad.is_contiguous(memory_format=torch.channels_last) or c.kernel_size[0] == 1)):
-            return False
-    return not _Flags.wgrad_stash and not _WgradStream.ON
-
-
-_FrozenBlockFn.ON = os.environ.get("AFAN_DET_BLOCK_NODE", "1") != "0"      # 0: layer-by-layer autograd nodes (A/B)
-
-
-class Bottleneck(nn.Module):
+class Bottleneck(frozen.FrozenBottleneck):
     """backbone/resnet101_ori.py:78-127 (torchvision v1.5: the 3x3 carries the stride)."""
-    expansion = 4
-
-    def __init__(self, inplanes, planes, stride=1, downsample=None):
-        super().__init__()
-        self.conv1 = Conv2d(inplanes, planes, kernel_size=1, stride=1, bias=False)
-        self.bn1 = FrozenBatchNorm2d(planes)
-        self.conv2 = Conv2d(planes, planes, kernel_size=3, stride=stride, padding=1, bias=False)
-        self.bn2 = FrozenBatchNorm2d(planes)
-        self.conv3 = Conv2d(planes, planes * 4, kernel_size=1, stride=1, bias=False)
-        self.bn3 = FrozenBatchNorm2d(planes * 4)
-        self.relu = nn.ReLU(inplace=True)
-        self.downsample = downsample
-        self.stride = stride
-
-    _plans, _plan_epoch, _params, _ver = None, -1, None, None
-
-    def __getstate__(self):
-        # launch-plan caches hold ctypes pointer objects (not picklable, and meaningless in a copy): a deepcopy / torch.save of
-        # the module starts without them and rebuilds them on its first forward
-        d = dict(self.__dict__)
-        for k in ("_plans", "_plan_epoch", "_params", "_ver"):
-            d.pop(k, None)
-        return d
+    norm = FrozenBatchNorm2d
+    _params = None
 
     def _block_params(self):
         if self._params is None:
@@ -481,11 +181,15 @@ class Bottleneck(nn.Module):
                 ((self.downsample[0].weight,) if self.downsample is not None else ())
         return self._params
 
+    def frozen_plan(self, x):
+        """The block's launch plan for the bf16 channels-last map `x` (frozen.block_plan: weight gradients through the plan), or None."""
+        return frozen.block_plan(self, x, trains=True) if _FrozenBlockFn.ON else None
+
     def forward(self, x):
         x = _to_compute(x, self.conv1.compute_dtype)
         if x.dtype == torch.bfloat16 and x.dim() == 4 and x.is_cuda and x.is_contiguous(memory_format=torch.channels_last):
-            plan = _block_plan(self, x)
-            if plan:
+            plan = self.frozen_plan(x)
+            if plan is not None:
                 return _FrozenBlockFn.apply(x, self, plan, *self._block_params())
         out = self.bn1.fused(self.conv1(x), None, True)
         out = self.bn2.fused(self.conv2(out), None, True)
@@ -493,47 +197,16 @@ class Bottleneck(nn.Module):
         return self.bn3.fused(self.conv3(out), res, True)
 
 
-class ResNet101(nn.Module):
+class ResNet101(BottleneckResNet):
     """backbone/resnet101_ori.py:130-262 with layers (3, 4, 23, 3): `forward(input_dict)` returns the feature map after
     layer `out_idx` (flag 'head'), runs the remaining layers up to layer3 from `adv` (flag 'tail'), or the whole stem ..
     layer3 (flag 'clean').  layer4 belongs to the module (and its state_dict) but is applied by the detection head."""
 
     def __init__(self, layers=(3, 4, 23, 3), num_classes=1000):
-        super().__init__()
-        self.normal = NormalizeByChannelMeanStd(mean=[0.485, 0.456, 0.406], std=[0.229, 0.224, 0.225])
-        self.inplanes = 64
-        self.conv1 = StemConv(3, 64, kernel_size=7, stride=2, padding=3, bias=False)
-        self.bn1 = FrozenBatchNorm2d(64)
-        self.relu = nn.ReLU(inplace=True)
-        self.maxpool = MaxPool2d(kernel_size=3, stride=2, padding=1)
-        self.layer1 = self._make_layer(64, layers[0])
-        self.layer2 = self._make_layer(128, layers[1], stride=2)
-        self.layer3 = self._make_layer(256, layers[2], stride=2)
-        self.layer4 = self._make_layer(512, layers[3], stride=2)
+        super().__init__(Bottleneck, layers)
         self.avgpool = nn.AdaptiveAvgPool2d((1, 1))
         self.fc = nn.Linear(512 * 4, num_classes)
-        for m in self.modules():                                            # resnet101_ori.py:166-171
-            if isinstance(m, nn.Conv2d):
-                nn.init.kaiming_normal_(m.weight, mode="fan_out", nonlinearity="relu")
-            elif isinstance(m, nn.BatchNorm2d):
-                nn.init.constant_(m.weight, 1)
-                nn.init.constant_(m.bias, 0)
-
-    def _make_layer(self, planes, blocks, stride=1):
-        downsample = None
-        if stride != 1 or self.inplanes != planes * 4:
-            downsample = nn.Sequential(Conv2d(self.inplanes, planes * 4, kernel_size=1, stride=stride, bias=False),
-                                       FrozenBatchNorm2d(planes * 4))
-        layers = [Bottleneck(self.inplanes, planes, stride, downsample)]
-        self.inplanes = planes * 4
-        for _ in range(1, blocks):
-            layers.append(Bottleneck(self.inplanes, planes))
-        return nn.Sequential(*layers)
-
-    def _stem(self, x):
-        x = self.normal(x)
-        x = self.bn1.fused(self.conv1(x), None, True)
-        return self.maxpool(x)
+        self._init_weights()                                                # resnet101_ori.py:166-171 (behind fc's own draw)
 
     def head_features(self, x, idxs=(1, 2, 3)):
         """The feature maps after layers `idxs` from ONE pass, detached: what the three `flag: 'head'` calls of

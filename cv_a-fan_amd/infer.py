@@ -19,7 +19,7 @@ convolution, the whole attack one hipGraph per batch shape."""
 import torch
 import torch.nn as nn
 
-from . import ops, pgd, resnet_s
+from . import frozen, ops, pgd, resnet_s
 from .deeplab import StemConv, _Stem7Fn
 
 
@@ -114,8 +114,7 @@ class _Conv:
                 self.w = torch.empty_like(w, memory_format=torch.channels_last)
             self.w.copy_(w)
         wt, b, rm, rv = _main_bn(self.bn)
-        invstd = torch.rsqrt(rv + self.bn.eps)          # BatchNorm2d.fused's expression
-        c = ops.affine_coefs(rm, invstd, wt, b)
+        c = frozen.affine_coefs(wt, b, rm, rv, self.bn.eps)
         if self.coefs is None:
             self.coefs = torch.empty_like(c)
         self.coefs.copy_(c)

@@ -636,7 +636,7 @@ def bn_train_forward_dual(xa, bna, sta, mom_a, xb, bnb, stb, mom_b):
 class FrozenBlockPlan:
     """Everything about one frozen bottleneck at one input shape that does not change between optimizer steps — sizes, scratch
     requirements, the ctypes pointer objects of its weights / transposed weights / coefficient rows / gradient views — gathered
-    once (det_model._block_plan) so that a block's forward and backward are a few allocations and ONE ctypes call each: the
+    once (frozen.block_plan) so that a block's forward and backward are a few allocations and ONE ctypes call each: the
     Detection iteration runs 388 block forwards and ~250 block backwards, and at ~100 us of Python per call (eligibility
     checks, 20 pointer wrappers, four workspace-size queries) the host, not the GPU, set its pace."""
     __slots__ = ("n", "cin", "h", "w", "ho", "wo", "planes", "co", "stride", "fwd_scratch", "bwd_scratch", "wgrad_ws", "w_ptrs", "k_ptrs",
@@ -688,7 +688,7 @@ def frozen_bottleneck_fwd_plan(x, p):
 
 
 def frozen_bottleneck_bwd_plan(g, x, a1, a2, out, p, want_dx, pre=None, prev=None):
-    """One block's backward.  Inside a stage's chain (det_model._stage_backward): `pre` = (d3, dres), this block's first backward
+    """One block's backward.  Inside a stage's chain (frozen._stage_backward): `pre` = (d3, dres), this block's first backward
     step as the block behind it left it (g is then None); `prev` = the plan of the block in front, whose first step this call's
     last input-gradient launch performs on the way out — returns that block's (d3, dres) instead of dx."""
     lib = _lib.load()

@@ -830,32 +830,6 @@ class _BlockFn(torch.autograd.Function):
         return (dx, None, None) + (None,) * (len(ctx.needs_input_grad) - 3)
 
 
-class _FrozenBlockFn(torch.autograd.Function):
-    """A frozen-BatchNorm bottleneck (Detection: backbone/resnet101_ori.py:78-127; Segmentation: DeepLab's eval-mode bottlenecks,
-    atrous ones included, deeplab.Bottleneck) as ONE autograd node on the bf16 channels-last path:
-    the same launches as the layer-by-layer form — three (four) tuned convolutions, three (four) fused affine(+residual)
-    (+ReLU) launches forward; affine backward, input gradient and weight gradient per layer backward, the identity shortcut's
-    gradient added in the first convolution's dgrad epilogue — but one `Function.apply`, one backward node and ONE native call
-    each way (ops.frozen_bottleneck_fwd_plan / _bwd_plan: afan_frozen_bottleneck_fwd / _bwd issue the launches from C++) instead of seven of each: the Detection
-    iteration is bound by Python dispatch (2 600 applies per iteration before this node)."""
-
-    @staticmethod
-    def forward(ctx, x, blk, plan, *params):
-        out, a1, a2 = ops.frozen_bottleneck_fwd_plan(x, plan)
-        ctx.plan = plan
-        ctx.save_for_backward(x, a1, a2, out)
-        return out
-
-    @staticmethod
-    def backward(ctx, g):
-        x, a1, a2, out = ctx.saved_tensors
-        g = _like_layout(g, out)
-        if g.dtype != out.dtype:
-            g = g.to(out.dtype)
-        dx = ops.frozen_bottleneck_bwd_plan(g, x, a1, a2, out, ctx.plan, ctx.needs_input_grad[0])
-        return (dx, None, None) + (None,) * (len(ctx.needs_input_grad) - 3)
-
-
 def _block_fast_path_ok(blk, x):
     """bf16 channels-last training step with every convolution of the block on the library's MFMA kernels and every
     parameter's gradient buffer owned by the arena (or parameter gradients switched off, as inside PGD)."""
@@ -938,11 +912,12 @@ class Conv2d(nn.Conv2d):
     compute_dtype = torch.float32
     _lp = None
     _lp_version = -1
+    _arena_shadow = None      # (a ParamArena's view, set on the instance; the class default keeps the lookup off nn.Module.__getattr__)
 
     def lp_weight(self):
         if self.compute_dtype == torch.float32:
             return self.weight
-        shadow = getattr(self, "_arena_shadow", None)
+        shadow = self._arena_shadow
         if shadow is not None:  # kept fresh by afan_sgd_step (ParamArena)
             return shadow
         if self._lp is None or self._lp_version != self.weight._version or self._lp.device != self.weight.device:
@@ -1014,7 +989,7 @@ class BatchNorm2d(nn.BatchNorm2d):
         self._branch = branch
 
     def train(self, mode=True):
-        _Flags.bn_epoch += 1         # (caches of this layer's frozen affine, deeplab._bn_coefs, end here)
+        _Flags.bn_epoch += 1         # (caches of this layer's frozen affine, frozen.bn_coefs / block_plan, end here)
         return super().train(mode)
 
     def fused(self, x, residual=None, relu=False, conv_stats=None):

@@ -231,19 +231,19 @@ def test_tiled_convolution_kernels_use_no_scratch():
 
 
 def test_detection_bottleneck_copies_without_its_launch_plans(pkg):
-    """det_model.Bottleneck caches launch plans (ctypes pointer objects) on the module; copy.deepcopy / pickling must still work
+    """det_model.Bottleneck caches launch plans (ctypes pointer objects) on the module (frozen.block_plan); copy.deepcopy / pickling must still work
     (EMA copies, torch.save of a module) and the copy must start without the cache."""
     import copy
     import ctypes
     import pickle
     blk = pkg.det_model.Bottleneck(64, 16)
-    blk._plans, blk._plan_epoch = {"key": ctypes.c_void_p(1234)}, 7
+    blk._frozen_plans = {"key": ([7], ctypes.c_void_p(1234))}
     blk._params = tuple(blk.parameters())
     c = copy.deepcopy(blk)
-    assert c._plans is None and c._plan_epoch == -1 and c._params is None
+    assert "_frozen_plans" not in c.__dict__ and c._params is None
     assert [tuple(p.shape) for p in c.parameters()] == [tuple(p.shape) for p in blk.parameters()]
-    assert pickle.loads(pickle.dumps(blk))._plans is None
-    assert blk._plans is not None                      # the original keeps its cache
+    assert "_frozen_plans" not in pickle.loads(pickle.dumps(blk)).__dict__
+    assert blk._frozen_plans                           # the original keeps its cache
 
 
 def test_padded_nms_contract_rejects_cpu_and_device_is_checked_first(pkg):

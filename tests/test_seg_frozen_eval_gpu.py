@@ -149,7 +149,7 @@ def test_other_paths_never_reach_the_frozen_forms(pkg, gpu, models, batch, monke
     drop = model.classifier.aspp.project[3]
     p_drop = drop.p
 
-    def boom(bn):
+    def boom(bn, cache=True):
         raise AssertionError("a frozen form ran on the %s path" % config)
 
     try:
@@ -165,7 +165,7 @@ def test_other_paths_never_reach_the_frozen_forms(pkg, gpu, models, batch, monke
             model.load_state_dict(state)
             monkeypatch.setattr(pkg.deeplab, "FROZEN_EVAL", on)
             if on:
-                monkeypatch.setattr(pkg.deeplab, "_bn_coefs", boom)
+                monkeypatch.setattr(pkg.frozen, "bn_coefs", boom)
             with torch.no_grad():
                 outs.append(model({"x": x, "adv": None, "out_idx": 0, "flag": "clean"}))
         assert bool(torch.isfinite(outs[0].float()).all())
