@@ -1,5 +1,5 @@
 // PGD feature-ascent kernels for gfx950: sign-step (+ L-inf projection) fused with the per-sample
-// perturbation norms and the bf16 shadow copy; host-noise random start.
+// perturbation norms and the bf16 shadow copy; host-noise random start; device-drawn random start (Philox4x32-10).
 // Reference behaviour restated (not translated) from Classification/attack_algo.py:9-19,35-36,41-56
 // and Classification/main_perturb.py:188-192.  All of these are HBM-bound streaming kernels:
 // 16 B per lane per access, grid-stride, >= 2048 workgroups when the tensor allows it.
@@ -235,6 +235,99 @@ __global__ __launch_bounds__(BLOCK) void axpy_noise_kernel(float* __restrict__ x
     }
 }
 
+// ---- device-drawn random start ----------------------------------------------------------------------
+// Philox4x32-10 (Salmon et al., "Parallel random numbers: as easy as 1, 2, 3", SC'11): counter (q, 0) with q = e >> 2 the
+// element's block of four LOGICAL (NCHW) indices, key = the two halves of the seed, output word e & 3.
+__device__ __forceinline__ void philox4x32_10(uint64_t q, uint64_t seed, uint32_t (&o)[4]) {
+    uint32_t c0 = (uint32_t)q, c1 = (uint32_t)(q >> 32), c2 = 0u, c3 = 0u;
+    uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
+        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
+        c1 = (uint32_t)p1;
+        c3 = (uint32_t)p0;
+        c0 = n0;
+        c2 = n2;
+        k0 += 0x9E3779B9u;
+        k1 += 0xBB67AE85u;
+    }
+    o[0] = c0; o[1] = c1; o[2] = c2; o[3] = c3;
+}
+
+__device__ __forceinline__ float rand_start_one(float x, uint32_t word, float eps) {
+    const float u = (float)(word >> 8) * 5.9604644775390625e-08f;  // 24 bits * 2^-24: exact, in [0, 1)
+    float t = 2.0f * u;  // afan_axpy_noise's roundings: each operation on its own, one add, no FMA
+    t = t - 1.0f;
+    t = t * eps;
+    return x + t;
+}
+
+// One lane per four consecutive elements IN MEMORY (one 16-byte load, one 16-byte store, one 8-byte shadow store).  NHWC = false:
+// memory order is logical order, the four share one Philox block.  NHWC = true: each element's logical index is rebuilt from its
+// (pixel, channel) position — a block per element, four times the integer work of a kernel that stays bound by its 8 (10) bytes per
+// element.  I: the index type of that decomposition (32-bit while the tensor allows it: 64-bit divisions cost tens of instructions).
+template <bool NHWC, typename I>
+__global__ __launch_bounds__(BLOCK) void pgd_rand_start_kernel(const float* __restrict__ x, float* __restrict__ x_adv,
+                                                               uint16_t* __restrict__ shadow, int64_t total, int64_t c,
+                                                               int64_t hw, float eps, const uint64_t* __restrict__ state,
+                                                               uint64_t* __restrict__ used) {
+    const uint64_t seed = state[0];
+    if (used && used != state && blockIdx.x == 0 && threadIdx.x == 0) used[0] = seed;
+    const int64_t nthreads = (int64_t)gridDim.x * BLOCK;
+    for (int64_t v = (int64_t)blockIdx.x * BLOCK + threadIdx.x; (v << 2) < total; v += nthreads) {
+        const int64_t i = v << 2;
+        uint32_t word[4];
+        if (!NHWC) {
+            uint32_t o[4];
+            philox4x32_10((uint64_t)v, seed, o);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) word[k] = o[k];
+        } else {
+            const I C = (I)c, HW = (I)hw;
+            I pix = (I)i / C, ch = (I)i - pix * C;   // memory index i = (img * HW + p) * C + ch
+            I img = pix / HW, p = pix - img * HW;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const uint64_t e = ((uint64_t)img * (uint64_t)c + (uint64_t)ch) * (uint64_t)hw + (uint64_t)p;
+                uint32_t o[4];
+                philox4x32_10(e >> 2, seed, o);
+                const uint32_t s = (uint32_t)e & 3u;
+                word[k] = s == 0 ? o[0] : s == 1 ? o[1] : s == 2 ? o[2] : o[3];
+                if (++ch == C) {
+                    ch = 0;
+                    if (++p == HW) { p = 0; ++img; }
+                }
+            }
+        }
+        if (i + 4 <= total) {
+            float xa[4];
+            Elt<float>::ldv(x + i, xa);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) xa[k] = rand_start_one(xa[k], word[k], eps);
+            Elt<float>::stv(x_adv + i, xa);
+            if (shadow) {
+                u16x4 s;
+#pragma unroll
+                for (int k = 0; k < 4; ++k) s[k] = f2bf(xa[k]);
+                *reinterpret_cast<u16x4*>(shadow + i) = s;
+            }
+        } else {  // ragged tail: total % 4 elements, by the one lane that owns them
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                if (i + k < total) {
+                    const float t = rand_start_one(x[i + k], word[k], eps);
+                    x_adv[i + k] = t;
+                    if (shadow) shadow[i + k] = f2bf(t);
+                }
+            }
+        }
+    }
+}
+
+// the generator's step, afan_seg.hip's dropout_advance_kernel: one lane, after the draw on the same stream
+__global__ void noise_advance_kernel(uint64_t* state) { state[0] = state[0] * 6364136223846793005ull + 1442695040888963407ull; }
+
 // attack_algo.py:9-19 with arbitrary bound tensors
 __global__ __launch_bounds__(BLOCK) void tensor_clamp_kernel(float* __restrict__ t, const float* __restrict__ lo,
                                                              const float* __restrict__ hi, int64_t n) {
@@ -439,6 +532,39 @@ int afan_axpy_noise(float* x_adv, const float* u, int64_t n, float eps, uint16_t
     AFAN_PROF("axpy_noise_kernel", n * (12.0 + (shadow_bf16 ? 2 : 0)), (hipStream_t)stream);
     axpy_noise_kernel<<<grid, BLOCK, 0, (hipStream_t)stream>>>(x_adv, u, n, eps, shadow_bf16, vec);
     AFAN_LAUNCH_CHECK();
+    return AFAN_OK;
+}
+
+int afan_pgd_rand_start(const float* x, float* x_adv, uint16_t* shadow_bf16, int64_t n, int64_t c, int64_t h, int64_t w,
+                        int layout, float eps, uint64_t* state, uint64_t* used, int advance, afan_stream_t stream) {
+    if (n < 0 || c < 0 || h < 0 || w < 0 || (layout != AFAN_NCHW && layout != AFAN_NHWC)) return AFAN_ESHAPE;
+    if (n == 0 || c == 0 || h == 0 || w == 0) return AFAN_OK;
+    const int64_t lim = INT64_MAX >> 2;  // (the kernel shifts element indices left by two)
+    if (c > lim / n || h > lim / (n * c) || w > lim / (n * c * h)) return AFAN_ESHAPE;
+    if (!x || !x_adv || !state) return AFAN_ENULL;
+    if (!aligned(x, 16) || !aligned(x_adv, 16) || (shadow_bf16 && !aligned(shadow_bf16, 16)) || !aligned(state, 8) ||
+        (used && !aligned(used, 8)))
+        return AFAN_EALIGN;
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t total = n * c * h * w, hw = h * w;
+    const bool nhwc = layout == AFAN_NHWC && c > 1 && hw > 1;  // (one channel or one pixel: both layouts are the same memory)
+    // one group of four per lane up to 67 M elements: under the usual 2048-workgroup cap a 4 x 3 x 513 x 513 batch is 1.5 rounds of
+    // the grid, the second half empty (measured with the generator step behind it: 14.9 -> 13.3 us per start)
+    const int grid = grid_for((total + 3) / 4, BLOCK, 1 << 16);
+    {
+        AFAN_PROF("pgd_rand_start_kernel", total * (8.0 + (shadow_bf16 ? 2 : 0)), st);
+        if (!nhwc)
+            pgd_rand_start_kernel<false, uint32_t><<<grid, BLOCK, 0, st>>>(x, x_adv, shadow_bf16, total, c, hw, eps, state, used);
+        else if (total + 4 < ((int64_t)1 << 32))
+            pgd_rand_start_kernel<true, uint32_t><<<grid, BLOCK, 0, st>>>(x, x_adv, shadow_bf16, total, c, hw, eps, state, used);
+        else
+            pgd_rand_start_kernel<true, uint64_t><<<grid, BLOCK, 0, st>>>(x, x_adv, shadow_bf16, total, c, hw, eps, state, used);
+        AFAN_LAUNCH_CHECK();
+    }
+    if (advance) {
+        noise_advance_kernel<<<1, 1, 0, st>>>(state);
+        AFAN_LAUNCH_CHECK();
+    }
     return AFAN_OK;
 }
 

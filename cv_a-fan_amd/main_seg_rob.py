@@ -76,6 +76,20 @@ def load_overlap(model, path):
     return len(overlap_dict), len(model_state_dict)
 
 
+def val_loader(opts, device):
+    """The validation split as a SegDeviceLoader -> (loader, number of images); main_advtrain.py scores the same one."""
+    if opts.dataset.lower() == "cityscapes":
+        opts.batch_size = opts.val_batch_size                                    # (build_loaders builds the training loader too)
+        _, loader, _, n_val = main_ori.build_loaders(opts, device)
+        return loader, n_val
+    if opts.synthetic:
+        split = seg_entry.synthetic_split(opts)
+        images, labels = split.images, split.labels
+    else:
+        images, labels = seg_data.load_voc(opts.data_root, opts.year, "val")
+    return seg_data.SegDeviceLoader(images, labels, opts.val_batch_size, device, False, opts.crop_size, crop_val=opts.crop_val), len(images)
+
+
 def _settings(opts):
     print("Attack Settings: Step[{}] Gamma[{}] Eps[{}] Randinit[{}] Clip[{}]"
           .format(opts.steps_pgd, opts.gamma_pgd, opts.eps_pgd, opts.randinit_pgd, opts.clip_pgd))
@@ -97,17 +111,7 @@ def main(argv=None):
     model.to(device)
     model.eval()
 
-    if opts.dataset.lower() == "cityscapes":
-        opts.batch_size = opts.val_batch_size                                    # (build_loaders builds the training loader too)
-        _, loader, _, n_val = main_ori.build_loaders(opts, device)
-    else:
-        if opts.synthetic:
-            split = seg_entry.synthetic_split(opts)
-            images, labels = split.images, split.labels
-        else:
-            images, labels = seg_data.load_voc(opts.data_root, opts.year, "val")
-        loader = seg_data.SegDeviceLoader(images, labels, opts.val_batch_size, device, False, opts.crop_size, crop_val=opts.crop_val)
-        n_val = len(images)
+    loader, n_val = val_loader(opts, device)
     print("Dataset: %s, Val set: %d" % (opts.dataset, n_val))
 
     metrics = seg_eval.StreamSegMetrics(opts.num_classes, device)

@@ -365,6 +365,39 @@ def axpy_noise_(x_adv, u, eps, shadow=None):
     return x_adv
 
 
+_noise_state = {}
+
+
+def noise_state(device):
+    """The device-resident generator of afan_pgd_rand_start for this device (one uint64, seeded from torch's CPU generator on first
+    use).  A word of its own: a random start must not move afan_dropout's stream, nor dropout the random start's."""
+    st = _noise_state.get(device.index)
+    if st is None:
+        seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+        st = _noise_state[device.index] = torch.tensor([seed], dtype=torch.int64, device=device)
+    return st
+
+
+def pgd_rand_start(x, eps, shadow=None, state=None, advance=True):
+    """Out of place, one launch: (x + (2u - 1) * eps with u drawn on the device, used) — `used` [1] int64 holds the seed of this call,
+    from which u can be re-derived (Philox4x32-10 over the logical NCHW index: include/afan_hip.h); `state` [1] int64 (default: the
+    device's noise_state) advances afterwards when `advance`.  `shadow`: receives the bf16 copy of the result."""
+    lib = _lib.load()
+    _need(x, "x", torch.float32)
+    state = noise_state(x.device) if state is None else _need(state, "state", torch.int64)
+    if state.numel() != 1:
+        raise ValueError("state must hold one int64 word")
+    if shadow is not None:
+        _need(shadow, "shadow", torch.bfloat16)
+    x_adv = torch.empty_like(x)
+    _same_layout(x, x_adv, shadow)
+    used = torch.empty(1, dtype=torch.int64, device=x.device)
+    n, c, h, w = x.shape if x.dim() == 4 else (x.numel(), 1, 1, 1)
+    check(lib.afan_pgd_rand_start(_ptr(x), _ptr(x_adv), _ptr(shadow), n, c, h, w, layout_of(x), float(eps), _ptr(state), _ptr(used),
+                                  int(bool(advance)), _stream(x)), "afan_pgd_rand_start")
+    return x_adv, used
+
+
 def cast_bf16(src, out=None):
     lib = _lib.load()
     _need(src, "src", torch.float32)

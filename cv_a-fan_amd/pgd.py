@@ -1,6 +1,6 @@
 """The sign-PGD core every attack path is built from (attack_algo, seg_attack_algo, det_ops, det_attack_algo, infer.Attacker):
 
-    start(x, eps, randinit, u)            fp32 x in its own dense layout, its clone x_adv (+ the host-drawn random start)
+    start(x, eps, randinit, u, noise)     fp32 x in its own dense layout, its clone x_adv (+ the host- or device-drawn random start)
     input_gradient(loss_of, leaves)       d loss / d leaves with parameter gradients switched off
     step(x_adv, grad, gamma, x, eps, clip)   x_adv += gamma * sign(grad) [projected onto the eps-ball around x]: one launch
     ascend(x_adv, loss_of, ...)           input_gradient at x_adv, then step
@@ -13,13 +13,23 @@ from . import ops
 from .resnet_s import _dense, _like_layout, dgrad_only
 
 
-def start(x, eps, randinit, u=None):
+def start(x, eps, randinit, u=None, noise="host"):
     """(x as detached fp32, x_adv = its clone), both dense in x's own layout (channels-last feature maps stay channels-last: no
     transposes per step).  randinit: x_adv += (2u - 1) * eps with u = torch.rand(x.shape) from the CPU default generator, as the
-    reference draws it, unless the caller hands its own draw in (host or device)."""
+    reference draws it, unless the caller hands its own draw in (host or device).  noise="device" with randinit: x_adv and its
+    start come out of ONE launch that draws u itself from ops.noise_state (ops.pgd_rand_start; capturable, a replay draws afresh);
+    the seed it used ([1] int64 on the device) rides on the result as `x_adv._afan_noise_seed`."""
+    if noise not in ("host", "device"):
+        raise ValueError(f"noise must be 'host' or 'device', not {noise!r}")
     if x.device.type != "cuda":
         raise ops.AfanLibraryError("x must live on the MI355X (no CPU path in this build)")
     x = _dense(x.detach().float())
+    if randinit and noise == "device":
+        if u is not None:
+            raise ValueError("noise='device' draws its own u")
+        x_adv, used = ops.pgd_rand_start(x, eps)
+        x_adv._afan_noise_seed = used
+        return x, x_adv
     x_adv = x.clone()
     if randinit:
         u = torch.rand(x_adv.shape) if u is None else u

@@ -80,10 +80,11 @@ def decoder_PGD(input_dict, image_batch, criterion, y=None, model=None, steps=3,
     return input_dict
 
 
-def adv_input(x=None, criterion=None, y=None, model=None, steps=3, eps=None, gamma=None, randinit=False, clip=False):
+def adv_input(x=None, criterion=None, y=None, model=None, steps=3, eps=None, gamma=None, randinit=False, clip=False, noise="host"):
     """Image-space PGD (:86-105), clamped to [0, 1] at the end.  With seg_criterion's fused callable the model hands back its
-    low-resolution logits and the criterion resizes inside its own kernel, as in PGD / decoder_PGD."""
-    x, x_adv = pgd.start(x, eps, randinit)
+    low-resolution logits and the criterion resizes inside its own kernel, as in PGD / decoder_PGD.  noise (an addition): "host" is
+    the reference's CPU draw of the random start, "device" pgd.start's one-launch draw (the result carries `_afan_noise_seed`)."""
+    x, x_adv = pgd.start(x, eps, randinit, noise=noise)
     loss_of = lambda t: criterion(model({"x": t, "adv": None, "out_idx": 0, "flag": "clean", "low_level_feat": None,
                                          "low_res": _low_res(criterion)}), y)
     for _ in range(steps):

@@ -156,3 +156,62 @@ class SegBaseTrainer(SegTrainer):
 
     def _tail_range(self):
         return None
+
+
+def seg_adv_phases(model, optimizer, criterion, images, labels, out, *, steps_pgd=1, eps_pgd=2.0, gamma_pgd=0.5, randinit=False,
+                   clip=False, noise="device", defer_step=False):
+    """The PGD-training iteration, Segmentation/main_advtrain.py:185-202, in seg_base_phases' form: image-space sign-PGD on the batch
+    with the model as the loop leaves it, in TRAINING mode (:185-194 — every attack pass normalises with batch statistics, updates the
+    running statistics and draws ASPP's dropout; no parameter gradient is computed, pgd.input_gradient runs under dgrad_only), then
+    seg_base_phases' body on the adversarial images (:196-202).  noise: where --randinit_pgd's start is drawn — "device" in the
+    start's own launch (ops.pgd_rand_start: the whole iteration can be captured), "host" on torch's CPU generator as the reference
+    does.  out: loss, adv_images, noise_seed (the device draw's seed word, None without one).  Never yields."""
+    from .deeplab import seg_criterion
+    from .seg_attack_algo import adv_input
+    criterion = seg_criterion(criterion)
+    if images.is_cuda:
+        ops.acc_reset(images.device)            # BatchNorm accumulator arena: one memset per iteration
+    adv_images = adv_input(x=images, criterion=criterion, y=labels, model=model, steps=steps_pgd, eps=(eps_pgd / 255),
+                           gamma=(gamma_pgd / 255), randinit=randinit, clip=clip, noise=noise)
+    seed = getattr(adv_images, "_afan_noise_seed", None)
+    adv_images = adv_images.detach()
+    optimizer.zero_grad()
+    low = bool(getattr(criterion, "low_res", False))
+    o = model({"x": adv_images, "adv": None, "out_idx": 0, "flag": "clean", "low_res": low})
+    if getattr(criterion, "fused", False) and _f32_logits(o):
+        loss = criterion(o, labels, grad_scale=1.0)
+        torch.autograd.backward([loss], [ops.one(images.device)])
+    else:
+        loss = criterion(o, labels)
+        loss.backward()
+    if not defer_step:
+        optimizer.step()
+    out.update({"loss": loss.detach(), "adv_images": adv_images, "noise_seed": seed})
+    return
+    yield
+
+
+class SegAdvTrainer(SegBaseTrainer):
+    """Segmentation PGD training (Segmentation/main_advtrain.py): SegBaseTrainer's arena, two-group SGD, schedule, BatchNorm momentum,
+    grid guard and data-parallel exchange around seg_adv_phases.  step() returns {"loss", "adv_images", "noise_seed"}.  With a random
+    start drawn on the host the iteration stays eager (the draw and its upload happen every step); drawn on the device it is captured
+    whole — attack passes, random start, training pass, SGD launch — and every replay draws a fresh start."""
+    _what = "the segmentation PGD-training step"
+    _small = ("loss",)
+
+    def __init__(self, model, criterion=None, *, steps_pgd=1, eps_pgd=2.0, gamma_pgd=0.5, randinit=False, clip=False, noise="device",
+                 lr=0.01, momentum=0.9, weight_decay=1e-4, total_itrs=30000, lr_policy="poly", step_size=10000,
+                 backbone_bn_momentum=0.01, use_graph=True, graph_warmup=2, group=None, allreduce_chunks=4, segmented=None,
+                 wgrad_stream=None):
+        if noise not in ("device", "host"):
+            raise ValueError(f"noise must be 'device' or 'host', not {noise!r}")
+        super().__init__(model, criterion, lr=lr, momentum=momentum, weight_decay=weight_decay, total_itrs=total_itrs,
+                         lr_policy=lr_policy, step_size=step_size, backbone_bn_momentum=backbone_bn_momentum,
+                         use_graph=bool(use_graph) and (not randinit or noise == "device"), graph_warmup=graph_warmup, group=group,
+                         allreduce_chunks=allreduce_chunks, segmented=segmented, wgrad_stream=wgrad_stream)
+        self.kw.update(steps_pgd=steps_pgd, eps_pgd=eps_pgd, gamma_pgd=gamma_pgd, randinit=bool(randinit), clip=bool(clip), noise=noise)
+        if randinit and noise == "device" and self.arena.param.is_cuda:
+            ops.noise_state(self.arena.param.device)        # seeded here, from the host generator: never inside a capture
+
+    def _phases(self, images, labels, out):
+        return seg_adv_phases(self.model, self.optimizer, self.criterion, images, labels, out, **self.kw)

@@ -87,6 +87,21 @@ int afan_perturb_norms(const float* x_adv, const float* x_clean, int64_t batch, 
 int afan_axpy_noise(float* x_adv, const float* u, int64_t n, float eps, uint16_t* shadow_bf16,
                     afan_stream_t stream);
 
+/* Random start drawn ON THE DEVICE, out of place: x_adv[e] = x[e] + fl(fl(fl(2 u_e) - 1) * eps) with afan_axpy_noise's roundings
+ * (operation by operation, one add, no FMA); shadow_bf16 (nullable) receives the bf16 (RNE) copy of x_adv.  It stands for the
+ * clone, the host draw, its upload and afan_axpy_noise, and can be captured into a hipGraph: a replay draws fresh numbers.
+ * u_e: Philox4x32-10 with key (seed & 0xffffffff, seed >> 32), seed = state[0]; counter (q & 0xffffffff, q >> 32, 0, 0) with
+ * q = e >> 2; output word e & 3; u = (word >> 8) * 2^-24, in [0, 1) and exact in fp32.  e is the element's LOGICAL NCHW index
+ * ((n C + c) H + h) W + w whatever `layout` (AFAN_NCHW / AFAN_NHWC, the memory order of x, x_adv and shadow_bf16) says: a
+ * channels-last map receives the numbers of its NCHW twin.  A tensor that is not 4-D is passed as n elements, c = h = w = 1.
+ * state: the generator, one device uint64; used (nullable): receives the seed of this call; `advance`: state[0] takes the step
+ * of afan_dropout's generator, s * 6364136223846793005 + 1442695040888963407, in a one-lane launch behind the draw on the same
+ * stream (every workgroup of the draw reads the seed, so the word cannot change inside it).
+ * Errors: a negative size or an unknown layout AFAN_ESHAPE; an empty tensor returns 0 without a launch; x, x_adv or state NULL
+ * AFAN_ENULL; x, x_adv or shadow_bf16 not 16-byte aligned (state, used: 8-byte) AFAN_EALIGN.  No allocation, no synchronisation. */
+int afan_pgd_rand_start(const float* x, float* x_adv, uint16_t* shadow_bf16, int64_t n, int64_t c, int64_t h, int64_t w,
+                        int layout, float eps, uint64_t* state, uint64_t* used, int advance, afan_stream_t stream);
+
 /* mix_feature.  Replaces Segmentation/attack_algo.py:121-130 == Detection/attack_algo.py:254-265:
  * per (n,h,w): mean and unbiased variance over the C channels of clean and adv;
  *   out = (clean - mean_c) / sqrt(var_c + 1e-5) * sqrt(var_a + 1e-5) + mean_a
