@@ -11,8 +11,9 @@ LIB_PATH = os.environ.get("AFAN_HIP_LIB") or os.path.join(_HERE, "libafan_hip.so
 
 AFAN_F32, AFAN_BF16 = 0, 1
 AFAN_NCHW, AFAN_NHWC = 0, 1
+AFAN_ESHAPE = -3           # (also how an entry point with a fallback declines a shape: the wrappers in ops return None)
 _ERRORS = {-1: "AFAN_EDTYPE (unknown dtype code)", -2: "AFAN_EALIGN (misaligned pointer)",
-           -3: "AFAN_ESHAPE (bad sizes)", -4: "AFAN_ENULL (required pointer is NULL)",
+           AFAN_ESHAPE: "AFAN_ESHAPE (bad sizes)", -4: "AFAN_ENULL (required pointer is NULL)",
            -5: "AFAN_ELAYOUT (unknown layout code)"}
 
 _p, _i, _l, _f = C.c_void_p, C.c_int, C.c_int64, C.c_float

@@ -10,7 +10,7 @@ import threading
 import torch
 
 from . import _lib
-from ._lib import AFAN_BF16, AFAN_F32, AFAN_NCHW, AFAN_NHWC, AfanLibraryError, check
+from ._lib import AFAN_BF16, AFAN_ESHAPE, AFAN_F32, AFAN_NCHW, AFAN_NHWC, AfanLibraryError, check
 
 _DT = {torch.float32: AFAN_F32, torch.bfloat16: AFAN_BF16}
 _ws_cache = {}
@@ -866,6 +866,10 @@ def _conv_acc_ok(c):
     return BN_ACC and bool(_lib.load().afan_bn_acc_supported(AFAN_BF16, int(c)))
 
 
+def _conv_out(i, k, stride, pad, dil):
+    return (i + 2 * pad - dil * (k - 1) - 1) // stride + 1
+
+
 def conv_fwd(x, w, stride, stats_shift=None, want_stats=False, stats_buf=None, groups=1, dilation=1):
     """y = conv2d(x, w, padding=dilation*(k//2), stride, dilation): x [N,Ci,H,W], w [Co,Ci,k,k], both bf16 channels_last.
     want_stats=True also returns a ConvStats (moments of y around stats_shift[c], e.g. the BN running mean); None for a
@@ -877,8 +881,8 @@ def conv_fwd(x, w, stride, stats_shift=None, want_stats=False, stats_buf=None, g
     co, ci2, k, k2 = w.shape
     if ci2 != ci or k != k2:
         raise ValueError("weight shape does not match the input")
-    pad = k // 2
-    ho, wo = (hi + 2 * pad - k) // stride + 1, (wi + 2 * pad - k) // stride + 1
+    # (padding = dilation * (k // 2) with an odd k — the kernels take 1 and 3 — makes this (hi - 1) // stride + 1 whatever the dilation)
+    ho, wo = (_conv_out(v, k, stride, int(dilation) * (k // 2), int(dilation)) for v in (hi, wi))
     y = torch.empty((n, co, ho, wo), dtype=torch.bfloat16, device=x.device, memory_format=torch.channels_last)
     st = None
     if groups != 1 and not (want_stats and _conv_acc_ok(co)):
@@ -1043,6 +1047,34 @@ def _acc_untake(device, blk):
         a.off -= blk.numel()
 
 
+def _grid_takes(k, dilation, ci, co):
+    """The in-launch forms take this stride-1 convolution: 3x3 (atrous too) or plain 1x1, both channel counts multiples of 64."""
+    return (k == 3 or (k == 1 and dilation == 1)) and ci % 64 == 0 and co % 64 == 0 and (k != 1 or GRID_BN_K1) and (dilation == 1 or GRID_BN_DIL)
+
+
+def _grid_launch(key, name, device, channels, call, n_fwd=0, n_dgrad=0):
+    """The launch protocol of the four in-launch forms.  `key` names the launch's shape in the refused memo: what the library declined
+    once (AFAN_ESHAPE: its workgroups would not all be resident) is not tried again.  One accumulator block per entry of `channels`
+    is taken in that order and passed to `call`, which allocates the outputs, launches and returns (return code, results).  A declined
+    launch gives its blocks back LAST TAKEN FIRST — _acc_untake only rewinds a block that ends the arena — and leaves CALLS alone.
+    Returns `results`, or None when nothing has run (the caller issues the two-launch form: the same bits)."""
+    if key in _grid_refused or not all(_conv_acc_ok(c) for c in channels):
+        return None
+    accs = [acc_take(device, c) for c in channels]
+    rc, results = call(*accs)
+    if rc == AFAN_ESHAPE:
+        _grid_refused.add(key)
+        for blk in reversed(accs):
+            _acc_untake(device, blk)
+        return None
+    check(rc, name)
+    _grid_check(device, key)
+    CALLS["conv_fwd"] += n_fwd
+    CALLS["conv_dgrad"] += n_dgrad
+    CALLS["conv_bn_fused"] += 1
+    return results
+
+
 def conv_fwd_bn(x, w, bn, momentum, residual=None, relu=True, sc=None, dilation=1):
     """(raw, act, stats) = conv(x, w) (3x3 padding 1, or 1x1; stride 1) with the train-mode BatchNorm `bn` (module: weight, bias, eps, running buffers) behind it,
     + residual, + ReLU, in ONE launch; sc = (raw_sc, bn_sc, ConvStats_sc, momentum_sc): act = relu(bn(raw) + bn_sc(raw_sc)) and a
@@ -1052,44 +1084,41 @@ def conv_fwd_bn(x, w, bn, momentum, residual=None, relu=True, sc=None, dilation=
         return None
     n, ci, hi, wi = x.shape
     co, ci2, k, k2 = w.shape
-    key = ("f", n, ci, hi, wi, co, k, int(dilation), x.device.index, _GRID_SHARED)
-    if ((k == 1 and dilation != 1) or k not in (1, 3) or k2 != k or ci2 != ci or ci % 64 or co % 64 or key in _grid_refused or not _conv_acc_ok(co) or (k == 1 and not GRID_BN_K1)
-            or (dilation != 1 and not GRID_BN_DIL)):
+    if not _grid_takes(k, dilation, ci, co) or k2 != k or ci2 != ci:
         return None
     lib = _lib.load()
     _cl4(x, "x"), _cl4(w, "w")
-    cl = torch.channels_last
-    y = torch.empty((n, co, hi, wi), dtype=torch.bfloat16, device=x.device, memory_format=cl)
-    a = torch.empty((n, co, hi, wi), dtype=torch.bfloat16, device=x.device, memory_format=cl)
-    stats = torch.empty((2, 4, co) if sc is not None else (4, co), dtype=torch.float32, device=x.device)
-    st_a = stats[0] if sc is not None else stats
-    acc = acc_take(x.device, co)
+    shape, cl = (n, co, hi, wi), torch.channels_last
     if residual is not None:
         _cl4(residual, "residual")
-        if residual.shape != y.shape:
+        if tuple(residual.shape) != shape:
             raise ValueError("residual must have the output's shape")
-    scp = [None] * 10
     if sc is not None:
         raw_sc, bsc, stc, mom_sc = sc
         _cl4(raw_sc, "raw_sc")
-        if raw_sc.shape != y.shape or stc.acc is None or residual is not None or not relu:
+        if tuple(raw_sc.shape) != shape or stc.acc is None or residual is not None or not relu:
             raise ValueError("projection form: same-shape raw_sc with accumulator sums, no residual, ReLU")
-        scp = [_ptr(raw_sc), _ptr(stc.acc), _ptr(bsc.weight), _ptr(bsc.bias), float(bsc.eps), float(mom_sc), _ptr(stats[1]),
-               _ptr(bsc.running_mean), _ptr(bsc.running_var), _ptr(bsc.num_batches_tracked)]
-    else:
-        scp[4] = scp[5] = 0.0
-    rc = lib.afan_conv_fwd_bn_nhwc_bf16(_ptr(x), _ptr(w), _ptr(y), _ptr(a), n, hi, wi, ci, co, k, int(dilation), _ptr(acc), _ptr(bn.running_mean),
-                                        _ptr(bn.weight), _ptr(bn.bias), float(bn.eps), float(momentum), _ptr(st_a),
-                                        _ptr(bn.running_mean), _ptr(bn.running_var), _ptr(bn.num_batches_tracked), _ptr(residual),
-                                        int(bool(relu)), *scp, _ptr(_grid_barrier(x.device)), _stream(x))
-    if rc == -3:                                # AFAN_ESHAPE: not this launch — remembered per shape
-        _grid_refused.add(key)
-        _acc_untake(x.device, acc)
+
+    def call(acc):
+        y = torch.empty(shape, dtype=torch.bfloat16, device=x.device, memory_format=cl)
+        a = torch.empty(shape, dtype=torch.bfloat16, device=x.device, memory_format=cl)
+        stats = torch.empty((2, 4, co) if sc is not None else (4, co), dtype=torch.float32, device=x.device)
+        scp = [None, None, None, None, 0.0, 0.0, None, None, None, None]
+        if sc is not None:
+            scp = [_ptr(raw_sc), _ptr(stc.acc), _ptr(bsc.weight), _ptr(bsc.bias), float(bsc.eps), float(mom_sc), _ptr(stats[1]),
+                   _ptr(bsc.running_mean), _ptr(bsc.running_var), _ptr(bsc.num_batches_tracked)]
+        return lib.afan_conv_fwd_bn_nhwc_bf16(
+            _ptr(x), _ptr(w), _ptr(y), _ptr(a), n, hi, wi, ci, co, k, int(dilation), _ptr(acc), _ptr(bn.running_mean), _ptr(bn.weight),
+            _ptr(bn.bias), float(bn.eps), float(momentum), _ptr(stats[0] if sc is not None else stats), _ptr(bn.running_mean),
+            _ptr(bn.running_var), _ptr(bn.num_batches_tracked), _ptr(residual), int(bool(relu)), *scp, _ptr(_grid_barrier(x.device)),
+            _stream(x)), (y, a, stats)
+
+    out = _grid_launch(("f", n, ci, hi, wi, co, k, int(dilation), x.device.index, _GRID_SHARED), "afan_conv_fwd_bn_nhwc_bf16", x.device,
+                       [co], call, n_fwd=1)
+    if out is None:
         return None
-    check(rc, "afan_conv_fwd_bn_nhwc_bf16")
-    _grid_check(x.device, key)
-    CALLS["conv_fwd"] += 1
-    CALLS["conv_bn_fused"] += 1
+    y, a, stats = out
+    st_a = stats[0] if sc is not None else stats
     if sc is not None:
         _bn_record(sc[1].running_mean, sc[1].running_var, sc[1].num_batches_tracked, stats[1], n * hi * wi, sc[1].eps, sc[3], 1)
     _bn_record(bn.running_mean, bn.running_var, bn.num_batches_tracked, st_a, n * hi * wi, bn.eps, momentum, 1)
@@ -1120,52 +1149,41 @@ def conv_dgrad_bn(dy, wt, in_hw, bn_x, bn_stats, relu, bn_y=None, addend=None, w
     n, co, ho, wo = dy.shape
     ci, co2, k, _ = wt.shape
     hi, wi = in_hw
-    key = ("b" if sc is None else "bs", n, ci, hi, wi, co, k, int(dilation), dy.device.index, _GRID_SHARED)
-    if ((k == 1 and dilation != 1) or k not in (1, 3) or co2 != co or (hi, wi) != (ho, wo) or ci % 64 or co % 64 or key in _grid_refused or not _conv_acc_ok(ci)
-            or (k == 1 and not GRID_BN_K1) or (dilation != 1 and not GRID_BN_DIL)):
+    if not _grid_takes(k, dilation, ci, co) or co2 != co or (hi, wi) != (ho, wo):
         return None
     lib = _lib.load()
     _cl4(dy, "dy"), _cl4(wt, "wt"), _cl4(bn_x, "bn_x")
     _need(bn_stats, "bn_stats", torch.float32)
-    cl = torch.channels_last
+    shape = (n, ci, hi, wi)
     if dx_out is not None:
         _cl4(dx_out, "dx_out")
-        if tuple(dx_out.shape) != (n, ci, hi, wi):
+        if tuple(dx_out.shape) != shape:
             raise ValueError("dx_out must have dx's shape")
-    dx = dx_out if dx_out is not None else torch.empty((n, ci, hi, wi), dtype=torch.bfloat16, device=dy.device, memory_format=cl)
-    dres = torch.empty((n, ci, hi, wi), dtype=torch.bfloat16, device=dy.device, memory_format=cl) if want_dres else None
-    if bn_x.shape != dx.shape or bn_stats.numel() != 4 * ci:
+    if tuple(bn_x.shape) != shape or bn_stats.numel() != 4 * ci:
         raise ValueError("bn_x / bn_stats do not match dx")
     for t, nm in ((bn_y, "bn_y"), (addend, "addend")):
         if t is not None:
             _cl4(t, nm)
-            if t.shape != dx.shape:
+            if tuple(t.shape) != shape:
                 raise ValueError(nm + " must have dx's shape")
-    scp, acc2 = [None] * 6, None
     if sc is not None:
         sc_x, sc_stats, d_sc, sc_dw, sc_db = sc
         _cl4(sc_x, "sc_x"), _cl4(d_sc, "d_sc")
         _need(sc_stats, "sc_stats", torch.float32)
-        if bn_y is None or sc_x.shape != dx.shape or d_sc.shape != dx.shape or sc_stats.numel() != 4 * ci:
+        if bn_y is None or tuple(sc_x.shape) != shape or tuple(d_sc.shape) != shape or sc_stats.numel() != 4 * ci:
             raise ValueError("projection form: block-output launch (bn_y) with sc_x / d_sc of dx's shape")
-    acc = acc_take(dy.device, ci)
-    if sc is not None:
-        acc2 = acc_take(dy.device, ci)
-        scp = [_ptr(sc_x), _ptr(sc_stats), _ptr(acc2), _ptr(d_sc), _ptr(sc_dw), _ptr(sc_db)]
-    rc = lib.afan_conv_dgrad_bn_nhwc_bf16(_ptr(dy), _ptr(wt), _ptr(dx), _ptr(dres), n, hi, wi, ci, co, k, int(dilation), _ptr(addend), _ptr(bn_x),
-                                          _ptr(bn_stats), int(bool(relu)), _ptr(bn_y), _ptr(acc), _ptr(dweight), _ptr(dbias),
-                                          int(bool(accumulate)), *scp, _ptr(_grid_barrier(dy.device)), _stream(dy))
-    if rc == -3:
-        _grid_refused.add(key)
-        if acc2 is not None:
-            _acc_untake(dy.device, acc2)
-        _acc_untake(dy.device, acc)
-        return None
-    check(rc, "afan_conv_dgrad_bn_nhwc_bf16")
-    _grid_check(dy.device, key)
-    CALLS["conv_dgrad"] += 1
-    CALLS["conv_bn_fused"] += 1
-    return dx, dres
+
+    def call(acc, acc2=None):
+        dx = dx_out if dx_out is not None else torch.empty(shape, dtype=torch.bfloat16, device=dy.device, memory_format=torch.channels_last)
+        dres = torch.empty_like(dx) if want_dres else None
+        scp = [None] * 6 if sc is None else [_ptr(sc_x), _ptr(sc_stats), _ptr(acc2), _ptr(d_sc), _ptr(sc_dw), _ptr(sc_db)]
+        return lib.afan_conv_dgrad_bn_nhwc_bf16(
+            _ptr(dy), _ptr(wt), _ptr(dx), _ptr(dres), n, hi, wi, ci, co, k, int(dilation), _ptr(addend), _ptr(bn_x), _ptr(bn_stats),
+            int(bool(relu)), _ptr(bn_y), _ptr(acc), _ptr(dweight), _ptr(dbias), int(bool(accumulate)), *scp,
+            _ptr(_grid_barrier(dy.device)), _stream(dy)), (dx, dres)
+
+    return _grid_launch(("b" if sc is None else "bs", n, ci, hi, wi, co, k, int(dilation), dy.device.index, _GRID_SHARED),
+                        "afan_conv_dgrad_bn_nhwc_bf16", dy.device, [ci] if sc is None else [ci, ci], call, n_dgrad=1)
 
 
 def _conv_dgrad_bn_pair(dy, pair, in_hw, bn_x, bn_stats, relu, bn_y, want_dres, dweight, dbias, accumulate):
@@ -1173,8 +1191,7 @@ def _conv_dgrad_bn_pair(dy, pair, in_hw, bn_x, bn_stats, relu, bn_y, want_dres, 
     n, co, ho, wo = dy.shape
     hi, wi = in_hw
     ci = bn_x.shape[1]
-    key = ("bp", n, ci, hi, wi, co, dy.device.index, _GRID_SHARED)
-    if (not GRID_BN_PAIR or bn_y is None or (hi, wi) != (2 * ho, 2 * wo) or ci % 64 or co % 64 or key in _grid_refused or not _conv_acc_ok(ci)
+    if (not GRID_BN_PAIR or bn_y is None or (hi, wi) != (2 * ho, 2 * wo) or ci % 64 or co % 64
             or wt10.numel() != ci * 10 * co or dy_sc.shape != dy.shape):
         return None
     lib = _lib.load()
@@ -1184,22 +1201,16 @@ def _conv_dgrad_bn_pair(dy, pair, in_hw, bn_x, bn_stats, relu, bn_y, want_dres, 
         raise ValueError("dy_sc must sit directly behind dy in one allocation")
     if bn_x.shape != (n, ci, hi, wi) or bn_y.shape != bn_x.shape or bn_stats.numel() != 4 * ci:
         raise ValueError("bn_x / bn_y / bn_stats do not match dx")
-    cl = torch.channels_last
-    dx = torch.empty((n, ci, hi, wi), dtype=torch.bfloat16, device=dy.device, memory_format=cl)
-    dres = torch.empty((n, ci, hi, wi), dtype=torch.bfloat16, device=dy.device, memory_format=cl) if want_dres else None
-    acc = acc_take(dy.device, ci)
-    rc = lib.afan_conv_dgrad_sc_bn_nhwc_bf16(_ptr(dy), _ptr(dy_sc), _ptr(wt10), _ptr(dx), _ptr(dres), n, hi, wi, ci, co, _ptr(bn_x),
-                                             _ptr(bn_stats), int(bool(relu)), _ptr(bn_y), _ptr(acc), _ptr(dweight), _ptr(dbias),
-                                             int(bool(accumulate)), _ptr(_grid_barrier(dy.device)), _stream(dy))
-    if rc == -3:
-        _grid_refused.add(key)
-        _acc_untake(dy.device, acc)
-        return None
-    check(rc, "afan_conv_dgrad_sc_bn_nhwc_bf16")
-    _grid_check(dy.device, key)
-    CALLS["conv_dgrad"] += 1
-    CALLS["conv_bn_fused"] += 1
-    return dx, dres
+
+    def call(acc):
+        dx = torch.empty((n, ci, hi, wi), dtype=torch.bfloat16, device=dy.device, memory_format=torch.channels_last)
+        dres = torch.empty_like(dx) if want_dres else None
+        return lib.afan_conv_dgrad_sc_bn_nhwc_bf16(
+            _ptr(dy), _ptr(dy_sc), _ptr(wt10), _ptr(dx), _ptr(dres), n, hi, wi, ci, co, _ptr(bn_x), _ptr(bn_stats), int(bool(relu)),
+            _ptr(bn_y), _ptr(acc), _ptr(dweight), _ptr(dbias), int(bool(accumulate)), _ptr(_grid_barrier(dy.device)), _stream(dy)), (dx, dres)
+
+    return _grid_launch(("bp", n, ci, hi, wi, co, dy.device.index, _GRID_SHARED), "afan_conv_dgrad_sc_bn_nhwc_bf16", dy.device, [ci],
+                        call, n_dgrad=1)
 
 
 def conv_fwd_affine(x, w, stride, coefs, residual=None, relu=False, any_kernel=False, dilation=1):
@@ -1215,12 +1226,11 @@ def conv_fwd_affine(x, w, stride, coefs, residual=None, relu=False, any_kernel=F
     n, ci, hi, wi = x.shape
     co, _, k, _ = w.shape
     dilation = int(dilation)
-    pad = dilation * (k // 2)
-    ho, wo = (hi + 2 * pad - dilation * (k - 1) - 1) // stride + 1, (wi + 2 * pad - dilation * (k - 1) - 1) // stride + 1
+    ho, wo = (_conv_out(v, k, stride, dilation * (k // 2), dilation) for v in (hi, wi))
     y = torch.empty((n, co, ho, wo), dtype=torch.bfloat16, device=x.device, memory_format=torch.channels_last)
     rc = lib.afan_conv_fwd_affine_nhwc_bf16(_ptr(x), _ptr(w), _ptr(y), n, hi, wi, ci, co, k, int(stride), dilation, _ptr(coefs),
                                             _ptr(residual), int(bool(relu)), int(any_kernel or dilation != 1), _stream(x))
-    if rc == -3:
+    if rc == AFAN_ESHAPE:
         return None
     check(rc, "afan_conv_fwd_affine_nhwc_bf16")
     CALLS["conv_fwd"] += 1
@@ -1249,24 +1259,27 @@ def conv_fwd_multi(x, ws, stride, dilations, stats_shifts=None, groups=1):
     CALLS["conv_fwd"] += nb
     _cl4(x, "x")
     n, ci, hi, wi = x.shape
-    co, _, k, _ = ws[0].shape
-    pad = k // 2
-    ho, wo = (hi + 2 * pad - k) // stride + 1, (wi + 2 * pad - k) // stride + 1
-    yall = torch.empty((nb * n, co, ho, wo), dtype=torch.bfloat16, device=x.device, memory_format=torch.channels_last)
-    ys = [yall[b * n:(b + 1) * n] for b in range(nb)]
+    co = ws[0].shape[0]
+    ys, ptrs, wp, yp, ks, ds = _multi_operands(x, ws, stride, dilations)
     sts = [None] * nb
-    arr_p = C.c_void_p * nb
     shifts = accs = None
     if stats_shifts is not None:
         sts = [ConvStats(None, 0, stats_shifts[b], acc_take(x.device, co, groups)) for b in range(nb)]
-        shifts = arr_p(*[t.data_ptr() for t in stats_shifts])
-        accs = arr_p(*[st.acc.data_ptr() for st in sts])
-    check(lib.afan_conv_fwd_multi_nhwc_bf16(_ptr(x), arr_p(*[w.data_ptr() for w in ws]), arr_p(*[y.data_ptr() for y in ys]), nb,
-                                            n, hi, wi, ci, co, (C.c_int * nb)(*[int(w.shape[2]) for w in ws]), stride,
-                                            (C.c_int * nb)(*[int(d) for d in dilations]), shifts, accs, int(groups if accs is not None else 1),
-                                            _stream(x)),
-          "afan_conv_fwd_multi_nhwc_bf16")
+        shifts, accs = ptrs(stats_shifts), ptrs([st.acc for st in sts])
+    check(lib.afan_conv_fwd_multi_nhwc_bf16(_ptr(x), wp, yp, nb, n, hi, wi, ci, co, ks, stride, ds, shifts, accs,
+                                            int(groups if accs is not None else 1), _stream(x)), "afan_conv_fwd_multi_nhwc_bf16")
     return ys, sts
+
+
+def _multi_operands(x, ws, stride, dilations):
+    """What the multi-problem forward launches marshal alike: the outputs [y_b] (slices of one allocation; one shape, problem 0's),
+    a function packing tensors' addresses into a pointer array, and the arrays of the weights, outputs, kernel sizes and dilations."""
+    nb, n, k = len(ws), x.shape[0], ws[0].shape[2]
+    ho, wo = (_conv_out(v, k, stride, k // 2, 1) for v in x.shape[2:])
+    yall = torch.empty((nb * n, ws[0].shape[0], ho, wo), dtype=torch.bfloat16, device=x.device, memory_format=torch.channels_last)
+    ys = [yall[b * n:(b + 1) * n] for b in range(nb)]
+    ptrs = lambda ts: (C.c_void_p * nb)(*[t.data_ptr() for t in ts])
+    return ys, ptrs, ptrs(ws), ptrs(ys), (C.c_int * nb)(*[int(w.shape[2]) for w in ws]), (C.c_int * nb)(*[int(d) for d in dilations])
 
 
 GRID_BN_MULTI = os.environ.get("AFAN_GRID_BN_MULTI", "1") != "0"       # ... and in the two-problem forward launch (first 3x3 / 2 + projection)
@@ -1281,38 +1294,27 @@ def conv_fwd_multi_bn(x, ws, stride, dilations, stats_shifts, bn0, momentum):
     nb = len(ws)
     n, ci, hi, wi = x.shape
     co, _, k, _ = ws[0].shape
-    key = ("fm", n, ci, hi, wi, co, nb, k, int(stride), x.device.index, _GRID_SHARED)
-    if nb < 2 or ci % 64 or co % 64 or key in _grid_refused or not _conv_acc_ok(co):
+    if nb < 2 or ci % 64 or co % 64:
         return None
     lib = _lib.load()
     _cl4(x, "x")
-    pad = k // 2
-    ho, wo = (hi + 2 * pad - k) // stride + 1, (wi + 2 * pad - k) // stride + 1
-    cl = torch.channels_last
-    yall = torch.empty((nb * n, co, ho, wo), dtype=torch.bfloat16, device=x.device, memory_format=cl)
-    ys = [yall[b * n:(b + 1) * n] for b in range(nb)]
-    act0 = torch.empty((n, co, ho, wo), dtype=torch.bfloat16, device=x.device, memory_format=cl)
-    stats0 = torch.empty((4, co), dtype=torch.float32, device=x.device)
-    arr_p = C.c_void_p * nb
-    sts = [ConvStats(None, 0, stats_shifts[b], acc_take(x.device, co, 1)) for b in range(nb)]
-    rc = lib.afan_conv_fwd_multi_bn_nhwc_bf16(_ptr(x), arr_p(*[w.data_ptr() for w in ws]), arr_p(*[y.data_ptr() for y in ys]), nb,
-                                              n, hi, wi, ci, co, (C.c_int * nb)(*[int(w.shape[2]) for w in ws]), int(stride),
-                                              (C.c_int * nb)(*[int(d) for d in dilations]), arr_p(*[t.data_ptr() for t in stats_shifts]),
-                                              arr_p(*[st.acc.data_ptr() for st in sts]), _ptr(act0), _ptr(bn0.weight), _ptr(bn0.bias),
-                                              float(bn0.eps), float(momentum), _ptr(stats0), _ptr(bn0.running_mean),
-                                              _ptr(bn0.running_var), _ptr(bn0.num_batches_tracked), 1, _ptr(_grid_barrier(x.device)),
-                                              _stream(x))
-    if rc == -3:
-        _grid_refused.add(key)
-        for st in reversed(sts):
-            _acc_untake(x.device, st.acc)
+
+    def call(*accs):
+        ys, ptrs, wp, yp, ks, ds = _multi_operands(x, ws, stride, dilations)
+        act0 = torch.empty(ys[0].shape, dtype=torch.bfloat16, device=x.device, memory_format=torch.channels_last)
+        stats0 = torch.empty((4, co), dtype=torch.float32, device=x.device)
+        return lib.afan_conv_fwd_multi_bn_nhwc_bf16(
+            _ptr(x), wp, yp, nb, n, hi, wi, ci, co, ks, int(stride), ds, ptrs(stats_shifts), ptrs(accs), _ptr(act0), _ptr(bn0.weight),
+            _ptr(bn0.bias), float(bn0.eps), float(momentum), _ptr(stats0), _ptr(bn0.running_mean), _ptr(bn0.running_var),
+            _ptr(bn0.num_batches_tracked), 1, _ptr(_grid_barrier(x.device)), _stream(x)), (ys, accs, act0, stats0)
+
+    out = _grid_launch(("fm", n, ci, hi, wi, co, nb, k, int(stride), x.device.index, _GRID_SHARED), "afan_conv_fwd_multi_bn_nhwc_bf16",
+                       x.device, [co] * nb, call, n_fwd=nb)
+    if out is None:
         return None
-    check(rc, "afan_conv_fwd_multi_bn_nhwc_bf16")
-    _grid_check(x.device, key)
-    CALLS["conv_fwd"] += nb
-    CALLS["conv_bn_fused"] += 1
-    _bn_record(bn0.running_mean, bn0.running_var, bn0.num_batches_tracked, stats0, n * ho * wo, bn0.eps, momentum, 1)
-    return ys, sts, act0, stats0
+    ys, accs, act0, stats0 = out
+    _bn_record(bn0.running_mean, bn0.running_var, bn0.num_batches_tracked, stats0, n * act0.shape[2] * act0.shape[3], bn0.eps, momentum, 1)
+    return ys, [ConvStats(None, 0, shift, acc) for shift, acc in zip(stats_shifts, accs)], act0, stats0
 
 
 def conv_dgrad(dy, wt, in_hw, stride, addend=None, bn_bwd=None, partials_buf=None, bn_y=None, groups=1, dilation=1, sc=None):
@@ -1429,10 +1431,6 @@ def _w_layout(w):
     if w.is_contiguous(memory_format=torch.channels_last):
         return w, AFAN_NHWC
     return w.contiguous(), AFAN_NCHW
-
-
-def _conv_out(i, k, stride, pad, dil):
-    return (i + 2 * pad - dil * (k - 1) - 1) // stride + 1
 
 
 def conv_general_fwd(x, w, bias=None, stride=1, padding=0, dilation=1):
@@ -1770,7 +1768,7 @@ def conv_dgrad_affine(dy, wt, in_hw, stride, alpha, act, any_kernel=False, dilat
     dx = torch.empty((n, ci, hi, wi), dtype=torch.bfloat16, device=dy.device, memory_format=torch.channels_last)
     rc = lib.afan_conv_dgrad_affine_nhwc_bf16(_ptr(dy), _ptr(wt), _ptr(dx), n, hi, wi, ci, co, k, int(stride), dilation, _ptr(alpha),
                                               _ptr(act), int(any_kernel or dilation != 1), _stream(dy))
-    if rc == -3:
+    if rc == AFAN_ESHAPE:
         return None
     check(rc, "afan_conv_dgrad_affine_nhwc_bf16")
     CALLS["conv_dgrad"] += 1
@@ -1791,7 +1789,7 @@ def conv_dgrad_dual(dy, wt, in_hw, stride, addend, alpha, act):
     dres = torch.empty_like(d3)
     rc = lib.afan_conv_dgrad_dual_nhwc_bf16(_ptr(dy), _ptr(wt), _ptr(d3), _ptr(dres), n, hi, wi, ci, co, k, int(stride), _ptr(addend), _ptr(alpha),
                                             _ptr(act), _stream(dy))
-    if rc == -3:
+    if rc == AFAN_ESHAPE:
         return None
     check(rc, "afan_conv_dgrad_dual_nhwc_bf16")
     CALLS["conv_dgrad"] += 1

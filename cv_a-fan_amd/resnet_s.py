@@ -541,6 +541,264 @@ class _BNEvalFn(torch.autograd.Function):
         return dx, dres, None, None
 
 
+class _BlockTail:
+    """What a block node publishes on its output tensor (`._afan_tail`) for the block node that consumes it."""
+    # (that node's first input-gradient launch can run this block's last-BatchNorm backward(s) inside itself.)  raw, stats, bn,
+    # want_pgrad: the last convolution's raw output, its BatchNorm's statistics and module, whether parameter gradients are wanted;
+    # G: the pass's group count; sc: the projection shortcut's (raw, stats, bn) or None
+    __slots__ = ("raw", "stats", "G", "bn", "want_pgrad", "sc", "consumers", "done")
+
+    def __init__(self, raw, stats, G, bn, want_pgrad, sc):
+        self.raw, self.stats, self.G, self.bn, self.want_pgrad, self.sc = raw, stats, G, bn, want_pgrad, sc
+        self.consumers = 0        # block nodes reading the output: the in-launch hand-off is for exactly one
+        self.done = 0             # set by the consumer whose launch ran that backward, reset by this block's own (_GradNote.read)
+
+
+# Sums form: `sums`, the ConvStats of the producer's last-BatchNorm backward reduction, taken by the consumer's dgrad epilogue.
+# Done form: that whole backward ran inside the launch — the tensor IS the masked gradient (the shortcut's share), `d_raw` the gradient
+# entering the last convolution's output, `pair` (where the producer's projection BatchNorm ran its backward there too) the buffer whose
+# second half holds the gradient entering the projection's output; the BatchNorms' parameter gradients are already accumulated.
+# The done form is only right if autograd delivers that very tensor, unmodified: a second consumer of the block's output makes the
+# engine add another contribution — in place (the note survives, the data does not match it) or into a new tensor (the note is lost
+# and a recomputation would count the parameter gradients twice).  read() refuses both loudly; a consumer only takes the form when it
+# is the output's one block consumer.  A note never holds the tensor it rides on, or anything that holds it: that would be a
+# reference cycle, and a dropped trainer's tensors must die by reference count.
+class _GradNote:
+    """What a consumer block's first input-gradient launch hands back to the producing block's node, on the gradient tensor."""
+    __slots__ = ("mark", "sums", "d_raw", "pair")
+
+    @staticmethod
+    def attach(g, sums=None, d_raw=None, pair=None):
+        note = g._afan_note = _GradNote()          # (mark: the tensor as it is now)
+        note.mark, note.sums, note.d_raw, note.pair = (g.data_ptr(), g._version), sums, d_raw, pair
+        return g
+
+    @staticmethod
+    def read(g, tail):
+        """(sums, d_raw, pair) for the node that published `tail`, from the gradient `g` that autograd delivers to it."""
+        note = getattr(g, "_afan_note", None)
+        fresh = note is not None and note.mark == (g.data_ptr(), g._version)
+        was_done, tail.done = tail.done, 0
+        if note is not None and note.d_raw is not None:
+            if not fresh:
+                raise ops.AfanLibraryError("block backward: the gradient tensor carrying an in-launch BatchNorm backward's results was "
+                                           "modified on its way (the block's output has another consumer, a hook or retain_grad): "
+                                           "run with resnet_s._Flags.block_fusion = False or AFAN_GRID_BN=0")
+            return None, note.d_raw, note.pair
+        if was_done:
+            raise ops.AfanLibraryError("block backward: a consumer block ran this block's last-BatchNorm backward inside its input-"
+                                       "gradient launch, but autograd delivered a different gradient tensor (the block's output has "
+                                       "another consumer): run with resnet_s._Flags.block_fusion = False or AFAN_GRID_BN=0")
+        return (note.sums if fresh else None), None, None          # (sums of a tensor that has changed since: reduce again)
+
+
+def _mom(bn):
+    return bn.momentum if bn.momentum is not None else 0.1
+
+
+# ---- the steps of _BlockFn (below), in the order they run
+def _fwd_shortcut(x, blk, stage1, G):
+    """The shortcut branch: (res, rawsc, stc, ssc, first, first_done)."""
+    # res: what the last stage adds (None: a projection in the dual form, below); rawsc, stc, ssc: the projection's raw output, moments
+    # and BatchNorm statistics; first = (raw_1, moments_1) where the chain's first convolution ran in the projection's launch,
+    # first_done = (a_1, stats_1) where its BatchNorm + ReLU did too
+    if blk._sc_kind != "conv":
+        # option-A shortcut (resnet_s.py:64-65): every second pixel, zero channels either side — data movement only
+        res = blk.shortcut(x).contiguous(memory_format=torch.channels_last) if blk._sc_kind == "pad" else x
+        return res, None, None, None, None, None
+    csc, bsc = blk.shortcut[0], blk.shortcut[1]
+    c1, b1 = stage1
+    res = ssc = first = first_done = None
+    if (_BlockFn.MULTI_SC and G == 1 and c1.stride == csc.stride and c1.dilation[0] == 1
+            and c1.out_channels == csc.out_channels
+            and ops.conv_fwd_multi_ok(x, [c1.lp_weight(), csc.lp_weight()], c1.stride[0])):
+        # a BasicBlock's first 3x3 and its 1x1 projection read the same x at the same stride and write the same
+        # shape: one launch, two problems (afan_conv_fwd_multi_nhwc_bf16)
+        # ... with the first convolution's BatchNorm + ReLU inside that launch where its workgroups fit the chip
+        fm = ops.conv_fwd_multi_bn(x, [c1.lp_weight(), csc.lp_weight()], c1.stride[0], [1, 1],
+                                   [b1.running_mean, bsc.running_mean], b1, _mom(b1)) if ops.GRID_BN else None
+        if fm is not None:
+            (raw1, rawsc), (st1, stc), act1, s1 = fm
+            first_done = (act1, s1)
+        else:
+            (raw1, rawsc), (st1, stc) = ops.conv_fwd_multi(x, [c1.lp_weight(), csc.lp_weight()], c1.stride[0], [1, 1],
+                                                           [b1.running_mean, bsc.running_mean])
+        first = (raw1, st1)
+    else:
+        rawsc, stc = ops.conv_fwd(x, csc.lp_weight(), csc.stride[0], stats_shift=bsc.running_mean, want_stats=True,
+                                  stats_buf=csc._stats_buf, groups=G)      # (1x1: no dilation)
+        csc._stats_buf = stc.partials
+    # with both convolutions' moments in accumulator blocks the projection's BatchNorm is applied by the block's
+    # LAST launch (ops.bn_train_forward_dual: relu(bn_n(raw_n) + bn_sc(raw_sc))), its output tensor never written
+    if first is None or stc.acc is None:
+        res, ssc = _bn_fwd_g(rawsc, bsc, None, False, stc, G, _mom(bsc))
+    return res, rawsc, stc, ssc, first, first_done
+
+
+def _fwd_chain(x, blk, chain, G, res, rawsc, stc, ssc, first, first_done):
+    """The conv -> BN -> ReLU stages: (block output, [raw_i, a_i, stats_i ...] to save, the projection's BatchNorm statistics)."""
+    n = len(chain)
+    dual_sc = res is None            # the projection's BatchNorm is still to be applied, by the last stage
+    bsc = blk.shortcut[1] if dual_sc else None
+    a, saved = x, []
+    for i, (c, b) in enumerate(chain):
+        last = i == n - 1
+        if i == 0 and first_done is not None and not last:
+            saved += [first[0], first_done[0], first_done[1]]
+            a = first_done[0]
+            continue
+        if G == 1 and ops.GRID_BN and not (i == 0 and first is not None) and c.kernel_size[0] in (1, 3) and c.stride[0] == 1:
+            # convolution + BatchNorm (+ shortcut) + ReLU as ONE launch (grid barrier between the sums and the second pass:
+            # ops.conv_fwd_bn); None = this launch does not take that form, the two launches below run instead (same bits)
+            kw = dict(sc=(rawsc, bsc, stc, _mom(bsc))) if (last and dual_sc) else dict(residual=res if last else None)
+            fused = ops.conv_fwd_bn(a, c.lp_weight(), b, _mom(b), relu=True, dilation=c.dilation[0], **kw)
+            if fused is not None:
+                raw, a, s_i = fused[:3]
+                ssc = fused[3] if len(fused) == 4 else ssc
+                saved += [raw, a, s_i]
+                continue
+        if i == 0 and first is not None:
+            raw, st = first
+        else:
+            raw, st = ops.conv_fwd(a, c.lp_weight(), c.stride[0], stats_shift=b.running_mean, want_stats=True,
+                                   stats_buf=c._stats_buf, groups=G, dilation=c.dilation[0])
+            c._stats_buf = st.partials
+        if last and dual_sc and st.acc is not None:
+            a, s_i, ssc = ops.bn_train_forward_dual(raw, b, st, _mom(b), rawsc, bsc, stc, _mom(bsc))
+        else:
+            if last and dual_sc:          # (the last convolution's moments did not go to accumulators after all)
+                res, ssc = _bn_fwd_g(rawsc, bsc, None, False, stc, G, _mom(bsc))
+            a, s_i = _bn_fwd_g(raw, b, res if last else None, True, st, G, _mom(b))
+        saved += [raw, a, s_i]
+    return a, saved, ssc
+
+
+def _bwd_last_bn(ctx, gout, bl, raw, out, stats):
+    """The last BatchNorm (+ residual, ReLU mask from `out`): (d_raw, the shortcut branch's share, the consumer's pair buffer | None)."""
+    # as the consumer block's launch left them (_GradNote's done form), else computed here, with that launch's sums if it took them
+    sums, d_raw, sc_done = _GradNote.read(gout, ctx.tail)
+    if d_raw is not None:
+        return d_raw, gout, sc_done                # the tensor handed back IS the shortcut's share
+    d_raw, dres = _bn_bwd_g(_like_layout(gout, out), raw, out, stats, bl, True, True, ctx.want_pgrad, sums, ctx.G)
+    return d_raw, dres, None
+
+
+def _bwd_chain(ctx, chain, d_raw, raws, acts, stats, first_out):
+    """conv_n .. conv_2, each with the BatchNorm backward in front of it: the gradient entering conv_1's output."""
+    # (written into first_out where given: the pair buffer's first half)
+    pg, G = ctx.want_pgrad, ctx.G
+    for i in range(ctx.n - 1, 0, -1):
+        c, bp = chain[i][0], chain[i - 1][1]
+        dx_out = first_out if i == 1 else None
+        # conv_i: dgrad carries bn_{i-1}'s backward reduction in its epilogue; wgrad straight into the arena
+        fused = None
+        if G == 1 and ops.GRID_BN and c.kernel_size[0] in (1, 3) and c.stride[0] == 1:
+            # ... or bn_{i-1}'s whole backward (sums -> grid barrier -> the gradient entering its input): ONE launch
+            fused = ops.conv_dgrad_bn(d_raw, c.lp_weight_t(), acts[i - 1].shape[2:], raws[i - 1], stats[i - 1], True,
+                                      dweight=bp.weight.grad if pg else None, dbias=bp.bias.grad if pg else None, accumulate=pg,
+                                      dx_out=dx_out, dilation=c.dilation[0])
+        if fused is None:
+            d_a, part = ops.conv_dgrad(d_raw, c.lp_weight_t(), acts[i - 1].shape[2:], c.stride[0],
+                                       bn_bwd=(raws[i - 1], stats[i - 1], True), partials_buf=c._bwd_buf, groups=G,
+                                       dilation=c.dilation[0])
+            c._bwd_buf = part.partials
+        if pg:
+            _wgrad_accumulate(acts[i - 1], d_raw, c)
+        if fused is not None:
+            d_raw = fused[0]
+        else:
+            d_raw, _ = _bn_bwd_g(d_a, raws[i - 1], None, stats[i - 1], bp, True, False, pg, part, G, dx_out=dx_out)
+    return d_raw
+
+
+def _takes_producer_bn(ctx):
+    """This node's input-gradient launch may run the producing block's last-BatchNorm backward inside itself."""
+    # (the gradient leaving this block is then only ever read by that backward: one block consumer; ungrouped pass, same BatchNorm branch)
+    prev = ctx.prev
+    return (prev is not None and prev.G == 1 and ops.GRID_BN and prev.consumers == 1
+            and getattr(prev.bn, "_branch", "main") == ctx.branch)
+
+
+def _hand_back(prev, fused, pair=None):
+    """fused = (d_raw, dres) of a launch that ran the producer's last-BatchNorm backward: dres is dx, the rest rides on it."""
+    prev.done = 1
+    return _GradNote.attach(fused[1], d_raw=fused[0], pair=pair)
+
+
+def _dx_plain(ctx, x, d_raw, **kw):
+    """conv_1's input gradient as a launch of its own (kw: the shortcut's share as `addend`, or the pair form's `sc`)."""
+    # where x is another block's output the epilogue takes that block's last-BatchNorm backward sums, which ride back on dx
+    c1, prev = ctx.blk._chain()[0][0], ctx.prev
+    if prev is not None:
+        kw.update(bn_bwd=(prev.raw, prev.stats, True), bn_y=x, groups=ctx.G)
+    dx = ops.conv_dgrad(d_raw, c1.lp_weight_t(), x.shape[2:], c1.stride[0], dilation=c1.dilation[0], **kw)
+    return dx if prev is None else _GradNote.attach(dx[0], sums=dx[1])
+
+
+def _dx_projection(ctx, x, d_raw, dres, rawsc, ssc, sc_done, pair, wt10):
+    """Projection shortcut: its BatchNorm's backward and weight gradient, then both branches' input gradients (one launch with `pair`)."""
+    blk, pg, need_dx = ctx.blk, ctx.want_pgrad, ctx.needs_input_grad[0]
+    c1, csc, bsc = blk._chain()[0][0], blk.shortcut[0], blk.shortcut[1]
+    if not (pg or need_dx):
+        return None
+    if sc_done is not None:
+        d_rawsc = sc_done[x.shape[0]:]
+    else:
+        d_rawsc, _ = _bn_bwd_g(dres, rawsc, None, ssc, bsc, False, False, pg, None, ctx.G,
+                               dx_out=pair[x.shape[0]:] if pair is not None else None)
+    if pg:
+        _wgrad_accumulate(x, d_rawsc, csc)
+    if not need_dx:
+        return None
+    if pair is None:
+        dx_sc = ops.conv_dgrad(d_rawsc, csc.lp_weight_t(), x.shape[2:], csc.stride[0])
+        return _dx_plain(ctx, x, d_raw, addend=dx_sc)
+    prev = ctx.prev
+    if _takes_producer_bn(ctx) and c1.stride[0] == 2:
+        # the producing block's last-BatchNorm backward inside this launch too (the stride-2 pair form: one set of
+        # sums over its four output-parity classes); that block's node finds its results on the tensor handed back
+        ppg = prev.want_pgrad
+        fused = ops.conv_dgrad_bn(d_raw, None, x.shape[2:], prev.raw, prev.stats, True, bn_y=x, want_dres=True,
+                                  dweight=prev.bn.weight.grad if ppg else None, dbias=prev.bn.bias.grad if ppg else None,
+                                  accumulate=ppg, pair=(d_rawsc, wt10))
+        if fused is not None:
+            return _hand_back(prev, fused)
+    return _dx_plain(ctx, x, d_raw, sc=(d_rawsc, wt10))
+
+
+def _dx_padded(ctx, x, d_raw, dres):
+    """Option-A shortcut: the gradient of the subsample + channel padding — the middle channels of dres land on the even pixels."""
+    pad = ctx.blk.shortcut.pad
+    dx_sc = torch.zeros_like(x)
+    dx_sc[:, :, ::2, ::2] = dres[:, pad:pad + x.shape[1]]
+    return _dx_plain(ctx, x, d_raw, addend=dx_sc)
+
+
+def _dx_identity(ctx, x, d_raw, dres):
+    """Identity shortcut: dres is added in the epilogue of conv_1's input gradient."""
+    c1, prev = ctx.blk._chain()[0][0], ctx.prev
+    if _takes_producer_bn(ctx) and c1.kernel_size[0] in (1, 3) and c1.stride[0] == 1:
+        # the gradient leaving this block is only ever read by the producing block's last-BatchNorm backward: that
+        # backward runs inside this launch and the producer's node finds its two results on the tensor handed back
+        ppg, psc = prev.want_pgrad, prev.sc
+        kw = dict(bn_y=x, addend=dres, want_dres=True, dweight=prev.bn.weight.grad if ppg else None,
+                  dbias=prev.bn.bias.grad if ppg else None, accumulate=ppg, dilation=c1.dilation[0])
+        if psc is not None and ops.GRID_BN_SC and _BlockFn.MULTI_SC and getattr(psc[2], "_branch", "main") == ctx.branch:
+            # the producing block has a projection shortcut: its BatchNorm's backward here as well, the result in the second
+            # half of the buffer that block's fused stride-2 input gradient reads (first half: its own first convolution's)
+            pair_p = torch.empty((2 * x.shape[0],) + tuple(x.shape[1:]), dtype=x.dtype, device=x.device,
+                                 memory_format=torch.channels_last)
+            fused = ops.conv_dgrad_bn(d_raw, c1.lp_weight_t(), x.shape[2:], prev.raw, prev.stats, True,
+                                      sc=(psc[0], psc[1], pair_p[x.shape[0]:], psc[2].weight.grad if ppg else None,
+                                          psc[2].bias.grad if ppg else None), **kw)
+            if fused is not None:
+                return _hand_back(prev, fused, pair_p)
+        fused = ops.conv_dgrad_bn(d_raw, c1.lp_weight_t(), x.shape[2:], prev.raw, prev.stats, True, **kw)
+        if fused is not None:
+            return _hand_back(prev, fused)
+    return _dx_plain(ctx, x, d_raw, addend=dres)
+
+
 class _BlockFn(torch.autograd.Function):
     """A whole residual block as ONE autograd node on the bf16 channels-last fast path.  The main branch is a chain of
     conv -> BN stages (2 for a BasicBlock, 3 for a Bottleneck), ReLU after each, the last one after adding the shortcut:
@@ -548,127 +806,28 @@ class _BlockFn(torch.autograd.Function):
     The hand-ordered backward fuses what autograd's per-op graph cannot: the reduction pass of bn_{i-1}'s backward rides
     in conv_i's dgrad epilogue, the sum of the two gradient branches arriving at the block input rides in conv_1's dgrad
     epilogue (no separate add launches), parameter gradients are accumulated by the kernels into the arena views, and
-    the dgrad producing the gradient for the PREVIOUS block's output also takes that block's last-BN backward sums.
+    the dgrad producing the gradient for the PREVIOUS block's output also takes that block's last-BN backward sums or runs it whole.
     `params` only tell autograd which leaves the node depends on; values are read from the modules."""
     MULTI_SC = os.environ.get("AFAN_BLOCK_MULTI_SC", "1") != "0"     # 0: the projection shortcut as its own launch (A/B)
 
     @staticmethod
     def forward(ctx, x, blk, want_pgrad, *params):
         chain = blk._chain()
-        n = len(chain)
         G = _Flags.bn_groups
-        mom = lambda bn: bn.momentum if bn.momentum is not None else 0.1
-        rawsc = ssc = first = first_done = None
-        dual_sc = False
-        if blk._sc_kind == "conv":
-            csc, bsc = blk.shortcut[0], blk.shortcut[1]
-            c1, b1 = chain[0]
-            if (_BlockFn.MULTI_SC and G == 1 and c1.stride == csc.stride and c1.dilation[0] == 1
-                    and c1.out_channels == csc.out_channels
-                    and ops.conv_fwd_multi_ok(x, [c1.lp_weight(), csc.lp_weight()], c1.stride[0])):
-                # a BasicBlock's first 3x3 and its 1x1 projection read the same x at the same stride and write the same
-                # shape: one launch, two problems (afan_conv_fwd_multi_nhwc_bf16)
-                # ... with the first convolution's BatchNorm + ReLU inside that launch where its workgroups fit the chip
-                fm = ops.conv_fwd_multi_bn(x, [c1.lp_weight(), csc.lp_weight()], c1.stride[0], [1, 1],
-                                           [b1.running_mean, bsc.running_mean], b1, mom(b1)) if ops.GRID_BN else None
-                if fm is not None:
-                    (raw1, rawsc), (st1, stc), act1, s1 = fm
-                    first_done = (act1, s1)
-                else:
-                    (raw1, rawsc), (st1, stc) = ops.conv_fwd_multi(x, [c1.lp_weight(), csc.lp_weight()], c1.stride[0], [1, 1],
-                                                                   [b1.running_mean, bsc.running_mean])
-                first = (raw1, st1)
-            else:
-                rawsc, stc = ops.conv_fwd(x, csc.lp_weight(), csc.stride[0], stats_shift=bsc.running_mean, want_stats=True,
-                                          stats_buf=csc._stats_buf, groups=G)      # (1x1: no dilation)
-                csc._stats_buf = stc.partials
-            # with both convolutions' moments in accumulator blocks the projection's BatchNorm is applied by the block's
-            # LAST launch (ops.bn_train_forward_dual: relu(bn_n(raw_n) + bn_sc(raw_sc))), its output tensor never written
-            dual_sc = first is not None and stc.acc is not None
-            if not dual_sc:
-                res, ssc = _bn_fwd_g(rawsc, bsc, None, False, stc, G, mom(bsc))
-        elif blk._sc_kind == "pad":
-            # option-A shortcut (resnet_s.py:64-65): every second pixel, zero channels either side — data movement only
-            res = blk.shortcut(x).contiguous(memory_format=torch.channels_last)
-        else:
-            res = x
-        a, saved = x, []
-        for i, (c, b) in enumerate(chain):
-            last = i == n - 1
-            if i == 0 and first_done is not None and not last:
-                saved += [first[0], first_done[0], first_done[1]]
-                a = first_done[0]
-                continue
-            if G == 1 and ops.GRID_BN and not (i == 0 and first is not None) and c.kernel_size[0] in (1, 3) and c.stride[0] == 1:
-                # convolution + BatchNorm (+ shortcut) + ReLU as ONE launch (grid barrier between the sums and the second pass:
-                # ops.conv_fwd_bn); None = this launch does not take that form, the two launches below run instead (same bits)
-                if last and dual_sc:
-                    fused = ops.conv_fwd_bn(a, c.lp_weight(), b, mom(b), relu=True, sc=(rawsc, bsc, stc, mom(bsc)), dilation=c.dilation[0])
-                else:
-                    fused = ops.conv_fwd_bn(a, c.lp_weight(), b, mom(b), residual=res if last else None, relu=True, dilation=c.dilation[0])
-                if fused is not None:
-                    if len(fused) == 4:
-                        raw, a, s_i, ssc = fused
-                    else:
-                        raw, a, s_i = fused
-                    saved += [raw, a, s_i]
-                    continue
-            if i == 0 and first is not None:
-                raw, st = first
-            else:
-                raw, st = ops.conv_fwd(a, c.lp_weight(), c.stride[0], stats_shift=b.running_mean, want_stats=True,
-                                       stats_buf=c._stats_buf, groups=G, dilation=c.dilation[0])
-                c._stats_buf = st.partials
-            if i == n - 1 and dual_sc and st.acc is not None:
-                a, s_i, ssc = ops.bn_train_forward_dual(raw, b, st, mom(b), rawsc, bsc, stc, mom(bsc))
-            else:
-                if i == n - 1 and dual_sc:          # (the last convolution's moments did not go to accumulators after all)
-                    res, ssc = _bn_fwd_g(rawsc, bsc, None, False, stc, G, mom(bsc))
-                a, s_i = _bn_fwd_g(raw, b, res if i == n - 1 else None, True, st, G, mom(b))
-            saved += [raw, a, s_i]
-        ctx.blk, ctx.want_pgrad, ctx.n, ctx.G = blk, want_pgrad, n, G
+        res, rawsc, stc, ssc, first, first_done = _fwd_shortcut(x, blk, chain[0], G)
+        a, saved, ssc = _fwd_chain(x, blk, chain, G, res, rawsc, stc, ssc, first, first_done)
+        ctx.blk, ctx.want_pgrad, ctx.n, ctx.G = blk, want_pgrad, len(chain), G
         ctx.branch = _Flags.bn_branch      # dual-BN: the backward reads the same parameter set from the modules
         # cross-block fusion: when x is the output of another _BlockFn, this block's input-gradient dgrad also takes the
         # reduction sums of THAT block's last BN backward (its ReLU mask is x > 0) — see backward
-        prev = getattr(x, "_afan_bn2", None) if _Flags.block_fusion else None
-        ctx.prev_bn = prev if (prev is not None and prev[2] == G) else None
+        prev = getattr(x, "_afan_tail", None) if _Flags.block_fusion else None
+        ctx.prev = prev if (prev is not None and prev.G == G) else None
         if prev is not None:
-            prev[6]["consumers"] += 1      # (block nodes reading the producer's output: the in-launch hand-off below is for exactly one)
-        ctx.handoff = {"consumers": 0, "done": 0}
+            prev.consumers += 1
         ctx.save_for_backward(x, rawsc, ssc, *saved)
-        # (raw_n, stats_n, G, bn_n, want_pgrad, the projection shortcut's (raw, stats, bn) or None): what a consumer block's first
-        # input-gradient launch needs to run this block's last-BatchNorm backward(s) inside itself
-        # [6]: the hand-off's bookkeeping, shared with this node's backward (see _handoff_check)
-        a._afan_bn2 = (saved[-3], saved[-1], G, chain[-1][1], want_pgrad,
-                       (rawsc, ssc, blk.shortcut[1]) if (blk._sc_kind == "conv" and ssc is not None) else None, ctx.handoff)
+        ctx.tail = a._afan_tail = _BlockTail(saved[-3], saved[-1], G, chain[-1][1], want_pgrad,
+                                             (rawsc, ssc, blk.shortcut[1]) if (blk._sc_kind == "conv" and ssc is not None) else None)
         return a
-
-    @staticmethod
-    def _handoff_check(ctx, gout):
-        """The consumer block's first input-gradient launch may have run THIS block's last-BatchNorm backward inside itself and
-        handed the results over as attributes of the gradient tensor (`_afan_bn_done`: the masked gradient IS the tensor, d_raw rides
-        on it, the BatchNorm's parameter gradients are already accumulated).  That is only right if autograd delivers that very
-        tensor, unmodified: a second consumer of the block's output makes the engine add another contribution — in place (the
-        attribute survives, the data does not match it) or into a new tensor (the attribute is lost and a recomputation would count
-        the parameter gradients twice).  Both are refused loudly here; a consumer only takes the form when it is the output's one
-        block consumer (`consumers == 1`)."""
-        st = ctx.handoff
-        done = getattr(gout, "_afan_bn_done", None)
-        mark = getattr(gout, "_afan_handoff", None)
-        was_done, st["done"] = st["done"], 0
-        if done is not None:
-            if mark != (gout.data_ptr(), gout._version):
-                raise ops.AfanLibraryError("block backward: the gradient tensor carrying an in-launch BatchNorm backward's results was "
-                                           "modified on its way (the block's output has another consumer, a hook or retain_grad): "
-                                           "run with resnet_s._Flags.block_fusion = False or AFAN_GRID_BN=0")
-        elif was_done:
-            raise ops.AfanLibraryError("block backward: a consumer block ran this block's last-BatchNorm backward inside its input-"
-                                       "gradient launch, but autograd delivered a different gradient tensor (the block's output has "
-                                       "another consumer): run with resnet_s._Flags.block_fusion = False or AFAN_GRID_BN=0")
-        pre = getattr(gout, "_afan_bn_sums", None)
-        if pre is not None and getattr(gout, "_afan_sums_mark", None) != (gout.data_ptr(), gout._version):
-            pre = None                                 # (sums of a tensor that has changed since: reduce again)
-        return pre, done
 
     @staticmethod
     def backward(ctx, gout):
@@ -701,132 +860,28 @@ class _BlockFn(torch.autograd.Function):
     @staticmethod
     def _backward_impl(ctx, gout):
         x, rawsc, ssc, *saved = ctx.saved_tensors
-        blk, pg, n, G = ctx.blk, ctx.want_pgrad, ctx.n, ctx.G
-        chain = blk._chain()
+        blk, G, chain = ctx.blk, ctx.G, ctx.blk._chain()
         raws, acts, stats = saved[0::3], saved[1::3], saved[2::3]
         need_dx = ctx.needs_input_grad[0]
-        g = lambda p: p.grad if pg else None
-        out = acts[-1]
-        # pre: this block's last-BatchNorm backward SUMS, taken by the consumer block's dgrad epilogue (same tensor object);
-        # done: ... or that whole backward, done inside that launch:
-        pre, done = _BlockFn._handoff_check(ctx, gout)
-        # last BN (+residual, ReLU mask from `out`): gradient to its conv output and to the shortcut branch
-        bl = chain[-1][1]
-        if done is not None:
-            d_raw, dres = done, gout                   # the tensor handed back IS the shortcut's share; the other result rides on it
-        else:
-            gout = _like_layout(gout, out)
-            d_raw, dres = _bn_bwd_g(gout, raws[-1], out, stats[-1], bl, True, True, pg, pre, G)
+        c1, r0 = chain[0][0], raws[0]
+        d_raw, dres, sc_done = _bwd_last_bn(ctx, gout, chain[-1][1], raws[-1], acts[-1], stats[-1])
         # the first convolution's and the projection's output gradients side by side in one buffer: their input gradients
         # are ONE launch (afan_conv_dgrad_sc_nhwc_bf16) when the arena holds the block's combined [Ci][10][Co] operand
-        c1 = chain[0][0]
+        # (sc_done: a pair buffer the consumer made, its second half already holding the projection BatchNorm's backward)
         wt10 = getattr(c1, "_arena_wt10", None) if (_BlockFn.MULTI_SC and blk._sc_kind == "conv" and G == 1 and need_dx
-                                                     and n >= 2) else None
+                                                     and ctx.n >= 2) else None
         pair = None
-        # ... and the projection BatchNorm's backward too: its result sits in the second half of a pair buffer the consumer made
-        sc_done = getattr(gout, "_afan_sc_done", None) if done is not None else None
-        r0 = raws[0]
         if wt10 is not None:
             pair = sc_done if sc_done is not None else torch.empty((2 * r0.shape[0],) + tuple(r0.shape[1:]), dtype=r0.dtype,
                                                                    device=r0.device, memory_format=torch.channels_last)
-        for i in range(n - 1, 0, -1):
-            c, bp = chain[i][0], chain[i - 1][1]
-            # conv_i: dgrad carries bn_{i-1}'s backward reduction in its epilogue; wgrad straight into the arena
-            fused = None
-            if G == 1 and ops.GRID_BN and c.kernel_size[0] in (1, 3) and c.stride[0] == 1:
-                # ... or bn_{i-1}'s whole backward (sums -> grid barrier -> the gradient entering its input): ONE launch
-                fused = ops.conv_dgrad_bn(d_raw, c.lp_weight_t(), acts[i - 1].shape[2:], raws[i - 1], stats[i - 1], True,
-                                          dweight=g(bp.weight), dbias=g(bp.bias), accumulate=pg,
-                                          dx_out=pair[:r0.shape[0]] if (pair is not None and i == 1) else None, dilation=c.dilation[0])
-            if fused is None:
-                d_a, part = ops.conv_dgrad(d_raw, c.lp_weight_t(), acts[i - 1].shape[2:], c.stride[0],
-                                           bn_bwd=(raws[i - 1], stats[i - 1], True), partials_buf=c._bwd_buf, groups=G,
-                                           dilation=c.dilation[0])
-                c._bwd_buf = part.partials
-            if pg:
-                _wgrad_accumulate(acts[i - 1], d_raw, c)
-            if fused is not None:
-                d_raw = fused[0]
-                continue
-            d_raw, _ = _bn_bwd_g(d_a, raws[i - 1], None, stats[i - 1], bp, True, False, pg, part, G,
-                                 dx_out=pair[:r0.shape[0]] if (pair is not None and i == 1) else None)
-        if pg:
+        d_raw = _bwd_chain(ctx, chain, d_raw, raws, acts, stats, pair[:r0.shape[0]] if pair is not None else None)
+        if ctx.want_pgrad:
             _wgrad_accumulate(x, d_raw, c1)
         dx = None
-        prev = ctx.prev_bn
-        fuse = dict(bn_bwd=(prev[0], prev[1], True), bn_y=x, groups=G) if (prev is not None and need_dx) else {}
-        fuse["dilation"] = c1.dilation[0]
         if blk._sc_kind == "conv":
-            csc, bsc = blk.shortcut[0], blk.shortcut[1]
-            if pg or need_dx:
-                if sc_done is not None:
-                    d_rawsc = sc_done[r0.shape[0]:]
-                else:
-                    d_rawsc, _ = _bn_bwd_g(dres, rawsc, None, ssc, bsc, False, False, pg, None, G,
-                                           dx_out=pair[r0.shape[0]:] if pair is not None else None)
-                if pg:
-                    _wgrad_accumulate(x, d_rawsc, csc)
-                if need_dx and pair is not None:
-                    if (prev is not None and G == 1 and ops.GRID_BN and len(prev) >= 5 and c1.stride[0] == 2
-                            and prev[6]["consumers"] == 1 and getattr(prev[3], "_branch", "main") == ctx.branch):
-                        # the producing block's last-BatchNorm backward inside this launch too (the stride-2 pair form: one set of
-                        # sums over its four output-parity classes); that block's node finds its results on the tensor handed back
-                        pbn, ppg = prev[3], prev[4]
-                        fused = ops.conv_dgrad_bn(d_raw, None, x.shape[2:], prev[0], prev[1], True, bn_y=x, want_dres=True,
-                                                  dweight=pbn.weight.grad if ppg else None, dbias=pbn.bias.grad if ppg else None,
-                                                  accumulate=ppg, pair=(d_rawsc, wt10))
-                        if fused is not None:
-                            dx = fused[1]
-                            dx._afan_bn_done = fused[0]
-                            dx._afan_handoff = (dx.data_ptr(), dx._version)
-                            prev[6]["done"] = 1
-                            return (dx, None, None) + (None,) * (len(ctx.needs_input_grad) - 3)
-                    dx = ops.conv_dgrad(d_raw, c1.lp_weight_t(), x.shape[2:], c1.stride[0], sc=(d_rawsc, wt10), **fuse)
-                elif need_dx:
-                    dx_sc = ops.conv_dgrad(d_rawsc, csc.lp_weight_t(), x.shape[2:], csc.stride[0])
-                    dx = ops.conv_dgrad(d_raw, c1.lp_weight_t(), x.shape[2:], c1.stride[0], addend=dx_sc, **fuse)
-        elif blk._sc_kind == "pad":
-            if need_dx:
-                # gradient of the subsample + channel padding: the middle channels of dres land on the even pixels
-                pad = blk.shortcut.pad
-                dx_sc = torch.zeros_like(x)
-                dx_sc[:, :, ::2, ::2] = dres[:, pad:pad + x.shape[1]]
-                dx = ops.conv_dgrad(d_raw, c1.lp_weight_t(), x.shape[2:], c1.stride[0], addend=dx_sc, **fuse)
+            dx = _dx_projection(ctx, x, d_raw, dres, rawsc, ssc, sc_done, pair, wt10)
         elif need_dx:
-            fused = pair_p = None
-            if (prev is not None and G == 1 and ops.GRID_BN and len(prev) >= 5 and c1.kernel_size[0] in (1, 3) and c1.stride[0] == 1
-                    and prev[6]["consumers"] == 1 and getattr(prev[3], "_branch", "main") == ctx.branch):
-                # the gradient leaving this block is only ever read by the producing block's last-BatchNorm backward: that
-                # backward runs inside this launch and the producer's node finds its two results on the tensor handed back
-                pbn, ppg = prev[3], prev[4]
-                kw = dict(bn_y=x, addend=dres, want_dres=True, dweight=pbn.weight.grad if ppg else None,
-                          dbias=pbn.bias.grad if ppg else None, accumulate=ppg, dilation=c1.dilation[0])
-                psc = prev[5] if (len(prev) > 5 and ops.GRID_BN_SC and _BlockFn.MULTI_SC) else None
-                if psc is not None and getattr(psc[2], "_branch", "main") == ctx.branch:
-                    # the producing block has a projection shortcut: its BatchNorm's backward here as well, the result in the second
-                    # half of the buffer that block's fused stride-2 input gradient reads (first half: its own first convolution's)
-                    pair_p = torch.empty((2 * x.shape[0],) + tuple(x.shape[1:]), dtype=x.dtype, device=x.device,
-                                         memory_format=torch.channels_last)
-                    fused = ops.conv_dgrad_bn(d_raw, c1.lp_weight_t(), x.shape[2:], prev[0], prev[1], True,
-                                              sc=(psc[0], psc[1], pair_p[x.shape[0]:], psc[2].weight.grad if ppg else None,
-                                                  psc[2].bias.grad if ppg else None), **kw)
-                    if fused is None:
-                        pair_p = None
-                if fused is None:
-                    fused = ops.conv_dgrad_bn(d_raw, c1.lp_weight_t(), x.shape[2:], prev[0], prev[1], True, **kw)
-            if fused is not None:
-                dx = fused[1]
-                dx._afan_bn_done = fused[0]            # (not the pair: a tuple holding dx on dx would be a reference cycle)
-                dx._afan_handoff = (dx.data_ptr(), dx._version)
-                prev[6]["done"] = 1
-                if pair_p is not None:
-                    dx._afan_sc_done = pair_p
-                return (dx, None, None) + (None,) * (len(ctx.needs_input_grad) - 3)
-            dx = ops.conv_dgrad(d_raw, c1.lp_weight_t(), x.shape[2:], c1.stride[0], addend=dres, **fuse)
-        if "bn_bwd" in fuse and dx is not None:
-            dx, sums = dx
-            dx._afan_bn_sums = sums
-            dx._afan_sums_mark = (dx.data_ptr(), dx._version)
+            dx = (_dx_padded if blk._sc_kind == "pad" else _dx_identity)(ctx, x, d_raw, dres)
         return (dx, None, None) + (None,) * (len(ctx.needs_input_grad) - 3)
 
 
