@@ -549,6 +549,10 @@ class BottleneckResNet(nn.Module):
         return nn.Sequential(*layers)
 
     def _stem(self, x):
+        if frozen.STEM_IMAGE_GRAD:                  # (an image under attack, frozen stem: one node, one backward launch)
+            y = frozen.stem_node(self, x, _Stem7Fn.DIRECT)
+            if y is not None:
+                return y
         x = self.normal(x)
         x = self.bn1.fused(self.conv1(x), None, True)
         return self.maxpool(x)

@@ -5,6 +5,7 @@ behaviour of the reference's `Detection/attack_algo.py`, and the loop body of `D
     PGD(x, image_batch, y, model, steps, eps, gamma, idx, randinit, clip)                                 :48-74
     rpn_roi_PGD(layer, rpn_roi_output_dict, y, model, steps, eps, gamma, randinit, clip, only_roi_loss)   :77-150
     adv_input(x, y, model, steps, eps, gamma, randinit, clip)                                             :153-178
+    eval_PGD(x, y, model, steps, eps, gamma, idx, randinit, clip)                                         :207-233
     get_sample_points / mix_feature / tensor_clamp / linfball_proj                      (shared with attack_algo.py)
     det_train_step(model, optimizer, image_batch, bboxes_batch, labels_batch, loss_settings)   train_aug_sat_muti_advt.py:70-172
     det_train_phases(...)                         the same iteration as a generator with the backward cut at the backbone's output
@@ -143,6 +144,20 @@ def adv_input(x=None, y=None, model=None, steps=3, eps=None, gamma=None, randini
     for _ in range(steps):
         pgd.ascend(x_adv, loss_of, gamma, x, eps, clip)
     return pgd.clamp01_(x_adv).requires_grad_(True)
+
+
+def eval_PGD(x, y=None, model=None, steps=3, eps=None, gamma=None, idx=1, randinit=False, clip=False, start=None):
+    """:207-233: the image-space PGD of the robust evaluation (eval_rob_ori.py -> evaluator.py:90-128) under the sum of the four
+    losses' means, train-mode forward, dict {'x': x_adv, 'adv': None, 'out_idx': 0, 'flag': 'clean'}; the random start is drawn on the
+    host.  Unlike adv_input there is NO final clamp to [0, 1], and without `clip` nothing projects.  `idx` is accepted and unused, as
+    in the reference.  start (an addition): the iterate to continue from instead of x (+ the random start): a run cut into pieces."""
+    x, x_adv = pgd.start(x, eps, randinit and start is None)
+    if start is not None:
+        x_adv.copy_(start)
+    loss_of = lambda t: compute_loss(*model.train().forward({"x": t, "adv": None, "out_idx": 0, "flag": "clean"}, y["bb"], y["lb"]))
+    for _ in range(steps):
+        pgd.ascend(x_adv, loss_of, gamma, x, eps, clip)
+    return x_adv.requires_grad_(True)
 
 
 def det_train_step(model, optimizer, image_batch, bboxes_batch, labels_batch, loss_settings=1):

@@ -266,9 +266,35 @@ def save_checkpoint(path_to_checkpoints_dir, step, model, optimizer, cfg):
     return path_to_checkpoint
 
 
-def load_checkpoint(path_to_checkpoint, model, optimizer=None, arena=None):
-    """Model.load (model.py:200-217): the keys the checkpoint and the model share are loaded, the rest keep their values -> step."""
+def convert_dict(ori_dict):
+    """model.py:420-437 as written: the keys of a checkpoint whose backbone was an nn.Sequential (`features.0.` .. `features.6`) renamed
+    to this model's (`features.conv1.` .. `features.layer3`).  `str.replace` replaces EVERY occurrence of the digit, so a key that holds
+    it twice (layer3's blocks 6 and 16, `features.4.2.conv1...` keeps its `conv1` only because the digit there is 1) comes out mangled
+    and is then dropped by load_checkpoint's overlap rule: the `Load Weight:[k/n]` line shows it."""
+    new_dict = {}
+    for k, v in ori_dict.items():
+        if "features.0." in k and "rpn" not in k:
+            j = k.replace("0", "conv1")
+        elif "features.1." in k:
+            j = k.replace("1", "bn1")
+        elif "features.4" in k:
+            j = k.replace("4", "layer1")
+        elif "features.5" in k:
+            j = k.replace("5", "layer2")
+        elif "features.6" in k:
+            j = k.replace("6", "layer3")
+        else:
+            j = k
+        new_dict[j] = v
+    return new_dict
+
+
+def load_checkpoint(path_to_checkpoint, model, optimizer=None, arena=None, convert=False):
+    """Model.load (model.py:200-217): the keys the checkpoint and the model share are loaded, the rest keep their values -> step.
+    convert: `convert_dict` on the checkpoint's keys first (:203-204)."""
     checkpoint = torch.load(path_to_checkpoint, map_location="cpu", weights_only=False)
+    if convert:
+        checkpoint['state_dict'] = convert_dict(checkpoint['state_dict'])
     model_state_dict = model.state_dict()
     overlap_dict = {k: v for k, v in checkpoint['state_dict'].items() if k in model_state_dict.keys()}
     model_state_dict.update(overlap_dict)

@@ -1,5 +1,6 @@
 """Detection evaluation: the VOC 2007 mean AP of the reference (Detection/voc_eval.py, dataset/voc2007.py:118-161, evaluator.py:20-47,
-eval.py) on in-memory arrays, the evaluator around Model.forward in eval mode, and the driver of eval.py.
+eval.py) on in-memory arrays, the evaluator around Model.forward in eval mode, the robust evaluator (evaluator.py:90-128: an image PGD
+in front of that forward) and the drivers of eval.py and eval_rob_ori.py.
 
 The metric runs on the host in numpy, float64, operation by operation as the reference does.  What the reference does on the way
 is part of its number and kept:
@@ -166,12 +167,17 @@ class Evaluator:
             raise ValueError("the ground truth names one image per image of the loader")
         self.results_dir = results_dir
 
+    def attack(self, model, index, image_batch, bboxes_batch, labels_batch):
+        """The image the eval-mode forward sees for image `index` of the list: the clean one here."""
+        return image_batch
+
     def detect(self, model):
         """-> (image ids, boxes, classes, probs) as the lists evaluator.py:41-44 builds."""
         import torch
         all_image_ids, all_bboxes, all_classes, all_probs = [], [], [], []
-        with torch.no_grad():
-            for image_id, (image_batch, _, _, scale_batch) in zip(self.image_ids, self.loader):
+        for index, (image_id, (image_batch, bboxes_batch, labels_batch, scale_batch)) in enumerate(zip(self.image_ids, self.loader)):
+            image_batch = self.attack(model, index, image_batch, bboxes_batch, labels_batch)
+            with torch.no_grad():
                 inputs_all = {"x": image_batch, "adv": None, "out_idx": None, "flag": 'clean', "min_prob": MIN_PROB}
                 bboxes, classes, probs, batch_indices = model.eval().forward(inputs_all)
                 bboxes = bboxes / scale_batch[batch_indices.to(scale_batch.device)].unsqueeze(dim=-1).expand_as(bboxes)
@@ -187,6 +193,50 @@ class Evaluator:
 
     def evaluate(self, model):
         return evaluate(self.ground_truth, *self.detect(model), path_to_results_dir=self.results_dir)
+
+
+# The one-launch stem image gradient (frozen.STEM_IMAGE_GRAD) during the robust evaluation's attack.  Decided by the project's rule for
+# every switch — on only where the measured gain of one image's attack + detection exceeds the two arms' combined min-max spread
+# (tools/probe/det_rob_time.py, profiles/det_rob_time.jsonl; README "Detection robust mAP").  Measured: no gain, so OFF here too;
+# AFAN_DET_ROB_STEM=1 (or RobustEvaluator(stem_image_grad=True)) turns it on.
+ROB_STEM_IMAGE_GRAD = os.environ.get("AFAN_DET_ROB_STEM", "0") == "1"
+
+
+class RobustEvaluator(Evaluator):
+    """evaluator.py:90-128 (`ori_rob_evaluate`): per image attack_algo.eval_PGD with gradients enabled — steps, eps / 255, gamma / 255,
+    randinit, clip — then Evaluator.detect's eval-mode forward, scale division, single host copy and lists on the adversarial image.
+    An image without a non-difficult object has no loss (the reference raises on it): it is scored unattacked and counted
+    (`self.unattacked`; one log line with the count).  stem_image_grad (None: ROB_STEM_IMAGE_GRAD): frozen.STEM_IMAGE_GRAD for the
+    attack's duration.  steps = 0 without randinit hands the forward the clean image's values: Evaluator.detect's lists."""
+
+    def __init__(self, loader, ground_truth, results_dir=None, steps=10, eps=2.0, gamma=0.5, randinit=False, clip=False,
+                 stem_image_grad=None, log=None):
+        super().__init__(loader, ground_truth, results_dir)
+        self.steps, self.eps, self.gamma, self.randinit, self.clip = int(steps), float(eps), float(gamma), bool(randinit), bool(clip)
+        self.stem_image_grad = ROB_STEM_IMAGE_GRAD if stem_image_grad is None else bool(stem_image_grad)
+        self.log, self.unattacked, self.attacked = log, 0, 0
+
+    def attack(self, model, index, image_batch, bboxes_batch, labels_batch):
+        import torch
+        from . import det_attack_algo, frozen
+        if int(self.loader.counts[index]) == 0:      # (the host's own count: no read of the device)
+            self.unattacked += 1
+            return image_batch
+        self.attacked += 1
+        with torch.enable_grad(), frozen.stem_image_grad(self.stem_image_grad):
+            adv = det_attack_algo.eval_PGD(x=image_batch, y={'bb': bboxes_batch, 'lb': labels_batch}, model=model, steps=self.steps,
+                                           eps=(self.eps / 255), gamma=(self.gamma / 255), randinit=self.randinit, clip=self.clip)
+        return adv.detach()
+
+    def detect(self, model):
+        self.unattacked = self.attacked = 0
+        out = super().detect(model)
+        line = 'Scored {:d} images without a non-difficult object unattacked (no loss to ascend)'.format(self.unattacked)
+        if self.log is not None:
+            self.log.i(line)
+        else:
+            print(line, flush=True)
+        return out
 
 
 # ------------------------------------------------------------------------------------ the driver of eval.py
@@ -264,6 +314,60 @@ def build_eval_split(args, cfg):
         return s.images, s.boxes, s.classes, (s.image_ids, s.ground_truth()), s.num_classes
     images, boxes, classes, image_ids, ground_truth = det_data.load_voc_det_eval(args.data_dir, args.dataset)
     return images, boxes, classes, (image_ids, ground_truth), NUM_CLASSES
+
+
+def get_rob_argparser(full=True):
+    """eval_rob_ori.py:41-60, flag for flag (the PGD settings, --convert, then eval.py's flags); full: the project's additions too."""
+    parser = get_full_argparser() if full else get_argparser()
+    eval_actions = parser._actions[1:]                                   # (behind -h) eval.py's flags, in their order
+    rob = argparse.ArgumentParser()
+    # PGD Setting
+    rob.add_argument('--steps', default=10, type=int, help='PGD-steps')
+    rob.add_argument('--gamma', help='index of PGD gamma', default=0.5, type=float)
+    rob.add_argument('--eps', default=2, type=float)
+    rob.add_argument('--randinit', action="store_true", help="random start inside the eps-ball")
+    rob.add_argument('--clip', action="store_true", help="project onto the eps-ball after every step")
+    rob.add_argument('--convert', action="store_true", help="rename the keys of a Sequential-backbone checkpoint (model.py:420-437)")
+    for a in eval_actions:
+        rob._add_action(a)
+    return rob
+
+
+def main_rob(program, argv=None):
+    """eval_rob_ori.py: robust mAP under an image PGD."""
+    from . import det_data, det_entry
+    args = get_rob_argparser().parse_args(argv)
+    det_entry.print_args(args)
+    check_unbuilt(args)
+    cfg = config(args)
+    device = det_entry.setup_device(program)
+
+    path_to_checkpoint = args.checkpoint
+    path_to_results_dir = results_dir(path_to_checkpoint)
+    os.makedirs(path_to_results_dir)
+    log = det_entry.Log(os.path.join(path_to_results_dir, 'eval.log'))
+    log.i('Arguments:')
+    for k, v in vars(args).items():
+        log.i(f'\t{k} = {v}')
+    log.i(det_entry.describe(cfg))
+
+    images, boxes, classes, ground_truth, num_classes = build_eval_split(args, cfg)
+    loader = det_data.DetDeviceLoader(images, boxes, classes, 1, device, False, cfg["image_min_side"], cfg["image_max_side"])
+    evaluator = RobustEvaluator(loader, ground_truth, path_to_results_dir, steps=args.steps, eps=args.eps, gamma=args.gamma,
+                                randinit=args.randinit, clip=args.clip, log=log)
+    log.i('Found {:d} samples'.format(len(images)))
+
+    model_cfg = dict(det_entry.DEFAULTS)
+    model_cfg.update(cfg)
+    model = det_entry.build_model(args, model_cfg, num_classes).to(device)
+    det_entry.load_checkpoint(path_to_checkpoint, model, convert=args.convert)
+
+    log.i('Start evaluating Robustness with 1 GPU (1 batch per GPU)')
+    mean_ap, detail = evaluator.evaluate(model)
+    log.i('Done')
+    log.i('syd: pgd attack mean AP = {:.4f}'.format(mean_ap))
+    log.i('\n' + detail)
+    return mean_ap, detail
 
 
 def main(program, argv=None):

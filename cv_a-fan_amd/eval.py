@@ -6,8 +6,9 @@ What differs from the reference is execution only: the forward is det_model's ev
 NMS for all 20 classes) is one launch (det_ops.class_nms); the batch is built on the device by det_data.DetDeviceLoader; the metric
 is det_eval's restatement of voc_eval.py on in-memory arrays, with the reference's text round trip applied to the numbers.
 
-Not built here: robust mAP (eval_rob.py), layer-wise SAT evaluation, COCO; backbones other than resnet101 (they raise, each with its
-reason)."""
+Robust mAP is its own program, eval_rob_ori.py (the reference's working one).  Not built: eval_rob.py (the reference's dead one: it
+calls attack_algo.untarget_PGD, which is commented out), layer-wise SAT evaluation, COCO; backbones other than resnet101 (they raise,
+each with its reason)."""
 import os
 import sys
 

@@ -5,7 +5,9 @@ frozen by type, det_model.FrozenBatchNorm2d) and DeepLab's in eval mode (deeplab
   * the launch plan of a block (`block_plan`: eligibility, ops.frozen_bottleneck_plan, one cache on the block with one validity
     stamp read from the live module attributes);
   * the autograd nodes over ops.frozen_bottleneck_fwd_plan / _bwd_plan: one per block (`_FrozenBlockFn`), one per stage
-    (`_FrozenStageFn`, `_run_stage`, `stage_input_gradient`) and the stage replayed from hipGraphs (`_StageGraphs`).
+    (`_FrozenStageFn`, `_run_stage`, `stage_input_gradient`) and the stage replayed from hipGraphs (`_StageGraphs`);
+  * the image end of the backbone as one node (`_FrozenStemFn`, `stem_node`: normaliser, 7x7 stem, frozen BatchNorm + ReLU, max pool)
+    whose backward is ONE launch, behind the switch STEM_IMAGE_GRAD.
 
 What differs between the callers are arguments of `block_plan` ("The frozen bottleneck path"); the switches stay with
 their families (deeplab.FROZEN_EVAL / COEF_CACHE; AFAN_DET_BLOCK_NODE / _STAGE_NODE / _GRAPHS act on Detection's calls only)."""
@@ -416,3 +418,77 @@ def _run_stage(stage, x):
                 return inst.out.detach()
             return _GraphedStageFn.apply(x, inst, *params)
     return _FrozenStageFn.apply(x, tuple(plans), *params)
+
+
+# ------------------------------------------------------------------------------------------------------- the image end
+# The stem of a frozen-BatchNorm backbone under an image attack (normaliser -> conv1 7x7 / 2 -> bn1 + ReLU -> max pool 3 / 2 / 1) as ONE
+# autograd node whose backward is ONE launch (ops.frozen_stem_image_grad) instead of six (pool backward, affine backward, the 1x1 MFMA
+# problem into a 41 MB column tensor at 600 x 904, col2im, the normaliser's division, a cast).  Off by default, read at call time; only
+# det_eval.RobustEvaluator turns it on (`stem_image_grad()`), for the duration of its attack: Detection training's adv_input,
+# Segmentation's image PGD and infer.Attacker keep the layer-by-layer nodes and their bits (the one-launch form rounds the gradient
+# once where the chain rounds it four times).
+STEM_IMAGE_GRAD = os.environ.get("AFAN_STEM_IMAGE_GRAD", "0") == "1"
+
+
+class stem_image_grad:
+    """`with frozen.stem_image_grad(True):` sets the switch for the block."""
+
+    def __init__(self, on=True):
+        self.on = bool(on)
+
+    def __enter__(self):
+        global STEM_IMAGE_GRAD
+        self.old, STEM_IMAGE_GRAD = STEM_IMAGE_GRAD, self.on
+        return self
+
+    def __exit__(self, *exc):
+        global STEM_IMAGE_GRAD
+        STEM_IMAGE_GRAD = self.old
+        return False
+
+
+class _FrozenStemFn(torch.autograd.Function):
+    """`BottleneckResNet._stem` on an image that carries a gradient: the forward issues that method's launches (normalise; im2col and
+    the 1x1 MFMA problem of deeplab._Stem7Fn; the fused affine + ReLU; the max pool) and gives its bits, keeping the post-ReLU map y1
+    instead of the column tensor; the backward is afan_frozen_stem_image_grad.  Input gradient only."""
+
+    @staticmethod
+    def forward(ctx, x, mean, std, w_lp, coefs):
+        xn = ops.normalize_nchw(x.detach().contiguous().float(), mean, std, torch.bfloat16, True)
+        cols = ops.conv_stem7_im2col(xn)
+        k = cols.shape[1]
+        wp = torch.zeros((64, k, 1, 1), dtype=torch.bfloat16, device=x.device)
+        wp.view(64, k)[:, :147] = w_lp.permute(0, 2, 3, 1).reshape(64, 147)
+        y1 = ops.affine_apply(ops.conv_fwd(cols, wp.contiguous(memory_format=torch.channels_last), 1), coefs, None, True)
+        out, _ = ops.maxpool2d(y1, 3, 2, 1, want_idx=False)
+        ctx.w_lp, ctx.alpha, ctx.in_hw = w_lp, coefs[2], tuple(x.shape[2:])
+        ctx.inv_std = (1.0 / std.float()).contiguous()
+        ctx.save_for_backward(y1, out)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        y1, out = ctx.saved_tensors
+        g = _like_layout(g, out)
+        if g.dtype != out.dtype:
+            g = g.to(out.dtype)
+        return ops.frozen_stem_image_grad(g, y1, ctx.w_lp, ctx.alpha, ctx.inv_std, ctx.in_hw), None, None, None, None
+
+
+def stem_node(net, x, direct=False):
+    """`net._stem(x)` as one `_FrozenStemFn` node, or None where that form does not apply: the switch is off, the image carries no
+    gradient, the path is not bf16 channels-last, bn1 is not frozen by type, conv1 would take a weight gradient, or the stem runs its
+    direct kernels (`direct`: deeplab._Stem7Fn.DIRECT)."""
+    if not (STEM_IMAGE_GRAD and not direct and torch.is_grad_enabled() and x.requires_grad and x.is_cuda and x.dim() == 4 and x.shape[1] == 3):
+        return None
+    conv, bn, norm, pool = net.conv1, net.bn1, net.normal, net.maxpool
+    if not (conv.compute_dtype == torch.bfloat16 and norm.channels_last and norm.out_dtype == torch.bfloat16 and conv.bias is None
+            and callable(getattr(bn, "_coefs", None)) and (pool.kernel_size, pool.stride, pool.padding) == (3, 2, 1)):
+        return None
+    if (_Flags.param_grads and conv.weight.requires_grad) or bn.weight.requires_grad or bn.bias.requires_grad:
+        return None
+    w = conv.lp_weight()
+    if not (tuple(w.shape) == (64, 3, 7, 7) and w.dtype == torch.bfloat16 and w.is_contiguous(memory_format=torch.channels_last)
+            and tuple(conv.stride) == (2, 2) and tuple(conv.padding) == (3, 3)):
+        return None
+    return _FrozenStemFn.apply(x, norm.mean, norm.std, w.detach(), bn._coefs())

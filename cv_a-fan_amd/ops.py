@@ -48,7 +48,8 @@ class _Calls(dict):
 
 
 CALLS = _Calls({"conv_fwd": 0, "conv_dgrad": 0, "conv_wgrad": 0, "conv_general": 0, "vendor_conv": 0, "conv_bn_fused": 0},
-               {"batch_crop_flip": 0, "seg_batch_aug": 0, "seg_batch_aug_jitter": 0, "seg_confusion": 0, "det_batch_resize": 0})
+               {"batch_crop_flip": 0, "seg_batch_aug": 0, "seg_batch_aug_jitter": 0, "seg_confusion": 0, "det_batch_resize": 0,
+                "frozen_stem_image_grad": 0})
 
 
 def _need(t, name, dtype=None):
@@ -1959,6 +1960,29 @@ def conv_stem7_col2im(dcols, in_hw):
         raise ValueError("conv_stem7_col2im: dcols must be the bf16 column tensor of an input of size in_hw")
     dx = torch.empty((n, 3, hi, wi), dtype=torch.bfloat16, device=dcols.device, memory_format=torch.channels_last)
     check(lib.afan_conv_stem7_col2im(_ptr(dcols), _ptr(dx), n, hi, wi, _stream(dcols)), "afan_conv_stem7_col2im")
+    return dx
+
+
+def frozen_stem_image_grad(gy, y1, w, alpha, inv_std, in_hw):
+    """The frozen stem's image gradient in one launch (afan_frozen_stem_image_grad): dx [N,3,Hi,Wi] fp32 NCHW from gy [N,64,Hp,Wp]
+    (the gradient at the max pool's output) and y1 [N,64,Ho,Wo] (the stem's post-ReLU map), both bf16 channels-last; w [64,3,7,7]
+    bf16 in KRSC memory, alpha [64] fp32 (the frozen BatchNorm's scale), inv_std [3] fp32."""
+    lib = _lib.load()
+    CALLS["frozen_stem_image_grad"] += 1
+    _cl4(gy, "gy"), _cl4(y1, "y1")
+    _need(w, "w", torch.bfloat16), _need(alpha, "alpha", torch.float32), _need(inv_std, "inv_std", torch.float32)
+    hi, wi = int(in_hw[0]), int(in_hw[1])
+    n, ho, wo = y1.shape[0], (hi - 1) // 2 + 1, (wi - 1) // 2 + 1
+    if tuple(y1.shape) != (n, 64, ho, wo) or tuple(gy.shape) != (n, 64, (ho - 1) // 2 + 1, (wo - 1) // 2 + 1) \
+            or gy.dtype != torch.bfloat16 or y1.dtype != torch.bfloat16:
+        raise ValueError("frozen_stem_image_grad: y1 / gy must be the bf16 stem and pooled maps of an image of size in_hw")
+    if tuple(w.shape) != (64, 3, 7, 7) or not w.is_contiguous(memory_format=torch.channels_last):
+        raise ValueError("stem weight must be [64, 3, 7, 7] in KRSC (channels_last) memory order")
+    if alpha.numel() != 64 or inv_std.numel() != 3:
+        raise ValueError("frozen_stem_image_grad: alpha [64] and inv_std [3]")
+    dx = torch.empty((n, 3, hi, wi), dtype=torch.float32, device=y1.device)
+    check(lib.afan_frozen_stem_image_grad(_ptr(gy), _ptr(y1), _ptr(w), _ptr(alpha), _ptr(inv_std), _ptr(dx), n, hi, wi, _stream(y1)),
+          "afan_frozen_stem_image_grad")
     return dx
 
 

@@ -487,6 +487,17 @@ int afan_conv_stem7_im2col(const void* x, void* cols, int64_t n, int64_t hi, int
  * dcols = dy x W (afan_conv_fwd_nhwc_bf16 as a 1x1 problem, 64 -> 152) it is the stem's input gradient — the image-level
  * perturbation of Detection/train_aug_sat_muti_advt.py:82-95 differentiates through conv1. */
 int afan_conv_stem7_col2im(const void* dcols, void* dx, int64_t n, int64_t hi, int64_t wi, afan_stream_t stream);
+/* The frozen stem's image gradient in one launch (afan_stem_grad.hip): from gy[N,Hp,Wp,64] (bf16 channels-last), the gradient at
+ * the 3x3 / 2 / 1 max pool's output, to dx[N,3,Hi,Wi] fp32 NCHW, the image's own form, with Ho = (Hi-1)/2+1, Hp = (Ho-1)/2+1:
+ *   g1[n,p,q,k] = alpha[k] * [y1 > 0] * sum of gy over the pool windows whose winner is (p, q)   (the max pool's winner rule below)
+ *   dx[n,c,i,j] = inv_std[c] * sum over k, r, s of g1[n,(i+3-r)/2,(j+3-s)/2,k] * w[k,r,s,c]       (divisions exact, position in range)
+ * y1[N,Ho,Wo,64] bf16 channels-last = the stem's post-ReLU map (the pool's input); w[64,7,7,3] bf16 KRSC; alpha[64] fp32 = the
+ * frozen BatchNorm's scale (row 2 of its afan_affine_coefs block, 16-byte aligned); inv_std[3] fp32 = 1 / the normaliser's std.
+ * g1 is rounded to bf16 once (fp32 window sum x alpha, RNE); products accumulate in fp32.  One workgroup per
+ * afan_frozen_stem_image_grad_tile()^2 image pixels; no workspace, no atomics.  Input gradients only: nothing reaches w or alpha. */
+int afan_frozen_stem_image_grad(const void* gy, const void* y1, const void* w, const float* alpha, const float* inv_std, float* dx,
+                                int64_t n, int64_t hi, int64_t wi, afan_stream_t stream);
+int afan_frozen_stem_image_grad_tile(void);
 int64_t afan_conv_stem7_wgrad_workspace_floats(int64_t n, int64_t hi, int64_t wi);
 int afan_conv_stem7_wgrad_nhwc_bf16(const void* x, const void* dy, float* grad, int64_t n, int64_t hi, int64_t wi,
                                     float* workspace, int accumulate, afan_stream_t stream);
