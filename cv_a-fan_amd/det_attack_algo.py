@@ -21,6 +21,7 @@ import torch
 from . import frozen, ops, pgd
 from .attack_algo import get_sample_points, linfball_proj, mix_feature, sample_points_mixed, tensor_clamp  # noqa: F401
 from .det_ops import PGD, sum_of_means  # noqa: F401  (Detection/attack_algo.py:48-74)
+from .resnet_s import _dense, _like_layout
 
 
 def compute_loss(loss1, loss2, loss3, loss4):
@@ -158,6 +159,39 @@ def eval_PGD(x, y=None, model=None, steps=3, eps=None, gamma=None, idx=1, randin
     for _ in range(steps):
         pgd.ascend(x_adv, loss_of, gamma, x, eps, clip)
     return x_adv.requires_grad_(True)
+
+
+# The layer-wise SAT evaluation's points in one launch (ops.sat_points_block) where the layout allows it; the module attribute is read at
+# call time.  Decided by the project's rule for every switch — on only where one single-setting image gains more than the two arms'
+# combined min-max spread (tools/probe/det_sat_time.py (c), profiles/det_sat_time.jsonl; README "Detection layer-wise SAT evaluation").
+# Measured: 0.015 ms against a spread of 0.39 ms on a 31 ms image, so OFF; AFAN_DET_SAT_POINTS=1 turns it on.  The evaluator's table asks
+# for the one launch itself (fused=True): there it replaces 16 launches, not three.
+SAT_POINTS_FUSED = os.environ.get("AFAN_DET_SAT_POINTS", "0") == "1"
+
+
+SAT_NUMBER = 5                                   # evaluator.py:154: get_sample_points(feature_map, feature_adv, 5)
+
+
+def sat_layer_points(feature_map, feature_adv, settings, out_dtype=torch.float32, fused=None):
+    """evaluator.py:154-159 for every (sat_layer, mix) of `settings`: `get_sample_points(feature_map, feature_adv, 5)[sat_layer]`, then
+    with mix the REVERSED `mix_feature(point, feature_map)` — the point is normalised, the clean map's per-pixel channel statistics are
+    the target — in out_dtype (the model's compute dtype: what the tail's entry would cast to).  The weight of point j is
+    j * (1.0 / 4), a Python double, as the reference computes it.  fused (None: SAT_POINTS_FUSED, read at call time): one launch for all settings where
+    the maps are channels-last or hw == 1; else, and in NCHW, the existing launches composed (ops.sat_points)."""
+    settings = [(int(j), bool(m)) for j, m in settings]
+    if any(not 0 <= j < SAT_NUMBER for j, _ in settings):
+        raise ValueError(f"sat_layer: a sample point 0..{SAT_NUMBER - 1}")
+    percent = 1.0 / (SAT_NUMBER - 1)
+    px, py = _dense(feature_map.detach().float()), _dense(feature_adv.detach().float())
+    if py.stride() != px.stride():
+        py = _like_layout(py, px)
+    return ops.sat_points(px, py, [j * percent for j, _ in settings], [m for _, m in settings], out_dtype,
+                          fused=SAT_POINTS_FUSED if fused is None else bool(fused))
+
+
+def sat_layer_point(feature_map, feature_adv, sat_layer, mix, out_dtype=torch.float32, fused=None):
+    """One setting of sat_layer_points."""
+    return sat_layer_points(feature_map, feature_adv, [(sat_layer, mix)], out_dtype, fused)[0]
 
 
 def det_train_step(model, optimizer, image_batch, bboxes_batch, labels_batch, loss_settings=1):

@@ -171,25 +171,35 @@ class Evaluator:
         """The image the eval-mode forward sees for image `index` of the list: the clean one here."""
         return image_batch
 
+    def eval_inputs(self, model, index, image_batch, bboxes_batch, labels_batch):
+        """The dict of the eval-mode forward for image `index` of the list (called with gradients as the caller left them)."""
+        image_batch = self.attack(model, index, image_batch, bboxes_batch, labels_batch)
+        return {"x": image_batch, "adv": None, "out_idx": None, "flag": 'clean', "min_prob": MIN_PROB}
+
+    @staticmethod
+    def score(model, lists, image_id, inputs_all, scale_batch):
+        """One eval-mode forward, the boxes divided by the scale, the image's one host copy; appends to lists = (ids, boxes, classes, probs)."""
+        import torch
+        all_image_ids, all_bboxes, all_classes, all_probs = lists
+        with torch.no_grad():
+            bboxes, classes, probs, batch_indices = model.eval().forward(inputs_all)
+            bboxes = bboxes / scale_batch[batch_indices.to(scale_batch.device)].unsqueeze(dim=-1).expand_as(bboxes)
+            host = torch.cat([bboxes, probs.unsqueeze(dim=-1).to(bboxes.dtype)], dim=1).cpu()       # the image's one copy
+            classes = classes.cpu()
+            keep = (host[:, 4] > MIN_PROB).nonzero().view(-1)       # evaluator.py:35 (nothing left to drop where the model took min_prob)
+            host, classes = host[keep], classes[keep]
+            all_bboxes.extend(host[:, :4].tolist())
+            all_probs.extend(host[:, 4].tolist())
+            all_classes.extend(classes.tolist())
+            all_image_ids.extend([image_id] * host.shape[0])
+
     def detect(self, model):
         """-> (image ids, boxes, classes, probs) as the lists evaluator.py:41-44 builds."""
-        import torch
-        all_image_ids, all_bboxes, all_classes, all_probs = [], [], [], []
+        lists = ([], [], [], [])
         for index, (image_id, (image_batch, bboxes_batch, labels_batch, scale_batch)) in enumerate(zip(self.image_ids, self.loader)):
-            image_batch = self.attack(model, index, image_batch, bboxes_batch, labels_batch)
-            with torch.no_grad():
-                inputs_all = {"x": image_batch, "adv": None, "out_idx": None, "flag": 'clean', "min_prob": MIN_PROB}
-                bboxes, classes, probs, batch_indices = model.eval().forward(inputs_all)
-                bboxes = bboxes / scale_batch[batch_indices.to(scale_batch.device)].unsqueeze(dim=-1).expand_as(bboxes)
-                host = torch.cat([bboxes, probs.unsqueeze(dim=-1).to(bboxes.dtype)], dim=1).cpu()       # the image's one copy
-                classes = classes.cpu()
-                keep = (host[:, 4] > MIN_PROB).nonzero().view(-1)       # evaluator.py:35 (nothing left to drop where the model took min_prob)
-                host, classes = host[keep], classes[keep]
-                all_bboxes.extend(host[:, :4].tolist())
-                all_probs.extend(host[:, 4].tolist())
-                all_classes.extend(classes.tolist())
-                all_image_ids.extend([image_id] * host.shape[0])
-        return all_image_ids, all_bboxes, all_classes, all_probs
+            inputs_all = self.eval_inputs(model, index, image_batch, bboxes_batch, labels_batch)
+            self.score(model, lists, image_id, inputs_all, scale_batch)
+        return lists
 
     def evaluate(self, model):
         return evaluate(self.ground_truth, *self.detect(model), path_to_results_dir=self.results_dir)
@@ -237,6 +247,89 @@ class RobustEvaluator(Evaluator):
         else:
             print(line, flush=True)
         return out
+
+
+SAT_TABLE = tuple((j, m) for j in range(5) for m in (False, True))      # the ten settings of eval_sat_layers.py: --sat_layer 0..4, without / with --mix
+
+
+class SatLayerEvaluator(Evaluator):
+    """evaluator.py:131-180 (`sat_layer_evaluate`): how the detections move as the backbone feature map behind layer `pertub_idx` is pushed
+    along the line from its clean value to its PGD-adversarial value.  Per image, with gradients enabled: one train-mode `flag: 'head'`
+    pass, det_ops.PGD on that feature map (steps, eps / 255, gamma / 255, randinit, clip), the sample point `sat_layer` of five
+    (det_attack_algo.sat_layer_point; with mix re-normalised by the REVERSED mix_feature(point, feature_map)) in the model's compute
+    dtype, then the eval-mode `flag: 'tail'` forward from it and Evaluator's scale division, single host copy and lists.  An image
+    without a non-difficult object has no loss: it is scored from its clean feature and counted (`self.unattacked`; one log line).
+    The model is left in eval mode.
+
+    table=True (an addition): ONE attack per image and one sat_layer_points call for all ten settings (SAT_TABLE; the one-launch form
+    wherever the layout allows it), then ten eval-mode tails one after another; detect -> {(sat_layer, mix): lists}, evaluate ->
+    {(sat_layer, mix): (mean_ap, detail)}; the results files are those of the constructor's (sat_layer, mix).  The eval tails draw
+    nothing from the host generator, so every row equals the single-setting run's lists from the same generator state."""
+
+    def __init__(self, loader, ground_truth, results_dir=None, steps=10, eps=2.0, gamma=0.5, pertub_idx=1, sat_layer=1, mix=False,
+                 randinit=False, clip=False, table=False, log=None):
+        super().__init__(loader, ground_truth, results_dir)
+        check_sat_settings(pertub_idx, sat_layer)
+        self.steps, self.eps, self.gamma, self.randinit, self.clip = int(steps), float(eps), float(gamma), bool(randinit), bool(clip)
+        self.pertub_idx, self.sat_layer, self.mix, self.table = int(pertub_idx), int(sat_layer), bool(mix), bool(table)
+        self.log, self.unattacked, self.attacked = log, 0, 0
+
+    def points(self, model, index, image_batch, bboxes_batch, labels_batch, settings, fused=None):
+        """-> one entering feature per (sat_layer, mix) of settings, from one head pass and one attack."""
+        import torch
+        from . import det_attack_algo, det_ops
+        idx = self.pertub_idx
+        with torch.enable_grad():
+            feature_map = model.train().forward({"x": image_batch, "adv": None, "out_idx": idx, "flag": 'head'}, bboxes_batch, labels_batch).detach()
+            if int(self.loader.counts[index]) == 0:      # (the host's own count: no read of the device)
+                self.unattacked += 1
+                return [feature_map] * len(settings)
+            self.attacked += 1
+            feature_adv = det_ops.PGD(feature_map, image_batch, y={'bb': bboxes_batch, 'lb': labels_batch}, model=model, steps=self.steps,
+                                      eps=(self.eps / 255), gamma=(self.gamma / 255), idx=idx, randinit=self.randinit, clip=self.clip)
+        return det_attack_algo.sat_layer_points(feature_map, feature_adv.detach(), settings, getattr(model, "compute_dtype", torch.float32), fused)
+
+    def eval_inputs(self, model, index, image_batch, bboxes_batch, labels_batch, point=None):
+        if point is None:
+            point = self.points(model, index, image_batch, bboxes_batch, labels_batch, [(self.sat_layer, self.mix)])[0]
+        return {"x": image_batch, "adv": point, "out_idx": self.pertub_idx, "flag": 'tail', "min_prob": MIN_PROB}
+
+    def _count_line(self):
+        line = 'Scored {:d} images without a non-difficult object from their clean feature (no loss to ascend)'.format(self.unattacked)
+        if self.log is not None:
+            self.log.i(line)
+        else:
+            print(line, flush=True)
+
+    def detect(self, model):
+        self.unattacked = self.attacked = 0
+        if not self.table:
+            out = super().detect(model)
+            self._count_line()
+            return out
+        rows = {s: ([], [], [], []) for s in SAT_TABLE}
+        for index, (image_id, (image_batch, bboxes_batch, labels_batch, scale_batch)) in enumerate(zip(self.image_ids, self.loader)):
+            pts = self.points(model, index, image_batch, bboxes_batch, labels_batch, SAT_TABLE, fused=True)
+            for s, point in zip(SAT_TABLE, pts):
+                self.score(model, rows[s], image_id, self.eval_inputs(model, index, image_batch, bboxes_batch, labels_batch, point), scale_batch)
+        self._count_line()
+        return rows
+
+    def evaluate(self, model):
+        if not self.table:
+            return super().evaluate(model)
+        own = (self.sat_layer, self.mix)
+        return {s: evaluate(self.ground_truth, *lists, path_to_results_dir=self.results_dir if s == own else None)
+                for s, lists in self.detect(model).items()}
+
+
+def check_sat_settings(pertub_idx, sat_layer):
+    """The two refusals of eval_sat_layers.py, before any work."""
+    if pertub_idx not in (1, 2, 3):
+        raise ValueError(f"--pertub_idx: a backbone layer 1..3, not {pertub_idx!r} (the reference's default 0 asserts in "
+                         "backbone/resnet101_ori.py:236)")
+    if sat_layer not in (0, 1, 2, 3, 4):
+        raise ValueError(f"--sat_layer: one of the five sample points 0..4, not {sat_layer!r}")
 
 
 # ------------------------------------------------------------------------------------ the driver of eval.py
@@ -366,6 +459,78 @@ def main_rob(program, argv=None):
     mean_ap, detail = evaluator.evaluate(model)
     log.i('Done')
     log.i('syd: pgd attack mean AP = {:.4f}'.format(mean_ap))
+    log.i('\n' + detail)
+    return mean_ap, detail
+
+
+SAT_ADDITIONS = ADDITIONS + ("table",)
+
+
+def get_sat_argparser(full=True):
+    """eval_sat_layers.py:40-61, flag for flag (the PGD settings, --pertub_idx / --sat_layer / --mix, then eval.py's flags); full: the
+    project's additions too (--synthetic --dtype --layout, then --table)."""
+    parser = get_full_argparser() if full else get_argparser()
+    eval_actions = parser._actions[1:]                                   # (behind -h) eval.py's flags, in their order
+    sat = argparse.ArgumentParser()
+    # PGD Setting
+    sat.add_argument('--steps', default=10, type=int, help='PGD-steps')
+    sat.add_argument('--gamma', help='index of PGD gamma', default=0.5, type=float)
+    sat.add_argument('--eps', default=2, type=float)
+    sat.add_argument('--randinit', action="store_true", help="random start inside the eps-ball")
+    sat.add_argument('--clip', action="store_true", help="project onto the eps-ball after every step")
+    sat.add_argument('--pertub_idx', help='the backbone layer (1..3) whose output is perturbed; the default 0 is refused, as the '
+                     'reference asserts on it', default=0, type=int)
+    sat.add_argument('--sat_layer', help='which of the five sample points clean .. adversarial (0..4) enters the tail', default=1, type=int)
+    sat.add_argument('--mix', action="store_true", help="re-normalise the point onto the clean map's channel statistics")
+    for a in eval_actions:
+        sat._add_action(a)
+    if full:
+        sat.add_argument('--table', action="store_true", help="all ten (sat_layer, mix) settings from one attack per image")
+    return sat
+
+
+def main_sat(program, argv=None):
+    """eval_sat_layers.py: mean AP at a sample point of the line clean feature -> PGD-adversarial feature."""
+    from . import det_data, det_entry
+    args = get_sat_argparser().parse_args(argv)
+    det_entry.print_args(args)
+    check_sat_settings(args.pertub_idx, args.sat_layer)
+    check_unbuilt(args)
+    cfg = config(args)
+    device = det_entry.setup_device(program)
+
+    path_to_checkpoint = args.checkpoint
+    path_to_results_dir = results_dir(path_to_checkpoint)
+    os.makedirs(path_to_results_dir)
+    log = det_entry.Log(os.path.join(path_to_results_dir, 'eval.log'))
+    log.i('Arguments:')
+    for k, v in vars(args).items():
+        log.i(f'\t{k} = {v}')
+    log.i(det_entry.describe(cfg))
+    print("SAT LAYER:[{}] MIX:[{}]".format(args.sat_layer, args.mix))
+
+    images, boxes, classes, ground_truth, num_classes = build_eval_split(args, cfg)
+    loader = det_data.DetDeviceLoader(images, boxes, classes, 1, device, False, cfg["image_min_side"], cfg["image_max_side"])
+    evaluator = SatLayerEvaluator(loader, ground_truth, path_to_results_dir, steps=args.steps, eps=args.eps, gamma=args.gamma,
+                                  pertub_idx=args.pertub_idx, sat_layer=args.sat_layer, mix=args.mix, randinit=args.randinit, clip=args.clip,
+                                  table=args.table, log=log)
+    log.i('Found {:d} samples'.format(len(images)))
+
+    model_cfg = dict(det_entry.DEFAULTS)
+    model_cfg.update(cfg)
+    model = det_entry.build_model(args, model_cfg, num_classes).to(device)
+    det_entry.load_checkpoint(path_to_checkpoint, model)
+
+    log.i('Start evaluating Robustness with 1 GPU (1 batch per GPU)')
+    out = evaluator.evaluate(model)
+    log.i('Done')
+    if args.table:
+        for (j, m), (ap, _) in out.items():
+            log.i('SAT LAYER:[{}] MIX:[{}] mean AP = {:.4f}'.format(j, m, ap))
+        mean_ap, detail = out[(args.sat_layer, args.mix)]
+    else:
+        mean_ap, detail = out
+    log.i('mean AP = {:.4f}'.format(mean_ap))
     log.i('\n' + detail)
     return mean_ap, detail
 

@@ -411,10 +411,13 @@ class Pooler(object):
         return nn.functional.max_pool2d(input=pool, kernel_size=2, stride=2)
 
 
-def PGD(x, image_batch, y=None, model=None, steps=3, eps=None, gamma=None, idx=1, randinit=False, clip=False):
+def PGD(x, image_batch, y=None, model=None, steps=3, eps=None, gamma=None, idx=1, randinit=False, clip=False, start=None):
     """Detection/attack_algo.py:48-74: K-step sign-gradient ascent on the backbone feature map `x` under the SUM of the four
-    detection losses (each a mean).  Returns a new fp32 leaf with requires_grad=True; `x` is not modified."""
-    x, x_adv = pgd.start(x, eps, randinit)
+    detection losses (each a mean).  Returns a new fp32 leaf with requires_grad=True; `x` is not modified.  start (an addition, as
+    eval_PGD's): the iterate to continue from instead of x (+ the random start): a run cut into pieces."""
+    x, x_adv = pgd.start(x, eps, randinit and start is None)
+    if start is not None:
+        x_adv.copy_(start)
     loss_of = lambda t: sum_of_means(*model.train().forward({"x": image_batch, "adv": t, "out_idx": idx, "flag": "tail"}, y["bb"], y["lb"]))
     for _ in range(steps):
         pgd.ascend(x_adv, loss_of, gamma, x, eps, clip)

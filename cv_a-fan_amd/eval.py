@@ -7,7 +7,7 @@ NMS for all 20 classes) is one launch (det_ops.class_nms); the batch is built on
 is det_eval's restatement of voc_eval.py on in-memory arrays, with the reference's text round trip applied to the numbers.
 
 Robust mAP is its own program, eval_rob_ori.py (the reference's working one).  Not built: eval_rob.py (the reference's dead one: it
-calls attack_algo.untarget_PGD, which is commented out), layer-wise SAT evaluation, COCO; backbones other than resnet101 (they raise,
+calls attack_algo.untarget_PGD, which is commented out), COCO; backbones other than resnet101 (they raise,
 each with its reason)."""
 import os
 import sys

@@ -8,7 +8,7 @@ Execution: det_eval.RobustEvaluator — det_attack_algo.eval_PGD on the sign-PGD
 eval.py's forward and metric.  An image without a non-difficult object has no loss; it is scored unattacked and counted in the log.
 
 Not built: eval_rob.py (the reference's other robust evaluation is dead code: it calls attack_algo.untarget_PGD, which is commented
-out), layer-wise SAT evaluation, COCO; backbones other than resnet101 (they raise, each with its reason)."""
+out), COCO; backbones other than resnet101 (they raise, each with its reason)."""
 import os
 import sys
 

@@ -23,7 +23,7 @@ class _Calls(dict):
     """The convolution counters are the dict's own items: what the logs and the tests enumerate (`dict(CALLS)`, `set(CALLS)`).
     Counters of launches outside the convolution path (`batch_crop_flip`, `seg_batch_aug`, `seg_batch_aug_jitter`, `det_batch_resize`:
     the loaders' kernels; `seg_confusion`:
-    validation's scoring kernel) live in `.other` and are read and
+    validation's scoring kernel; `sat_points`: the layer-wise SAT evaluation's one-launch points) live in `.other` and are read and
     written through the same subscript, `in` and `.get`, so that the enumerated table stays the convolution table
     (tests/test_host_logic.py::test_no_convolution_leaves_the_library pins `set(CALLS)` to the six convolution counters)."""
 
@@ -49,7 +49,7 @@ class _Calls(dict):
 
 CALLS = _Calls({"conv_fwd": 0, "conv_dgrad": 0, "conv_wgrad": 0, "conv_general": 0, "vendor_conv": 0, "conv_bn_fused": 0},
                {"batch_crop_flip": 0, "seg_batch_aug": 0, "seg_batch_aug_jitter": 0, "seg_confusion": 0, "det_batch_resize": 0,
-                "frozen_stem_image_grad": 0})
+                "frozen_stem_image_grad": 0, "sat_points": 0})
 
 
 def _need(t, name, dtype=None):
@@ -486,6 +486,72 @@ def lerp_mix(x, y, number, mix, eps=1e-5):
           "afan_lerp_mix")
     if not mix[-1]:
         out[-1] = y
+    return out
+
+
+def sat_points_block(clean, adv, weights, mix, out_dtype=torch.float32, eps=1e-5):
+    """The layer-wise SAT evaluation's points (Detection/evaluator.py:154-159) in ONE launch (afan_sat_points_nhwc): output j is the
+    point of weights[j] on the line clean -> adv (0: clean, 1: adv, else torch.lerp), re-normalised by mix_feature(point, clean) — the
+    evaluation's reversed order — where mix[j] is set, in out_dtype.  clean / adv: fp32, same shape and strides, channels-last or
+    hw == 1.  -> the [k * N, C, H, W] block in the inputs' layout (k = len(weights), 1..10); output j is rows j*N .. (j+1)*N."""
+    lib = _lib.load()
+    _need(clean, "clean", torch.float32)
+    _need(adv, "adv", torch.float32)
+    if clean.shape != adv.shape or clean.dim() != 4:
+        raise ValueError("clean/adv must be 4-d tensors of the same shape")
+    _same_layout(clean, adv)
+    k = len(weights)
+    if not 1 <= k <= 10 or len(mix) != k or out_dtype not in _DT:
+        raise ValueError("1..10 points, one mix flag per point; out_dtype fp32 or bf16")
+    n, c, hw = _nchw(clean)
+    if layout_of(clean) != AFAN_NHWC and hw != 1:
+        raise ValueError("sat_points_block: channels-last (or hw == 1) inputs; ops.sat_points composes the NCHW form")
+    w = (C.c_float * k)(*[float(v) for v in weights])
+    mask = sum(1 << j for j, f in enumerate(mix) if f)
+    N, _, H, W = clean.shape
+    strides = (H * W * c, 1, W * c, c) if layout_of(clean) == AFAN_NHWC else (c * H * W, H * W, W, 1)
+    block = torch.empty_strided((k * N, c, H, W), strides, dtype=out_dtype, device=clean.device)
+    check(lib.afan_sat_points_nhwc(_ptr(clean), _ptr(adv), _ptr(block), _DT[out_dtype], n * hw, c, w, k, mask, float(eps), _stream(clean)),
+          "afan_sat_points_nhwc")
+    CALLS["sat_points"] += 1
+    return block
+
+
+def sat_points(clean, adv, weights, mix, out_dtype=torch.float32, eps=1e-5, fused=True):
+    """-> len(weights) tensors of clean's shape and strides: sat_points_block's outputs (views of its one block) on channels-last or
+    hw == 1 inputs; on NCHW with hw > 1 (the fp32 parity mode), or with fused=False, the existing launches composed: lerp_points'
+    expression for an interior weight, mix_feature(point, clean) for a mixed point, a cast for bf16."""
+    _need(clean, "clean", torch.float32)
+    _need(adv, "adv", torch.float32)
+    if clean.shape != adv.shape or clean.dim() != 4:
+        raise ValueError("clean/adv must be 4-d tensors of the same shape")
+    _same_layout(clean, adv)
+    k = len(weights)
+    if not 1 <= k <= 10 or len(mix) != k or out_dtype not in _DT:
+        raise ValueError("1..10 points, one mix flag per point; out_dtype fp32 or bf16")
+    if any(not 0.0 <= float(v) <= 1.0 for v in weights):
+        raise ValueError("weights lie in [0, 1]")
+    n, c, hw = _nchw(clean)
+    if fused and (layout_of(clean) == AFAN_NHWC or hw == 1):
+        N = clean.shape[0]
+        block = sat_points_block(clean, adv, weights, mix, out_dtype, eps)
+        return [block[j * N:(j + 1) * N].as_strided(clean.shape, clean.stride(), j * clean.numel()) for j in range(k)]
+    lib = _lib.load()
+    inner = sorted({float(v) for v in weights if 0.0 < float(v) < 1.0})
+    points = {0.0: clean, 1.0: adv}
+    for at in range(0, len(inner), 8):           # (afan_lerp_points takes 8 weights a launch)
+        part = inner[at:at + 8]
+        flat = torch.empty(len(part) * clean.numel(), dtype=torch.float32, device=clean.device)
+        check(lib.afan_lerp_points(_ptr(clean), _ptr(adv), _ptr(flat), clean.numel(), (C.c_float * len(part))(*part), len(part), _stream(clean)),
+              "afan_lerp_points")
+        for i, v in enumerate(part):
+            points[v] = flat[i * clean.numel():(i + 1) * clean.numel()].as_strided(clean.shape, clean.stride())
+    out = []
+    for v, m in zip(weights, mix):
+        p = points[float(v)]
+        if m:
+            p = mix_feature(p, clean, eps)
+        out.append(p if out_dtype == torch.float32 else cast_bf16(p))
     return out
 
 

@@ -131,6 +131,19 @@ int afan_lerp_points(const float* x, const float* y, float* out, int64_t n, cons
 int afan_lerp_mix(const float* clean, const float* adv, float* out, int64_t n, int64_t c, int64_t hw, const float* weights,
                   int n_points, unsigned mix_mask, float eps, int layout, afan_stream_t stream);
 
+/* Layer-wise SAT evaluation points (Detection/eval_sat_layers.py -> evaluator.py:154-159): n_points (1..10) outputs from ONE read of
+ * two fp32 channels-last maps of `pixels` = N*H*W rows of c contiguous channels (an hw == 1 NCHW tensor is the same bytes).
+ * Output j = the point of weights[j] (host array, each in [0, 1]: 0 is clean's bits, 1 adv's, else torch.lerp's two forms as in
+ * afan_lerp_points); with bit j of mix_mask the stored value is mix_feature(point_j, clean, eps) — the evaluation's REVERSED order:
+ * the point is normalised, the clean map's per-pixel channel statistics are the target (unbiased variance, eps inside the root).
+ * out: n_points dense blocks of pixels*c elements of out_dtype (AFAN_F32 / AFAN_BF16 = the RNE cast of the fp32 result), each in the
+ * inputs' layout.  Bit-identical to afan_lerp_points / afan_mix_feature_nhwc run separately, whatever the grid.  Errors, decided
+ * before any GPU call: out_dtype AFAN_EDTYPE; n_points outside 1..10, a weight outside [0, 1], mask bits at or above n_points,
+ * c <= 0, pixels < 0 AFAN_ESHAPE; NULL AFAN_ENULL; alignment AFAN_EALIGN; pixels == 0 returns 0 without a launch.
+ * Algorithmic bytes: (8 + sizeof(out element) * n_points) per element. */
+int afan_sat_points_nhwc(const float* clean, const float* adv, void* out, int out_dtype, int64_t pixels, int64_t c,
+                         const float* weights, int n_points, unsigned mix_mask, float eps, afan_stream_t stream);
+
 /* Learnable feature mixing of the multi-layer A-FAN (Classification/main_learnable.py:226):
  *   out[i] = clean[i] + w * (adv[i] - clean[i])      three fp32 roundings, like the eager expression
  * clean/adv fp32 [n] (same memory layout), w = one fp32 on the DEVICE (an entry of the model's `w` parameter), out in
