@@ -11,36 +11,10 @@
 // one wave, so no separate finalize launch and no float atomics (bitwise reproducible).
 //   forward : stats partials -> [fold] normalise + affine (+ residual) (+ ReLU), running stats by s==0
 //   backward: (sum g, sum g*xhat) partials -> [fold] dx (+ d_residual), dweight/dbias by s==0
-#include "afan_common.h"
+#include "afan_bn_nhwc.h"
 
 using namespace afan;
-
-namespace afan_nhwc {  // afan_bn_nhwc.hip
-int fwd(int dtype, const void* x, const void* res, void* y, int64_t M, int64_t C, float eps, float mom, const float* w,
-        const float* b, int relu, float* ws, float* stats, const float* mean_in, const float* invstd_in, float* rm,
-        float* rv, int64_t* nbt, bool train, hipStream_t st, const float* partials, int64_t partials_g,
-        const float* partials_shift);
-int stats(int dtype, const void* x, int64_t M, int64_t C, float eps, float mom, float* ws, float* stats_out, float* rm,
-          float* rv, int64_t* nbt, hipStream_t st);
-int bwd(int dtype, const void* dy, const void* x, const void* y, void* dx, void* dres, int64_t M, int64_t C,
-        const float* stats_in, int relu, float* ws, float* dw, float* db, int acc, hipStream_t st,
-        const float* partials, int64_t partials_g);
-int64_t workspace_floats(int64_t c);
-int fwd_acc(int dtype, const void* x, const void* res, void* y, int64_t M, int64_t C, float eps, float mom,
-            const float* w, const float* b, int relu, double* acc, int acc_ready, float* stats, float* rm, float* rv,
-            int64_t* nbt, hipStream_t st, int groups);
-int bwd_acc(int dtype, const void* dy, const void* x, const void* y, void* dx, void* dres, int64_t M, int64_t C,
-            const float* stats_in, int relu, double* acc, int acc_ready, float* dw, float* db, int accumulate,
-            hipStream_t st, int groups);
-int acc_supported(int dtype, int64_t C);
-int64_t acc_doubles(int64_t C);
-int set_running_updates(int n);
-int fwd_acc_dual(int dtype, const void* xa, const void* xb, void* y, int64_t M, int64_t C, float eps_a, float mom_a,
-                 const float* w_a, const float* b_a, double* acc_a, float* stats_a, float* rm_a, float* rv_a, int64_t* nbt_a,
-                 float eps_b, float mom_b, const float* w_b, const float* b_b, double* acc_b, float* stats_b, float* rm_b,
-                 float* rv_b, int64_t* nbt_b, hipStream_t st);
-int coefs(int64_t C, const float* mean, const float* invstd, const float* w, const float* b, float* out, hipStream_t st);
-}
+using namespace afan_nhwc;   // the request records and helpers of afan_bn_nhwc.h
 
 namespace {
 
@@ -340,6 +314,8 @@ __global__ __launch_bounds__(BLOCK) void normalize_kernel(const float* __restric
 }
 
 // ---- host side ------------------------------------------------------------------------------------
+// The NCHW launch code reads the request records of afan_bn_nhwc.h: sources Slab (train) and Given (eval) forward, Slab backward;
+// bn.stats is [2][C] = mean | invstd here.
 struct Plan {
     Geo g;
     int vec;  // elements per access
@@ -374,115 +350,135 @@ bool make_plan(int64_t n, int64_t c, int64_t hw, std::initializer_list<const voi
 }
 
 template <typename T>
-int bn_stats_impl(const void* x, int64_t n, int64_t c, int64_t hw, float eps, float momentum, float* ws,
-                  float* mean, float* invstd, float* rmean, float* rvar, int64_t* nbt, hipStream_t st) {
+void launch_stats(const Plan& p, const BnFwd& r) {
+    AFAN_PROF("bn_stats_kernel", p.tensor_bytes, r.st);
+    if (p.vec == 1) bn_stats_kernel<T, 1><<<p.grid, BLOCK, 0, r.st>>>((const T*)r.x, p.g, r.ws);
+    else bn_stats_kernel<T, Elt<T>::VEC><<<p.grid, BLOCK, 0, r.st>>>((const T*)r.x, p.g, r.ws);
+}
+
+template <typename T>
+int bn_stats_impl(const BnFwd& r) {
+    const BnOperands& b = r.bn;
     Plan p;
-    if (!make_plan<T>(n, c, hw, {x}, p)) return AFAN_ESHAPE;
-    {
-        AFAN_PROF("bn_stats_kernel", p.tensor_bytes, st);
-        if (p.vec == 1)
-            bn_stats_kernel<T, 1><<<p.grid, BLOCK, 0, st>>>((const T*)x, p.g, ws);
-        else
-            bn_stats_kernel<T, Elt<T>::VEC><<<p.grid, BLOCK, 0, st>>>((const T*)x, p.g, ws);
-    }
+    if (!make_plan<T>(r.n, r.c, r.hw, {r.x}, p)) return AFAN_ESHAPE;
+    launch_stats<T>(p, r);
     AFAN_LAUNCH_CHECK();
-    AFAN_PROF("bn_finalize_kernel", 16.0 * c * p.grid.x, st);
-    bn_finalize_kernel<<<(unsigned)c, AFAN_WAVE, 0, st>>>(ws, (int)p.grid.x, eps, momentum, mean, invstd,
-                                                          rmean, rvar, nbt);
+    AFAN_PROF("bn_finalize_kernel", 16.0 * r.c * p.grid.x, r.st);
+    bn_finalize_kernel<<<(unsigned)r.c, AFAN_WAVE, 0, r.st>>>(r.ws, (int)p.grid.x, b.eps, b.momentum, b.stats, b.stats + r.c,
+                                                              b.rmean, b.rvar, b.nbt);
     AFAN_LAUNCH_CHECK();
     return AFAN_OK;
 }
 
 template <typename T, int VEC, bool TRAIN>
-void launch_apply(const Plan& p, const void* x, const void* res, void* y, const float* ws, float eps,
-                  float momentum, const float* weight, const float* bias, float* mean, float* invstd,
-                  float* rmean, float* rvar, int64_t* nbt, int relu, hipStream_t st) {
-    AFAN_PROF("bn_apply_kernel", p.tensor_bytes * (res ? 3 : 2), st);
-#define AFAN_GO(RES, RELU)                                                                          \
-    bn_apply_kernel<T, VEC, RES, RELU, TRAIN><<<p.grid, BLOCK, 0, st>>>(                            \
-        (const T*)x, (const T*)res, (T*)y, p.g, ws, eps, momentum, weight, bias, mean, invstd, rmean, \
-        rvar, nbt)
-    if (res) {
-        if (relu) AFAN_GO(true, true); else AFAN_GO(true, false);
-    } else {
-        if (relu) AFAN_GO(false, true); else AFAN_GO(false, false);
-    }
-#undef AFAN_GO
+void launch_apply(const Plan& p, const BnFwd& r) {
+    const BnOperands& b = r.bn;
+    float* mean = TRAIN ? b.stats : const_cast<float*>(r.mean_in);
+    float* invstd = TRAIN ? b.stats + r.c : const_cast<float*>(r.invstd_in);
+    AFAN_PROF("bn_apply_kernel", p.tensor_bytes * (r.res ? 3 : 2), r.st);
+    with_flag(r.res, [&](auto RES) { with_flag(r.relu, [&](auto RELU) {
+        bn_apply_kernel<T, VEC, RES(), RELU(), TRAIN><<<p.grid, BLOCK, 0, r.st>>>(
+            (const T*)r.x, (const T*)r.res, (T*)r.y, p.g, r.ws, b.eps, b.momentum, b.weight, b.bias, mean, invstd, b.rmean,
+            b.rvar, b.nbt);
+    }); });
     ++afan::prof::g_launches;       // (the caller checks the launch; the profiling scope above counts it here)
 }
 
 template <typename T>
-int bn_forward_impl(const void* x, const void* res, void* y, int64_t n, int64_t c, int64_t hw, float eps,
-                    float momentum, const float* weight, const float* bias, int relu, float* ws,
-                    float* mean, float* invstd, float* rmean, float* rvar, int64_t* nbt, bool train,
-                    hipStream_t st) {
+int bn_forward_impl(const BnFwd& r) {
     Plan p;
-    if (!make_plan<T>(n, c, hw, {x, res, y}, p)) return AFAN_ESHAPE;
+    if (!make_plan<T>(r.n, r.c, r.hw, {r.x, r.res, r.y}, p)) return AFAN_ESHAPE;
     constexpr int NV = Elt<T>::VEC;
-    if (train) {
-        {
-            AFAN_PROF("bn_stats_kernel", p.tensor_bytes, st);
-            if (p.vec == 1) bn_stats_kernel<T, 1><<<p.grid, BLOCK, 0, st>>>((const T*)x, p.g, ws);
-            else bn_stats_kernel<T, NV><<<p.grid, BLOCK, 0, st>>>((const T*)x, p.g, ws);
-        }
+    if (r.src == BnSource::Slab) {
+        launch_stats<T>(p, r);
         AFAN_LAUNCH_CHECK();
-        if (p.vec == 1) launch_apply<T, 1, true>(p, x, res, y, ws, eps, momentum, weight, bias, mean, invstd, rmean, rvar, nbt, relu, st);
-        else launch_apply<T, NV, true>(p, x, res, y, ws, eps, momentum, weight, bias, mean, invstd, rmean, rvar, nbt, relu, st);
+        if (p.vec == 1) launch_apply<T, 1, true>(p, r);
+        else launch_apply<T, NV, true>(p, r);
     } else {
-        if (p.vec == 1) launch_apply<T, 1, false>(p, x, res, y, ws, eps, momentum, weight, bias, mean, invstd, rmean, rvar, nbt, relu, st);
-        else launch_apply<T, NV, false>(p, x, res, y, ws, eps, momentum, weight, bias, mean, invstd, rmean, rvar, nbt, relu, st);
+        if (p.vec == 1) launch_apply<T, 1, false>(p, r);
+        else launch_apply<T, NV, false>(p, r);
     }
     AFAN_LAUNCH_CHECK();
     return AFAN_OK;
 }
 
 template <typename T, int VEC>
-int bn_backward_vec(const Plan& p, const void* dy, const void* x, const void* y, void* dx, void* dres,
-                    const float* mean, const float* invstd, const float* weight, const float* bias,
-                    int relu, float* ws, float inv_m, float* dweight, float* dbias, int accumulate,
-                    hipStream_t st) {
-    const T* dy_ = (const T*)dy; const T* x_ = (const T*)x; const T* y_ = (const T*)y;
-#define AFAN_RED(RELU, HY) \
-    bn_bwd_reduce_kernel<T, VEC, RELU, HY><<<p.grid, BLOCK, 0, st>>>(dy_, x_, y_, p.g, mean, invstd, weight, bias, ws)
+int bn_backward_vec(const Plan& p, const BnBwd& r) {
+    const T* dy_ = (const T*)r.dy; const T* x_ = (const T*)r.x; const T* y_ = (const T*)r.y;
+    const float *mean = r.stats, *invstd = r.stats + r.c;
+    const float inv_m = 1.0f / (float)((double)r.n * (double)r.hw);
+    const int mask_read = (r.relu && r.y) ? 1 : 0;   // the forward's output is read as the ReLU mask
+    hipStream_t st = r.st;
     {
-        AFAN_PROF("bn_bwd_reduce_kernel", p.tensor_bytes * ((relu && y) ? 3 : 2), st);
-        if (!relu) AFAN_RED(false, false);
-        else if (y) AFAN_RED(true, true);
-        else AFAN_RED(true, false);
+        AFAN_PROF("bn_bwd_reduce_kernel", p.tensor_bytes * (2 + mask_read), st);
+        with_mask(r.relu, r.y, [&](auto RELU, auto HY) {
+            bn_bwd_reduce_kernel<T, VEC, RELU(), HY()><<<p.grid, BLOCK, 0, st>>>(dy_, x_, y_, p.g, mean, invstd, r.weight, r.bias, r.ws);
+        });
     }
-#undef AFAN_RED
     AFAN_LAUNCH_CHECK();
-#define AFAN_APP(RELU, HY, DR)                                                                         \
-    bn_bwd_apply_kernel<T, VEC, RELU, HY, DR><<<p.grid, BLOCK, 0, st>>>(dy_, x_, y_, (T*)dx, (T*)dres, p.g, \
-        mean, invstd, weight, bias, ws, inv_m, dweight, dbias, accumulate)
-    AFAN_PROF("bn_bwd_apply_kernel", p.tensor_bytes * (3 + ((relu && y) ? 1 : 0) + (dres ? 1 : 0)), st);
-    if (!relu) { if (dres) AFAN_APP(false, false, true); else AFAN_APP(false, false, false); }
-    else if (y) { if (dres) AFAN_APP(true, true, true); else AFAN_APP(true, true, false); }
-    else { if (dres) AFAN_APP(true, false, true); else AFAN_APP(true, false, false); }
-#undef AFAN_APP
+    AFAN_PROF("bn_bwd_apply_kernel", p.tensor_bytes * (3 + mask_read + (r.dres ? 1 : 0)), st);
+    with_mask(r.relu, r.y, [&](auto RELU, auto HY) { with_flag(r.dres, [&](auto DR) {
+        bn_bwd_apply_kernel<T, VEC, RELU(), HY(), DR()><<<p.grid, BLOCK, 0, st>>>(dy_, x_, y_, (T*)r.dx, (T*)r.dres, p.g, mean, invstd,
+            r.weight, r.bias, r.ws, inv_m, r.dweight, r.dbias, r.accumulate);
+    }); });
     AFAN_LAUNCH_CHECK();
     return AFAN_OK;
 }
 
 template <typename T>
-int bn_backward_impl(const void* dy, const void* x, const void* y, void* dx, void* dres, int64_t n,
-                     int64_t c, int64_t hw, const float* mean, const float* invstd, const float* weight,
-                     const float* bias, int relu, float* ws, float* dweight, float* dbias, int accumulate,
-                     hipStream_t st) {
+int bn_backward_impl(const BnBwd& r) {
     Plan p;
-    if (!make_plan<T>(n, c, hw, {dy, x, y, dx, dres}, p)) return AFAN_ESHAPE;
-    const float inv_m = 1.0f / (float)((double)n * (double)hw);
-    if (p.vec == 1)
-        return bn_backward_vec<T, 1>(p, dy, x, y, dx, dres, mean, invstd, weight, bias, relu, ws, inv_m, dweight, dbias, accumulate, st);
-    return bn_backward_vec<T, Elt<T>::VEC>(p, dy, x, y, dx, dres, mean, invstd, weight, bias, relu, ws, inv_m, dweight, dbias, accumulate, st);
+    if (!make_plan<T>(r.n, r.c, r.hw, {r.dy, r.x, r.y, r.dx, r.dres}, p)) return AFAN_ESHAPE;
+    if (p.vec == 1) return bn_backward_vec<T, 1>(p, r);
+    return bn_backward_vec<T, Elt<T>::VEC>(p, r);
 }
 
-int check_layout(int layout) { return (layout == AFAN_NCHW || layout == AFAN_NHWC) ? AFAN_OK : AFAN_ELAYOUT; }
+// the statistics alone, in either layout (defined in front of run_fwd: the code object's kernels follow the order of instantiation)
+int run_stats(const BnFwd& r, int layout) {
+    if (layout == AFAN_NHWC) return afan_nhwc::stats(r);
+    return with_dtype(r.dtype, [&](auto t) { return bn_stats_impl<decltype(t)>(r); });
+}
+// a forward in either layout (the NCHW kernels apply one running-statistics update per pass: a pending repeat count is refused loudly)
+int run_fwd(const BnFwd& r, int layout) {
+    if (layout == AFAN_NHWC) return afan_nhwc::fwd(r);
+    if (r.src == BnSource::Slab && r.updates != 1) return AFAN_ESHAPE;
+    return with_dtype(r.dtype, [&](auto t) { return bn_forward_impl<decltype(t)>(r); });
+}
 
-int check_common(int dtype, int64_t n, int64_t c, int64_t hw) {
+// ---- the exports' argument checks, in the order every export applies them ----------------------------------------
+// dtype, shape, layout (exports without a layout argument pass AFAN_NHWC), then the operands that must be there
+int check_request(int dtype, int layout, int64_t n, int64_t c, int64_t hw, std::initializer_list<const void*> required) {
     if (dtype != AFAN_F32 && dtype != AFAN_BF16) return AFAN_EDTYPE;
     if (n <= 0 || c <= 0 || hw <= 0) return AFAN_ESHAPE;
+    if (layout != AFAN_NCHW && layout != AFAN_NHWC) return AFAN_ELAYOUT;
+    for (const void* q : required)
+        if (!q) return AFAN_ENULL;
     return AFAN_OK;
+}
+bool paired(const BnOperands& b) { return (b.rmean == nullptr) == (b.rvar == nullptr); }   // running mean and variance: both or neither
+// a filled request: check_request; the convolution's partials (channels-last only, a positive count); the running statistics;
+// with accumulator blocks (`accs`) the channel mapping; every tensor that is there on an element boundary and every block on
+// 16 bytes; the image groups
+int check(const afan_nhwc::BnReq& r, int layout, std::initializer_list<const void*> required,
+          std::initializer_list<const void*> tensors, bool running_ok = true, std::initializer_list<const void*> accs = {}) {
+    if (const int e = check_request(r.dtype, layout, r.n, r.c, r.hw, required)) return e;
+    if (r.src == BnSource::ConvPartials && (layout != AFAN_NHWC || r.partials_g <= 0)) return AFAN_ESHAPE;
+    if (!running_ok) return AFAN_ENULL;
+    if (accs.size() && !afan_nhwc::acc_supported(r.dtype, r.c)) return AFAN_ESHAPE;
+    for (const void* q : tensors)
+        if (q && !aligned(q, r.dtype == AFAN_F32 ? 4 : 2)) return AFAN_EALIGN;
+    for (const void* q : accs)
+        if (!aligned(q, 16)) return AFAN_EALIGN;
+    return (r.groups < 1 || r.n % r.groups != 0) ? AFAN_ESHAPE : AFAN_OK;
+}
+
+// what every request starts from
+template <typename R>
+R request(int dtype, int64_t n, int64_t c, int64_t hw, int relu, afan_stream_t stream) {
+    R r;
+    r.dtype = dtype; r.n = n; r.c = c; r.hw = hw; r.relu = relu;
+    r.st = (hipStream_t)stream;
+    return r;
 }
 
 // One more running-statistics update of a train-mode BatchNorm from the moments of an EARLIER forward pass (its saved
@@ -531,43 +527,24 @@ int64_t afan_bn_workspace_floats(int64_t c) {
 int afan_bn_stats(const void* x, int dtype, int layout, int64_t n, int64_t c, int64_t hw, float eps, float momentum,
                   float* workspace, float* stats, float* running_mean, float* running_var, int64_t* num_batches,
                   afan_stream_t stream) {
-    int e = check_common(dtype, n, c, hw);
-    if (e) return e;
-    if ((e = check_layout(layout))) return e;
-    if (!x || !workspace || !stats) return AFAN_ENULL;
-    if ((running_mean == nullptr) != (running_var == nullptr)) return AFAN_ENULL;
-    if (!aligned(x, dtype == AFAN_F32 ? 4 : 2)) return AFAN_EALIGN;
-    hipStream_t st = (hipStream_t)stream;
-    if (layout == AFAN_NHWC)
-        return afan_nhwc::stats(dtype, x, n * hw, c, eps, momentum, workspace, stats, running_mean, running_var, num_batches, st);
-    if (dtype == AFAN_F32)
-        return bn_stats_impl<float>(x, n, c, hw, eps, momentum, workspace, stats, stats + c, running_mean, running_var, num_batches, st);
-    return bn_stats_impl<uint16_t>(x, n, c, hw, eps, momentum, workspace, stats, stats + c, running_mean, running_var, num_batches, st);
+    BnFwd r = request<BnFwd>(dtype, n, c, hw, /*relu*/ 0, stream);
+    r.x = x; r.ws = workspace; r.updates = running_updates();
+    r.bn.eps = eps; r.bn.momentum = momentum;
+    r.bn.stats = stats; r.bn.rmean = running_mean; r.bn.rvar = running_var; r.bn.nbt = num_batches;
+    const int e = check(r, layout, {x, workspace, stats}, {x}, paired(r.bn));
+    return e ? e : run_stats(r, layout);
 }
 
 int afan_bn_train_forward(const void* x, const void* residual, void* y, int dtype, int layout, int64_t n, int64_t c,
                           int64_t hw, float eps, float momentum, const float* weight, const float* bias, int relu,
                           float* workspace, float* save_stats, float* running_mean, float* running_var,
                           int64_t* num_batches, afan_stream_t stream) {
-    int e = check_common(dtype, n, c, hw);
-    if (e) return e;
-    if ((e = check_layout(layout))) return e;
-    if (!x || !y || !workspace || !save_stats) return AFAN_ENULL;
-    if ((running_mean == nullptr) != (running_var == nullptr)) return AFAN_ENULL;
-    const size_t a = dtype == AFAN_F32 ? 4 : 2;
-    if (!aligned(x, a) || !aligned(y, a) || (residual && !aligned(residual, a))) return AFAN_EALIGN;
-    hipStream_t st = (hipStream_t)stream;
-    if (layout == AFAN_NHWC)
-        return afan_nhwc::fwd(dtype, x, residual, y, n * hw, c, eps, momentum, weight, bias, relu, workspace, save_stats,
-                              nullptr, nullptr, running_mean, running_var, num_batches, true, st, nullptr, 0, nullptr);
-    {   // the NCHW kernels apply one running-statistics update per pass: refuse a pending repeat count loudly
-        const int pending = afan_nhwc::set_running_updates(1);
-        afan_nhwc::set_running_updates(pending);
-        if (pending != 1) return AFAN_ESHAPE;
-    }
-    if (dtype == AFAN_F32)
-        return bn_forward_impl<float>(x, residual, y, n, c, hw, eps, momentum, weight, bias, relu, workspace, save_stats, save_stats + c, running_mean, running_var, num_batches, true, st);
-    return bn_forward_impl<uint16_t>(x, residual, y, n, c, hw, eps, momentum, weight, bias, relu, workspace, save_stats, save_stats + c, running_mean, running_var, num_batches, true, st);
+    BnFwd r = request<BnFwd>(dtype, n, c, hw, relu, stream);
+    r.x = x; r.res = residual; r.y = y; r.ws = workspace; r.updates = running_updates();
+    r.bn.weight = weight; r.bn.bias = bias; r.bn.eps = eps; r.bn.momentum = momentum;
+    r.bn.stats = save_stats; r.bn.rmean = running_mean; r.bn.rvar = running_var; r.bn.nbt = num_batches;
+    const int e = check(r, layout, {x, y, workspace, save_stats}, {x, y, residual}, paired(r.bn));
+    return e ? e : run_fwd(r, layout);
 }
 
 int afan_bn_train_forward_partials(const void* x, const void* residual, void* y, int dtype, int64_t n, int64_t c,
@@ -575,39 +552,31 @@ int afan_bn_train_forward_partials(const void* x, const void* residual, void* y,
                                    int relu, const float* partials, int64_t partials_g, const float* partials_shift,
                                    float* save_stats, float* running_mean, float* running_var, int64_t* num_batches,
                                    afan_stream_t stream) {
-    int e = check_common(dtype, n, c, hw);
-    if (e) return e;
-    if (!x || !y || !partials || !save_stats) return AFAN_ENULL;
-    if (partials_g <= 0) return AFAN_ESHAPE;
-    if ((running_mean == nullptr) != (running_var == nullptr)) return AFAN_ENULL;
-    const size_t a = dtype == AFAN_F32 ? 4 : 2;
-    if (!aligned(x, a) || !aligned(y, a) || (residual && !aligned(residual, a))) return AFAN_EALIGN;
-    return afan_nhwc::fwd(dtype, x, residual, y, n * hw, c, eps, momentum, weight, bias, relu, nullptr, save_stats, nullptr,
-                          nullptr, running_mean, running_var, num_batches, true, (hipStream_t)stream, partials,
-                          partials_g, partials_shift);
+    BnFwd r = request<BnFwd>(dtype, n, c, hw, relu, stream);
+    r.x = x; r.res = residual; r.y = y; r.updates = running_updates();
+    r.src = BnSource::ConvPartials;
+    r.partials = partials; r.partials_g = partials_g; r.partials_shift = partials_shift;
+    r.bn.weight = weight; r.bn.bias = bias; r.bn.eps = eps; r.bn.momentum = momentum;
+    r.bn.stats = save_stats; r.bn.rmean = running_mean; r.bn.rvar = running_var; r.bn.nbt = num_batches;
+    const int e = check(r, AFAN_NHWC, {x, y, partials, save_stats}, {x, y, residual}, paired(r.bn));
+    return e ? e : afan_nhwc::fwd(r);
 }
 
 int afan_bn_apply(const void* x, const void* residual, void* y, int dtype, int layout, int64_t n, int64_t c, int64_t hw,
                   const float* mean, const float* invstd, const float* weight, const float* bias, int relu,
                   float* workspace, afan_stream_t stream) {
-    int e = check_common(dtype, n, c, hw);
-    if (e) return e;
-    if ((e = check_layout(layout))) return e;
-    if (!x || !y || !mean || !invstd) return AFAN_ENULL;
-    const size_t a = dtype == AFAN_F32 ? 4 : 2;
-    if (!aligned(x, a) || !aligned(y, a) || (residual && !aligned(residual, a))) return AFAN_EALIGN;
-    hipStream_t st = (hipStream_t)stream;
-    float* m = const_cast<float*>(mean);
-    float* is = const_cast<float*>(invstd);
-    if (layout == AFAN_NHWC) {
+    BnFwd r = request<BnFwd>(dtype, n, c, hw, relu, stream);
+    r.x = x; r.res = residual; r.y = y;
+    r.src = BnSource::Given;
+    r.mean_in = mean; r.invstd_in = invstd;
+    r.bn.weight = weight; r.bn.bias = bias;
+    if (const int e = check(r, layout, {x, y, mean, invstd}, {x, y, residual})) return e;
+    if (layout == AFAN_NHWC) {   // the coefficient block is built in the tail of the workspace
         if (!workspace) return AFAN_ENULL;
-        float* stats = workspace + afan_nhwc::workspace_floats(c) - 4 * c;   // tail of the workspace
-        return afan_nhwc::fwd(dtype, x, residual, y, n * hw, c, 0.f, 0.f, weight, bias, relu, workspace, stats, mean, invstd,
-                              nullptr, nullptr, nullptr, false, st, nullptr, 0, nullptr);
+        r.ws = workspace;
+        r.bn.stats = workspace + afan_nhwc::workspace_floats(c) - 4 * c;
     }
-    if (dtype == AFAN_F32)
-        return bn_forward_impl<float>(x, residual, y, n, c, hw, 0.f, 0.f, weight, bias, relu, nullptr, m, is, nullptr, nullptr, nullptr, false, st);
-    return bn_forward_impl<uint16_t>(x, residual, y, n, c, hw, 0.f, 0.f, weight, bias, relu, nullptr, m, is, nullptr, nullptr, nullptr, false, st);
+    return run_fwd(r, layout);
 }
 
 int afan_affine_coefs(const float* mean, const float* invstd, const float* weight, const float* bias, int64_t c,
@@ -620,37 +589,27 @@ int afan_affine_coefs(const float* mean, const float* invstd, const float* weigh
 
 int afan_affine_apply(const void* x, const void* residual, void* y, int dtype, int64_t n, int64_t c, int64_t hw,
                       const float* coefs, int relu, afan_stream_t stream) {
-    int e = check_common(dtype, n, c, hw);
-    if (e) return e;
-    if (!x || !y || !coefs) return AFAN_ENULL;
-    const size_t a = dtype == AFAN_F32 ? 4 : 2;
-    if (!aligned(x, a) || !aligned(y, a) || (residual && !aligned(residual, a))) return AFAN_EALIGN;
-    return afan_nhwc::fwd(dtype, x, residual, y, n * hw, c, 0.f, 0.f, nullptr, nullptr, relu, nullptr, const_cast<float*>(coefs),
-                          nullptr, nullptr, nullptr, nullptr, nullptr, false, (hipStream_t)stream, nullptr, 0, nullptr);
+    BnFwd r = request<BnFwd>(dtype, n, c, hw, relu, stream);
+    r.x = x; r.res = residual; r.y = y;
+    r.src = BnSource::Coefs;
+    r.bn.stats = const_cast<float*>(coefs);
+    const int e = check(r, AFAN_NHWC, {x, y, coefs}, {x, y, residual});
+    return e ? e : afan_nhwc::fwd(r);
 }
 
 int afan_bn_backward(const void* dy, const void* x, const void* y, void* dx, void* d_residual, int dtype, int layout,
                      int64_t n, int64_t c, int64_t hw, const float* save_stats, const float* weight, const float* bias,
                      int relu, float* workspace, float* dweight, float* dbias, int accumulate, const float* partials,
                      int64_t partials_g, afan_stream_t stream) {
-    int e = check_common(dtype, n, c, hw);
-    if (e) return e;
-    if ((e = check_layout(layout))) return e;
-    if (!dy || !x || !dx || !save_stats || !workspace) return AFAN_ENULL;
-    if (partials && (layout != AFAN_NHWC || partials_g <= 0)) return AFAN_ESHAPE;
-    const size_t a = dtype == AFAN_F32 ? 4 : 2;
-    if (!aligned(dy, a) || !aligned(x, a) || !aligned(dx, a) || (y && !aligned(y, a)) ||
-        (d_residual && !aligned(d_residual, a)))
-        return AFAN_EALIGN;
-    hipStream_t st = (hipStream_t)stream;
-    if (layout == AFAN_NHWC)
-        return afan_nhwc::bwd(dtype, dy, x, y, dx, d_residual, n * hw, c, save_stats, relu, workspace, dweight, dbias, accumulate, st,
-                              partials, partials_g);
-    const float* mean = save_stats;
-    const float* invstd = save_stats + c;
-    if (dtype == AFAN_F32)
-        return bn_backward_impl<float>(dy, x, y, dx, d_residual, n, c, hw, mean, invstd, weight, bias, relu, workspace, dweight, dbias, accumulate, st);
-    return bn_backward_impl<uint16_t>(dy, x, y, dx, d_residual, n, c, hw, mean, invstd, weight, bias, relu, workspace, dweight, dbias, accumulate, st);
+    BnBwd r = request<BnBwd>(dtype, n, c, hw, relu, stream);
+    r.dy = dy; r.x = x; r.y = y; r.dx = dx; r.dres = d_residual;
+    r.stats = save_stats; r.weight = weight; r.bias = bias; r.ws = workspace;
+    r.dweight = dweight; r.dbias = dbias; r.accumulate = accumulate;
+    if (partials) r.src = BnSource::ConvPartials;
+    r.partials = partials; r.partials_g = partials_g;
+    if (const int e = check(r, layout, {dy, x, dx, save_stats, workspace}, {dy, x, dx, y, d_residual})) return e;
+    if (layout == AFAN_NHWC) return afan_nhwc::bwd(r);
+    return with_dtype(dtype, [&](auto t) { return bn_backward_impl<decltype(t)>(r); });
 }
 
 int64_t afan_bn_acc_doubles(int64_t c) { return afan_nhwc::acc_doubles(c); }
@@ -699,16 +658,14 @@ int afan_bn_train_forward_acc(const void* x, const void* residual, void* y, int 
                               int64_t hw, float eps, float momentum, const float* weight, const float* bias, int relu,
                               double* acc, int acc_ready, float* save_stats, float* running_mean, float* running_var,
                               int64_t* num_batches, int groups, afan_stream_t stream) {
-    int e = check_common(dtype, n, c, hw);
-    if (e) return e;
-    if (!x || !y || !acc || !save_stats) return AFAN_ENULL;
-    if ((running_mean == nullptr) != (running_var == nullptr)) return AFAN_ENULL;
-    if (!afan_nhwc::acc_supported(dtype, c)) return AFAN_ESHAPE;
-    const size_t a = dtype == AFAN_F32 ? 4 : 2;
-    if (!aligned(x, a) || !aligned(y, a) || (residual && !aligned(residual, a)) || !aligned(acc, 16)) return AFAN_EALIGN;
-    if (groups < 1 || n % groups != 0) return AFAN_ESHAPE;
-    return afan_nhwc::fwd_acc(dtype, x, residual, y, (n / groups) * hw, c, eps, momentum, weight, bias, relu, acc, acc_ready,
-                              save_stats, running_mean, running_var, num_batches, (hipStream_t)stream, groups);
+    BnFwd r = request<BnFwd>(dtype, n, c, hw, relu, stream);
+    r.x = x; r.res = residual; r.y = y; r.updates = running_updates();
+    r.src = acc_ready ? BnSource::AccReady : BnSource::AccFill;
+    r.groups = groups;
+    r.bn.weight = weight; r.bn.bias = bias; r.bn.eps = eps; r.bn.momentum = momentum; r.bn.acc = acc;
+    r.bn.stats = save_stats; r.bn.rmean = running_mean; r.bn.rvar = running_var; r.bn.nbt = num_batches;
+    const int e = check(r, AFAN_NHWC, {x, y, acc, save_stats}, {x, y, residual}, paired(r.bn), {acc});
+    return e ? e : afan_nhwc::fwd_acc(r);
 }
 
 int afan_bn_train_forward_acc_dual(const void* x_a, const void* x_b, void* y, int dtype, int64_t n, int64_t c, int64_t hw,
@@ -717,42 +674,38 @@ int afan_bn_train_forward_acc_dual(const void* x_a, const void* x_b, void* y, in
                                    float eps_b, float momentum_b, const float* weight_b, const float* bias_b, double* acc_b,
                                    float* save_stats_b, float* running_mean_b, float* running_var_b, int64_t* num_batches_b,
                                    afan_stream_t stream) {
-    int e = check_common(dtype, n, c, hw);
-    if (e) return e;
-    if (!x_a || !x_b || !y || !acc_a || !acc_b || !save_stats_a || !save_stats_b) return AFAN_ENULL;
-    if ((running_mean_a == nullptr) != (running_var_a == nullptr) || (running_mean_b == nullptr) != (running_var_b == nullptr))
-        return AFAN_ENULL;
-    if (!afan_nhwc::acc_supported(dtype, c)) return AFAN_ESHAPE;
-    const size_t a = dtype == AFAN_F32 ? 4 : 2;
-    if (!aligned(x_a, a) || !aligned(x_b, a) || !aligned(y, a) || !aligned(acc_a, 16) || !aligned(acc_b, 16)) return AFAN_EALIGN;
-    return afan_nhwc::fwd_acc_dual(dtype, x_a, x_b, y, n * hw, c, eps_a, momentum_a, weight_a, bias_a, acc_a, save_stats_a,
-                                   running_mean_a, running_var_a, num_batches_a, eps_b, momentum_b, weight_b, bias_b, acc_b,
-                                   save_stats_b, running_mean_b, running_var_b, num_batches_b, (hipStream_t)stream);
+    BnFwd r = request<BnFwd>(dtype, n, c, hw, /*relu*/ 1, stream);
+    r.x = x_a; r.res = x_b; r.y = y; r.updates = running_updates();
+    r.src = BnSource::AccReady;
+    BnOperands &a = r.bn, &b = r.bn_b;
+    a.weight = weight_a; a.bias = bias_a; a.eps = eps_a; a.momentum = momentum_a; a.acc = acc_a;
+    a.stats = save_stats_a; a.rmean = running_mean_a; a.rvar = running_var_a; a.nbt = num_batches_a;
+    b.weight = weight_b; b.bias = bias_b; b.eps = eps_b; b.momentum = momentum_b; b.acc = acc_b;
+    b.stats = save_stats_b; b.rmean = running_mean_b; b.rvar = running_var_b; b.nbt = num_batches_b;
+    const int e = check(r, AFAN_NHWC, {x_a, x_b, y, acc_a, acc_b, save_stats_a, save_stats_b}, {x_a, x_b, y}, paired(a) && paired(b),
+                        {acc_a, acc_b});
+    return e ? e : afan_nhwc::fwd_dual(r);
 }
 
 int afan_bn_backward_acc(const void* dy, const void* x, const void* y, void* dx, void* d_residual, int dtype,
                          int64_t n, int64_t c, int64_t hw, const float* save_stats, int relu, double* acc,
                          int acc_ready, float* dweight, float* dbias, int accumulate, int groups,
                          afan_stream_t stream) {
-    int e = check_common(dtype, n, c, hw);
-    if (e) return e;
-    if (!dy || !x || !dx || !save_stats || !acc) return AFAN_ENULL;
-    if (!afan_nhwc::acc_supported(dtype, c)) return AFAN_ESHAPE;
-    const size_t a = dtype == AFAN_F32 ? 4 : 2;
-    if (!aligned(dy, a) || !aligned(x, a) || !aligned(dx, a) || (y && !aligned(y, a)) ||
-        (d_residual && !aligned(d_residual, a)) || !aligned(acc, 16))
-        return AFAN_EALIGN;
-    if (groups < 1 || n % groups != 0) return AFAN_ESHAPE;
-    return afan_nhwc::bwd_acc(dtype, dy, x, y, dx, d_residual, (n / groups) * hw, c, save_stats, relu, acc, acc_ready, dweight,
-                              dbias, accumulate, (hipStream_t)stream, groups);
+    BnBwd r = request<BnBwd>(dtype, n, c, hw, relu, stream);
+    r.dy = dy; r.x = x; r.y = y; r.dx = dx; r.dres = d_residual;
+    r.stats = save_stats; r.acc = acc;
+    r.src = acc_ready ? BnSource::AccReady : BnSource::AccFill;
+    r.groups = groups;
+    r.dweight = dweight; r.dbias = dbias; r.accumulate = accumulate;
+    const int e = check(r, AFAN_NHWC, {dy, x, dx, save_stats, acc}, {dy, x, dx, y, d_residual}, true, {acc});
+    return e ? e : afan_nhwc::bwd_acc(r);
 }
+
 
 int afan_normalize_nchw(const float* x, void* y, int out_dtype, int out_layout, int64_t n, int64_t c, int64_t hw,
                         const float* mean, const float* std, afan_stream_t stream) {
-    int e = check_common(out_dtype, n, c, hw);
+    const int e = check_request(out_dtype, out_layout, n, c, hw, {x, y, mean, std});
     if (e) return e;
-    if ((e = check_layout(out_layout))) return e;
-    if (!x || !y || !mean || !std) return AFAN_ENULL;
     const int64_t total = n * c * hw;
     const int grid = grid_for(total, BLOCK);
     hipStream_t st = (hipStream_t)stream;

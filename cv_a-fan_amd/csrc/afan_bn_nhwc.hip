@@ -14,7 +14,7 @@
 // slab and the finalize launch: f64 atomics into a few copies per channel, folded in the prologue of the apply pass.
 // Channel counts that do not fit the mapping (C/VEC not a divisor of 256, e.g. C = 304) take the generic
 // kernels: one thread per channel walking rows, lanes across channels (still coalesced, narrower accesses).
-#include "afan_common.h"
+#include "afan_bn_nhwc.h"
 #include <stdlib.h>
 
 using namespace afan;
@@ -114,14 +114,6 @@ inline int acc_slots(int64_t C) {   // NS * C <= 1024, 1 <= NS <= 16, power of t
     while (ns > 1 && (int64_t)ns * C > budget) ns >>= 1;
     return ns;
 }
-
-int64_t acc_doubles(int64_t C);   // doubles per accumulator block (defined with the entry points below)
-
-// How many identical train-mode forward passes the next BatchNorm forward launches of this host thread stand for (1 by
-// default): the running statistics are updated that many times, in sequence, from the same batch moments —
-// main_perturb.py:173 and :196 run the head twice on the same images with the same weights (afan_bn_set_running_updates).
-static thread_local int g_running_updates = 1;
-static inline int running_updates() { return g_running_updates; }
 
 template <int VEC, int NQ, typename A>
 __device__ __forceinline__ void block_fold_atomic(A (&acc)[NQ][VEC], int CV, int C, int NS,
@@ -787,6 +779,12 @@ __global__ __launch_bounds__(BLOCK) void bwd_apply_acc_kernel(const T* __restric
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------
+// How many identical train-mode forward passes the next BatchNorm forward requests of this host thread stand for (1 by
+// default): the running statistics are updated that many times, in sequence, from the same batch moments —
+// main_perturb.py:173 and :196 run the head twice on the same images with the same weights (afan_bn_set_running_updates).
+// Whoever fills a request copies it in through running_updates(); the launch code below sees BnFwd::updates only.
+static thread_local int g_running_updates = 1;
+
 struct Plan {
     bool vec;      // vector mapping usable
     int CV;        // channel vectors per row
@@ -821,239 +819,224 @@ static inline int apply_grid(const Plan& p, int64_t total) {
     return grid_for(p.vec ? (p.nvec + vpt - 1) / vpt : total, BLOCK, cap);
 }
 
+// tensors a backward pass reads beyond dy and x: the forward's output, where it is the ReLU mask
+static inline int mask_reads(const BnBwd& r) { return (r.relu && r.y) ? 1 : 0; }
+
 template <typename T>
-int run_stats(const Plan& p, const T* x_, int64_t M, int64_t C, float eps, float momentum, const float* weight,
-              const float* bias, float* ws, float* stats, float* rmean, float* rvar, int64_t* nbt, hipStream_t st) {
+int run_stats(const Plan& p, const BnFwd& r) {
+    const int64_t M = r.rows(), C = r.c;
+    const BnOperands& b = r.bn;
+    const T* x_ = (const T*)r.x;
+    hipStream_t st = r.st;
     {
         AFAN_PROF("bn_nhwc_stats_kernel", p.tensor_bytes, st);
-        if (p.vec) stats_kernel<T, Elt<T>::VEC><<<p.G, BLOCK, 0, st>>>(x_, p.nvec, p.CV, (int)C, ws);
-        else stats_generic_kernel<T><<<p.G, BLOCK, 0, st>>>(x_, M, (int)C, ws);
+        if (p.vec) stats_kernel<T, Elt<T>::VEC><<<p.G, BLOCK, 0, st>>>(x_, p.nvec, p.CV, (int)C, r.ws);
+        else stats_generic_kernel<T><<<p.G, BLOCK, 0, st>>>(x_, M, (int)C, r.ws);
     }
     AFAN_LAUNCH_CHECK();
     AFAN_PROF("bn_nhwc_finalize_kernel", 8.0 * C * p.G, st);
-    finalize_kernel<T, 0><<<(unsigned)((C + 3) / 4), BLOCK, 0, st>>>(ws, p.G, (int)C, x_, 1.0f / (float)M, (float)M, eps,
-                                                                      momentum, weight, bias, stats, nullptr, rmean,
-                                                                      rvar, nbt, nullptr, nullptr, 0, nullptr, running_updates());
+    finalize_kernel<T, 0><<<(unsigned)((C + 3) / 4), BLOCK, 0, st>>>(r.ws, p.G, (int)C, x_, 1.0f / (float)M, (float)M, b.eps,
+                                                                      b.momentum, b.weight, b.bias, b.stats, nullptr, b.rmean,
+                                                                      b.rvar, b.nbt, nullptr, nullptr, 0, nullptr, r.updates);
     AFAN_LAUNCH_CHECK();
     return AFAN_OK;
 }
 
-// stats: [4][C] = mean, invstd, alpha, beta.  train: computed here; eval: mean/invstd given, alpha/beta derived.
+// the Slab, ConvPartials, Given and Coefs sources.  bn.stats: [4][C] = mean, invstd, alpha, beta.
 template <typename T>
-int forward(const void* x, const void* res, void* y, int64_t M, int64_t C, float eps, float momentum,
-            const float* weight, const float* bias, int relu, float* ws, float* stats, const float* mean_in,
-            const float* invstd_in, float* rmean, float* rvar, int64_t* nbt, bool train, hipStream_t st,
-            const float* partials = nullptr, int64_t partials_g = 0, const float* partials_shift = nullptr) {
+int forward(const BnFwd& r) {
+    const int64_t M = r.rows(), C = r.c;
+    const BnOperands& b = r.bn;
+    hipStream_t st = r.st;
     Plan p;
-    if (!make_plan<T>(M, C, {x, res, y}, p)) return AFAN_ESHAPE;
-    p.vec = p.vec && aligned(stats, 16);
+    if (!make_plan<T>(M, C, {r.x, r.res, r.y}, p)) return AFAN_ESHAPE;
+    p.vec = p.vec && aligned(b.stats, 16);
     constexpr int NV = Elt<T>::VEC;
-    const T* x_ = (const T*)x; const T* r_ = (const T*)res; T* y_ = (T*)y;
-    if (train && partials) {
+    const T* x_ = (const T*)r.x; const T* r_ = (const T*)r.res; T* y_ = (T*)r.y;
+    if (r.src == BnSource::ConvPartials) {
         // moments already summed per tile by the producing convolution's epilogue: only the fold is left
-        AFAN_PROF("bn_nhwc_finalize_kernel", 8.0 * C * partials_g, st);
+        AFAN_PROF("bn_nhwc_finalize_kernel", 8.0 * C * r.partials_g, st);
         finalize_kernel<T, 0><<<(unsigned)((C + 3) / 4), BLOCK, 0, st>>>(
-            partials, (int)partials_g, (int)C, nullptr, 1.0f / (float)M, (float)M, eps, momentum, weight, bias, stats,
-            nullptr, rmean, rvar, nbt, nullptr, nullptr, 0, partials_shift, running_updates());
+            r.partials, (int)r.partials_g, (int)C, nullptr, 1.0f / (float)M, (float)M, b.eps, b.momentum, b.weight, b.bias, b.stats,
+            nullptr, b.rmean, b.rvar, b.nbt, nullptr, nullptr, 0, r.partials_shift, r.updates);
         AFAN_LAUNCH_CHECK();
-    } else if (train) {
-        int e = run_stats<T>(p, x_, M, C, eps, momentum, weight, bias, ws, stats, rmean, rvar, nbt, st);
+    } else if (r.src == BnSource::Slab) {
+        int e = run_stats<T>(p, r);
         if (e) return e;
-    } else if (mean_in) {       // (mean_in == NULL: `stats` already holds mean | invstd | alpha | beta — afan_affine_apply)
+    } else if (r.src == BnSource::Given) {
         AFAN_PROF("bn_nhwc_coef_kernel", 24.0 * C, st);
-        coef_kernel<<<(unsigned)((C + BLOCK - 1) / BLOCK), BLOCK, 0, st>>>((int)C, mean_in, invstd_in, weight, bias, stats);
+        coef_kernel<<<(unsigned)((C + BLOCK - 1) / BLOCK), BLOCK, 0, st>>>((int)C, r.mean_in, r.invstd_in, b.weight, b.bias, b.stats);
         AFAN_LAUNCH_CHECK();
     }
-    AFAN_PROF("bn_nhwc_apply_kernel", p.tensor_bytes * (res ? 3 : 2), st);
+    AFAN_PROF("bn_nhwc_apply_kernel", p.tensor_bytes * (r.res ? 3 : 2), st);
     const int grid = apply_grid(p, M * C);
-#define AFAN_GO(RES, RELU)                                                                                         \
-    do {                                                                                                           \
-        if (p.vec) apply_kernel<T, NV, RES, RELU><<<grid, BLOCK, 0, st>>>(x_, r_, y_, p.nvec, p.CV, (int)C, stats); \
-        else apply_generic_kernel<T, RES, RELU><<<grid, BLOCK, 0, st>>>(x_, r_, y_, M * C, (int)C, stats);          \
-    } while (0)
-    if (res) { if (relu) AFAN_GO(true, true); else AFAN_GO(true, false); }
-    else { if (relu) AFAN_GO(false, true); else AFAN_GO(false, false); }
-#undef AFAN_GO
+    with_flag(r.res, [&](auto RES) { with_flag(r.relu, [&](auto RELU) {
+        if (p.vec) apply_kernel<T, NV, RES(), RELU()><<<grid, BLOCK, 0, st>>>(x_, r_, y_, p.nvec, p.CV, (int)C, b.stats);
+        else apply_generic_kernel<T, RES(), RELU()><<<grid, BLOCK, 0, st>>>(x_, r_, y_, M * C, (int)C, b.stats);
+    }); });
     AFAN_LAUNCH_CHECK();
     return AFAN_OK;
 }
 
 template <typename T>
-int stats_only(const void* x, int64_t M, int64_t C, float eps, float momentum, float* ws, float* stats,
-               float* rmean, float* rvar, int64_t* nbt, hipStream_t st) {
+int stats_only(const BnFwd& r) {
     Plan p;
-    if (!make_plan<T>(M, C, {x}, p)) return AFAN_ESHAPE;
-    return run_stats<T>(p, (const T*)x, M, C, eps, momentum, nullptr, nullptr, ws, stats, rmean, rvar, nbt, st);
+    if (!make_plan<T>(r.rows(), r.c, {r.x}, p)) return AFAN_ESHAPE;
+    return run_stats<T>(p, r);
 }
 
+// the Slab and ConvPartials sources
 template <typename T>
-int backward(const void* dy, const void* x, const void* y, void* dx, void* dres, int64_t M, int64_t C,
-             const float* stats, int relu, float* ws, float* dweight, float* dbias, int accumulate, hipStream_t st,
-             const float* partials = nullptr, int64_t partials_g = 0) {
+int backward(const BnBwd& r) {
+    const int64_t M = r.rows(), C = r.c;
+    hipStream_t st = r.st;
     Plan p;
-    if (!make_plan<T>(M, C, {dy, x, y, dx, dres}, p)) return AFAN_ESHAPE;
-    p.vec = p.vec && aligned(stats, 16);
+    if (!make_plan<T>(M, C, {r.dy, r.x, r.y, r.dx, r.dres}, p)) return AFAN_ESHAPE;
+    p.vec = p.vec && aligned(r.stats, 16);
     constexpr int NV = Elt<T>::VEC;
-    const T* dy_ = (const T*)dy; const T* x_ = (const T*)x; const T* y_ = (const T*)y;
-    float* coef = ws + (int64_t)2 * C * MAX_G;  // [2][C] after the partials (16-byte aligned: C*MAX_G*8 bytes)
-    const float* red = ws;
+    const T* dy_ = (const T*)r.dy; const T* x_ = (const T*)r.x; const T* y_ = (const T*)r.y;
+    T* dx_ = (T*)r.dx; T* dres_ = (T*)r.dres;
+    float* coef = r.ws + (int64_t)2 * C * MAX_G;  // [2][C] after the partials (16-byte aligned: C*MAX_G*8 bytes)
+    const float* red = r.ws;
     int red_g = p.G;
-    if (partials) {   // the producing dgrad's epilogue already took the sums
-        red = partials;
-        red_g = (int)partials_g;
+    if (r.src == BnSource::ConvPartials) {   // the producing dgrad's epilogue already took the sums
+        red = r.partials;
+        red_g = (int)r.partials_g;
     } else {
-        AFAN_PROF("bn_nhwc_bwd_reduce_kernel", p.tensor_bytes * ((relu && y) ? 3 : 2), st);
-#define AFAN_RED(RELU, HY)                                                                                        \
-    do {                                                                                                          \
-        if (p.vec) bwd_reduce_kernel<T, NV, RELU, HY><<<p.G, BLOCK, 0, st>>>(dy_, x_, y_, p.nvec, p.CV, (int)C, stats, ws); \
-        else bwd_reduce_generic_kernel<T, RELU, HY><<<p.G, BLOCK, 0, st>>>(dy_, x_, y_, M, (int)C, stats, ws);      \
-    } while (0)
-        if (!relu) AFAN_RED(false, false);
-        else if (y) AFAN_RED(true, true);
-        else AFAN_RED(true, false);
-#undef AFAN_RED
+        AFAN_PROF("bn_nhwc_bwd_reduce_kernel", p.tensor_bytes * (2 + mask_reads(r)), st);
+        with_mask(r.relu, r.y, [&](auto RELU, auto HY) {
+            if (p.vec) bwd_reduce_kernel<T, NV, RELU(), HY()><<<p.G, BLOCK, 0, st>>>(dy_, x_, y_, p.nvec, p.CV, (int)C, r.stats, r.ws);
+            else bwd_reduce_generic_kernel<T, RELU(), HY()><<<p.G, BLOCK, 0, st>>>(dy_, x_, y_, M, (int)C, r.stats, r.ws);
+        });
     }
     AFAN_LAUNCH_CHECK();
     {
         AFAN_PROF("bn_nhwc_finalize_kernel", 8.0 * C * red_g, st);
         finalize_kernel<T, 1><<<(unsigned)((C + 3) / 4), BLOCK, 0, st>>>(
-            red, red_g, (int)C, nullptr, 1.0f / (float)M, (float)M, 0.f, 0.f, nullptr, nullptr, const_cast<float*>(stats),
-            coef, nullptr, nullptr, nullptr, dweight, dbias, accumulate, nullptr, 1);
+            red, red_g, (int)C, nullptr, 1.0f / (float)M, (float)M, 0.f, 0.f, nullptr, nullptr, const_cast<float*>(r.stats),
+            coef, nullptr, nullptr, nullptr, r.dweight, r.dbias, r.accumulate, nullptr, 1);
     }
     AFAN_LAUNCH_CHECK();
     const int grid = apply_grid(p, M * C);
-    AFAN_PROF("bn_nhwc_bwd_apply_kernel", p.tensor_bytes * (3 + ((relu && y) ? 1 : 0) + (dres ? 1 : 0)), st);
-#define AFAN_APP(RELU, HY, DR)                                                                                    \
-    do {                                                                                                          \
-        if (p.vec) bwd_apply_kernel<T, NV, RELU, HY, DR><<<grid, BLOCK, 0, st>>>(dy_, x_, y_, (T*)dx, (T*)dres, p.nvec, p.CV, (int)C, stats, coef); \
-        else bwd_apply_generic_kernel<T, RELU, HY, DR><<<grid, BLOCK, 0, st>>>(dy_, x_, y_, (T*)dx, (T*)dres, M * C, (int)C, stats, coef); \
-    } while (0)
-    if (!relu) { if (dres) AFAN_APP(false, false, true); else AFAN_APP(false, false, false); }
-    else if (y) { if (dres) AFAN_APP(true, true, true); else AFAN_APP(true, true, false); }
-    else { if (dres) AFAN_APP(true, false, true); else AFAN_APP(true, false, false); }
-#undef AFAN_APP
+    AFAN_PROF("bn_nhwc_bwd_apply_kernel", p.tensor_bytes * (3 + mask_reads(r) + (r.dres ? 1 : 0)), st);
+    with_mask(r.relu, r.y, [&](auto RELU, auto HY) { with_flag(r.dres, [&](auto DR) {
+        if (p.vec) bwd_apply_kernel<T, NV, RELU(), HY(), DR()><<<grid, BLOCK, 0, st>>>(dy_, x_, y_, dx_, dres_, p.nvec, p.CV, (int)C, r.stats, coef);
+        else bwd_apply_generic_kernel<T, RELU(), HY(), DR()><<<grid, BLOCK, 0, st>>>(dy_, x_, y_, dx_, dres_, M * C, (int)C, r.stats, coef);
+    }); });
     AFAN_LAUNCH_CHECK();
     return AFAN_OK;
 }
 
-// ---- accumulator path, host side.  acc: double[acc_doubles(C)] — NS = acc_slots(C) copies of [2][C] accumulators
+// ---- accumulator sources, host side.  acc: double[acc_doubles(C)] — NS = acc_slots(C) copies of [2][C] accumulators
 // (zeroed by the caller before the producer ran), then C floats: the shift the producer used (written by the producing
 // convolution's epilogue).
 template <typename T>
-int forward_acc(const void* x, const void* res, void* y, int64_t M, int64_t C, float eps, float momentum,
-                const float* weight, const float* bias, int relu, double* acc, int acc_ready, float* stats,
-                float* rmean, float* rvar, int64_t* nbt, hipStream_t st, int groups = 1) {
-    // M: rows per group; groups > 1 needs accumulators that a convolution epilogue already filled
-    if (groups < 1 || (groups > 1 && !acc_ready)) return AFAN_ESHAPE;
+int forward_acc(const BnFwd& r) {
+    const bool ready = r.src == BnSource::AccReady;
+    const int groups = r.groups;   // rows() is per group; more than one needs sums that a convolution epilogue already took
+    if (groups < 1 || (groups > 1 && !ready)) return AFAN_ESHAPE;
+    const int64_t M = r.rows(), C = r.c;
+    const BnOperands& b = r.bn;
+    hipStream_t st = r.st;
     Plan p;
-    if (!make_plan<T>(M, C, {x, res, y}, p)) return AFAN_ESHAPE;
-    if (!p.vec || !aligned(stats, 16) || !aligned(acc, 16)) return AFAN_ESHAPE;
+    if (!make_plan<T>(M, C, {r.x, r.res, r.y}, p)) return AFAN_ESHAPE;
+    if (!p.vec || !aligned(b.stats, 16) || !aligned(b.acc, 16)) return AFAN_ESHAPE;
     constexpr int NV = Elt<T>::VEC;
-    const T* x_ = (const T*)x; const T* r_ = (const T*)res; T* y_ = (T*)y;
-    if (!acc_ready) {
+    const T* x_ = (const T*)r.x; const T* r_ = (const T*)r.res; T* y_ = (T*)r.y;
+    const int NS = acc_slots(C);
+    if (!ready) {
         AFAN_PROF("bn_nhwc_stats_kernel", p.tensor_bytes, st);
-        stats_kernel<T, NV, true><<<p.G, BLOCK, 0, st>>>(x_, p.nvec, p.CV, (int)C, nullptr, acc, acc_slots(C));
+        stats_kernel<T, NV, true><<<p.G, BLOCK, 0, st>>>(x_, p.nvec, p.CV, (int)C, nullptr, b.acc, NS);
         AFAN_LAUNCH_CHECK();
     }
-    const int NS = acc_slots(C);
-    const float* shift = acc_ready ? reinterpret_cast<const float*>(acc + (int64_t)2 * NS * C) : nullptr;
+    const float* shift = ready ? reinterpret_cast<const float*>(b.acc + (int64_t)2 * NS * C) : nullptr;
     const size_t lds = (size_t)2 * C * sizeof(float);
     const double inv_m = 1.0 / (double)M;
     const float unbias = M > 1 ? (float)((double)M / (double)(M - 1)) : 1.0f;
-    AFAN_PROF("bn_nhwc_apply_kernel", p.tensor_bytes * (res ? 3 : 2) * groups, st);
+    AFAN_PROF("bn_nhwc_apply_kernel", p.tensor_bytes * (r.res ? 3 : 2) * groups, st);
     const dim3 grid((unsigned)apply_grid(p, M * C), (unsigned)groups);
     const int64_t acc_stride = (acc_doubles(C) + 1) & ~(int64_t)1;
-#define AFAN_GO1(RES, RELU, GR)                                                                                   \
-    apply_acc_kernel<T, NV, RES, RELU, GR><<<grid, BLOCK, lds, st>>>(x_, r_, y_, p.nvec, p.CV, (int)C, NS, acc, shift,   \
-                                                                   inv_m, unbias, eps, momentum, weight, bias, stats,  \
-                                                                   rmean, rvar, nbt, acc_ready, acc_stride,        \
-                                                                   groups > 1 ? 1 : running_updates())
-#define AFAN_GO(RES, RELU) do { if (groups > 1) AFAN_GO1(RES, RELU, true); else AFAN_GO1(RES, RELU, false); } while (0)
-    if (res) { if (relu) AFAN_GO(true, true); else AFAN_GO(true, false); }
-    else { if (relu) AFAN_GO(false, true); else AFAN_GO(false, false); }
-#undef AFAN_GO
-#undef AFAN_GO1
+    const int updates = groups > 1 ? 1 : r.updates;   // the kernel counts the groups themselves as consecutive passes
+    with_flag(r.res, [&](auto RES) { with_flag(r.relu, [&](auto RELU) { with_flag(groups > 1, [&](auto GROUPED) {
+        apply_acc_kernel<T, NV, RES(), RELU(), GROUPED()><<<grid, BLOCK, lds, st>>>(
+            x_, r_, y_, p.nvec, p.CV, (int)C, NS, b.acc, shift, inv_m, unbias, b.eps, b.momentum, b.weight, b.bias, b.stats, b.rmean,
+            b.rvar, b.nbt, ready, acc_stride, updates);
+    }); }); });
     AFAN_LAUNCH_CHECK();
     return AFAN_OK;
 }
 
+static inline DualBN dual_of(const BnOperands& b) { return DualBN{b.acc, b.weight, b.bias, b.stats, b.rmean, b.rvar, b.nbt, b.eps, b.momentum}; }
+
 template <typename T>
-int forward_acc_dual(const void* xa, const void* xb, void* y, int64_t M, int64_t C, const DualBN& A, const DualBN& B,
-                     hipStream_t st) {
+int forward_acc_dual(const BnFwd& r) {
+    const int64_t M = r.rows(), C = r.c;
+    const BnOperands &a = r.bn, &b = r.bn_b;
     Plan p;
-    if (!make_plan<T>(M, C, {xa, xb, y}, p)) return AFAN_ESHAPE;
-    if (!p.vec || !aligned(A.stats, 16) || !aligned(B.stats, 16) || !aligned(A.acc, 16) || !aligned(B.acc, 16)) return AFAN_ESHAPE;
+    if (!make_plan<T>(M, C, {r.x, r.res, r.y}, p)) return AFAN_ESHAPE;
+    if (!p.vec || !aligned(a.stats, 16) || !aligned(b.stats, 16) || !aligned(a.acc, 16) || !aligned(b.acc, 16)) return AFAN_ESHAPE;
     constexpr int NV = Elt<T>::VEC;
     const int NS = acc_slots(C);
     const size_t lds = (size_t)4 * C * sizeof(float);
     const double inv_m = 1.0 / (double)M;
     const float unbias = M > 1 ? (float)((double)M / (double)(M - 1)) : 1.0f;
-    AFAN_PROF("bn_nhwc_apply_kernel", p.tensor_bytes * 3, st);
-    apply_acc_dual_kernel<T, NV><<<apply_grid(p, M * C), BLOCK, lds, st>>>((const T*)xa, (const T*)xb, (T*)y, p.nvec, p.CV, (int)C,
-                                                                           NS, A, B, inv_m, unbias, running_updates());
+    AFAN_PROF("bn_nhwc_apply_kernel", p.tensor_bytes * 3, r.st);
+    apply_acc_dual_kernel<T, NV><<<apply_grid(p, M * C), BLOCK, lds, r.st>>>((const T*)r.x, (const T*)r.res, (T*)r.y, p.nvec, p.CV,
+                                                                             (int)C, NS, dual_of(a), dual_of(b), inv_m, unbias,
+                                                                             r.updates);
     AFAN_LAUNCH_CHECK();
     return AFAN_OK;
 }
 
 template <typename T>
-int backward_acc(const void* dy, const void* x, const void* y, void* dx, void* dres, int64_t M, int64_t C,
-                 const float* stats, int relu, double* acc, int acc_ready, float* dweight, float* dbias,
-                 int accumulate, hipStream_t st, int groups = 1) {
-    if (groups < 1 || (groups > 1 && !acc_ready)) return AFAN_ESHAPE;
+int backward_acc(const BnBwd& r) {
+    const bool ready = r.src == BnSource::AccReady;
+    const int groups = r.groups;   // rows() is per group; more than one needs sums that a convolution epilogue already took
+    if (groups < 1 || (groups > 1 && !ready)) return AFAN_ESHAPE;
+    const int64_t M = r.rows(), C = r.c;
+    hipStream_t st = r.st;
     Plan p;
-    if (!make_plan<T>(M, C, {dy, x, y, dx, dres}, p)) return AFAN_ESHAPE;
-    if (!p.vec || !aligned(stats, 16) || !aligned(acc, 16)) return AFAN_ESHAPE;
+    if (!make_plan<T>(M, C, {r.dy, r.x, r.y, r.dx, r.dres}, p)) return AFAN_ESHAPE;
+    if (!p.vec || !aligned(r.stats, 16) || !aligned(r.acc, 16)) return AFAN_ESHAPE;
     constexpr int NV = Elt<T>::VEC;
-    const T* dy_ = (const T*)dy; const T* x_ = (const T*)x; const T* y_ = (const T*)y;
-    if (!acc_ready) {
-        AFAN_PROF("bn_nhwc_bwd_reduce_kernel", p.tensor_bytes * ((relu && y) ? 3 : 2), st);
-#define AFAN_RED(RELU, HY)                                                                                        \
-    bwd_reduce_kernel<T, NV, RELU, HY, true><<<p.G, BLOCK, 0, st>>>(dy_, x_, y_, p.nvec, p.CV, (int)C, stats, nullptr, acc, acc_slots(C))
-        if (!relu) AFAN_RED(false, false);
-        else if (y) AFAN_RED(true, true);
-        else AFAN_RED(true, false);
-#undef AFAN_RED
+    const T* dy_ = (const T*)r.dy; const T* x_ = (const T*)r.x; const T* y_ = (const T*)r.y;
+    T* dx_ = (T*)r.dx; T* dres_ = (T*)r.dres;
+    const int NS = acc_slots(C);
+    if (!ready) {
+        AFAN_PROF("bn_nhwc_bwd_reduce_kernel", p.tensor_bytes * (2 + mask_reads(r)), st);
+        with_mask(r.relu, r.y, [&](auto RELU, auto HY) {
+            bwd_reduce_kernel<T, NV, RELU(), HY(), true><<<p.G, BLOCK, 0, st>>>(dy_, x_, y_, p.nvec, p.CV, (int)C, r.stats, nullptr, r.acc, NS);
+        });
         AFAN_LAUNCH_CHECK();
     }
     const dim3 grid((unsigned)apply_grid(p, M * C), (unsigned)groups);
     const int64_t acc_stride = (acc_doubles(C) + 1) & ~(int64_t)1;
     const double inv_m = 1.0 / (double)M;
-    const int NS = acc_slots(C);
     const size_t lds = (size_t)2 * C * sizeof(float);
-    AFAN_PROF("bn_nhwc_bwd_apply_kernel", p.tensor_bytes * (3 + ((relu && y) ? 1 : 0) + (dres ? 1 : 0)) * groups, st);
-#define AFAN_APP1(RELU, HY, DR, GR)                                                                               \
-    bwd_apply_acc_kernel<T, NV, RELU, HY, DR, GR><<<grid, BLOCK, lds, st>>>(dy_, x_, y_, (T*)dx, (T*)dres, p.nvec, p.CV, \
-                                                                            (int)C, NS, stats, acc, inv_m, dweight, \
-                                                                            dbias, accumulate, acc_stride)
-#define AFAN_APP(RELU, HY, DR) do { if (groups > 1) AFAN_APP1(RELU, HY, DR, true); else AFAN_APP1(RELU, HY, DR, false); } while (0)
-    if (!relu) { if (dres) AFAN_APP(false, false, true); else AFAN_APP(false, false, false); }
-    else if (y) { if (dres) AFAN_APP(true, true, true); else AFAN_APP(true, true, false); }
-    else { if (dres) AFAN_APP(true, false, true); else AFAN_APP(true, false, false); }
-#undef AFAN_APP1
-#undef AFAN_APP
+    AFAN_PROF("bn_nhwc_bwd_apply_kernel", p.tensor_bytes * (3 + mask_reads(r) + (r.dres ? 1 : 0)) * groups, st);
+    with_mask(r.relu, r.y, [&](auto RELU, auto HY) { with_flag(r.dres, [&](auto DR) { with_flag(groups > 1, [&](auto GROUPED) {
+        bwd_apply_acc_kernel<T, NV, RELU(), HY(), DR(), GROUPED()><<<grid, BLOCK, lds, st>>>(
+            dy_, x_, y_, dx_, dres_, p.nvec, p.CV, (int)C, NS, r.stats, r.acc, inv_m, r.dweight, r.dbias, r.accumulate, acc_stride);
+    }); }); });
     AFAN_LAUNCH_CHECK();
     return AFAN_OK;
 }
 
-int fwd_acc(int dtype, const void* x, const void* res, void* y, int64_t M, int64_t C, float eps, float mom,
-            const float* w, const float* b, int relu, double* acc, int acc_ready, float* stats, float* rm, float* rv,
-            int64_t* nbt, hipStream_t st, int groups) {
-    return dtype == AFAN_F32 ? forward_acc<float>(x, res, y, M, C, eps, mom, w, b, relu, acc, acc_ready, stats, rm, rv, nbt, st, groups)
-                             : forward_acc<uint16_t>(x, res, y, M, C, eps, mom, w, b, relu, acc, acc_ready, stats, rm, rv, nbt, st, groups);
+// ---- the entry points of afan_bn_nhwc.h --------------------------------------------------------------------
+// (the launch templates are instantiated in the order of these definitions, and the kernels of the code object follow it)
+int fwd_acc(const BnFwd& r) { return with_dtype(r.dtype, [&](auto t) { return forward_acc<decltype(t)>(r); }); }
+int fwd_dual(const BnFwd& r) { return with_dtype(r.dtype, [&](auto t) { return forward_acc_dual<decltype(t)>(r); }); }
+int bwd_acc(const BnBwd& r) { return with_dtype(r.dtype, [&](auto t) { return backward_acc<decltype(t)>(r); }); }
+int fwd(const BnFwd& r) { return with_dtype(r.dtype, [&](auto t) { return forward<decltype(t)>(r); }); }
+int stats(const BnFwd& r) { return with_dtype(r.dtype, [&](auto t) { return stats_only<decltype(t)>(r); }); }
+int bwd(const BnBwd& r) { return with_dtype(r.dtype, [&](auto t) { return backward<decltype(t)>(r); }); }
+int coefs(int64_t C, const float* mean, const float* invstd, const float* w, const float* b, float* out, hipStream_t st) {
+    AFAN_PROF("bn_nhwc_coef_kernel", 24.0 * C, st);
+    coef_kernel<<<(unsigned)((C + BLOCK - 1) / BLOCK), BLOCK, 0, st>>>((int)C, mean, invstd, w, b, out);
+    AFAN_LAUNCH_CHECK();
+    return AFAN_OK;
 }
-int fwd_acc_dual(int dtype, const void* xa, const void* xb, void* y, int64_t M, int64_t C, float eps_a, float mom_a,
-                 const float* w_a, const float* b_a, double* acc_a, float* stats_a, float* rm_a, float* rv_a, int64_t* nbt_a,
-                 float eps_b, float mom_b, const float* w_b, const float* b_b, double* acc_b, float* stats_b, float* rm_b,
-                 float* rv_b, int64_t* nbt_b, hipStream_t st) {
-    const DualBN A{acc_a, w_a, b_a, stats_a, rm_a, rv_a, nbt_a, eps_a, mom_a}, B{acc_b, w_b, b_b, stats_b, rm_b, rv_b, nbt_b, eps_b, mom_b};
-    return dtype == AFAN_F32 ? forward_acc_dual<float>(xa, xb, y, M, C, A, B, st) : forward_acc_dual<uint16_t>(xa, xb, y, M, C, A, B, st);
-}
-int bwd_acc(int dtype, const void* dy, const void* x, const void* y, void* dx, void* dres, int64_t M, int64_t C,
-            const float* stats_in, int relu, double* acc, int acc_ready, float* dw, float* db, int accumulate,
-            hipStream_t st, int groups) {
-    return dtype == AFAN_F32 ? backward_acc<float>(dy, x, y, dx, dres, M, C, stats_in, relu, acc, acc_ready, dw, db, accumulate, st, groups)
-                             : backward_acc<uint16_t>(dy, x, y, dx, dres, M, C, stats_in, relu, acc, acc_ready, dw, db, accumulate, st, groups);
-}
+
 int64_t acc_doubles(int64_t C) { return C > 0 ? (int64_t)2 * acc_slots(C) * C + (C + 1) / 2 : 0; }
 int acc_slot_count(int64_t C) { return acc_slots(C); }
 // can the accumulator path take this channel count (vector mapping: C/VEC divides the block)
@@ -1061,34 +1044,7 @@ int acc_supported(int dtype, int64_t C) {
     const int nv = dtype == AFAN_F32 ? Elt<float>::VEC : Elt<uint16_t>::VEC;
     return C > 0 && C % nv == 0 && C / nv <= BLOCK && BLOCK % (C / nv) == 0;
 }
-
-// entry points used by afan_bn.hip's extern "C" dispatch (dtype: 0 = f32, 1 = bf16)
-int fwd(int dtype, const void* x, const void* res, void* y, int64_t M, int64_t C, float eps, float mom, const float* w,
-        const float* b, int relu, float* ws, float* stats, const float* mean_in, const float* invstd_in, float* rm,
-        float* rv, int64_t* nbt, bool train, hipStream_t st, const float* partials, int64_t partials_g,
-        const float* partials_shift) {
-    return dtype == AFAN_F32
-               ? forward<float>(x, res, y, M, C, eps, mom, w, b, relu, ws, stats, mean_in, invstd_in, rm, rv, nbt, train, st, partials, partials_g, partials_shift)
-               : forward<uint16_t>(x, res, y, M, C, eps, mom, w, b, relu, ws, stats, mean_in, invstd_in, rm, rv, nbt, train, st, partials, partials_g, partials_shift);
-}
-int stats(int dtype, const void* x, int64_t M, int64_t C, float eps, float mom, float* ws, float* stats_out, float* rm,
-          float* rv, int64_t* nbt, hipStream_t st) {
-    return dtype == AFAN_F32 ? stats_only<float>(x, M, C, eps, mom, ws, stats_out, rm, rv, nbt, st)
-                             : stats_only<uint16_t>(x, M, C, eps, mom, ws, stats_out, rm, rv, nbt, st);
-}
-int bwd(int dtype, const void* dy, const void* x, const void* y, void* dx, void* dres, int64_t M, int64_t C,
-        const float* stats_in, int relu, float* ws, float* dw, float* db, int acc, hipStream_t st,
-        const float* partials, int64_t partials_g) {
-    return dtype == AFAN_F32
-               ? backward<float>(dy, x, y, dx, dres, M, C, stats_in, relu, ws, dw, db, acc, st, partials, partials_g)
-               : backward<uint16_t>(dy, x, y, dx, dres, M, C, stats_in, relu, ws, dw, db, acc, st, partials, partials_g);
-}
-int coefs(int64_t C, const float* mean, const float* invstd, const float* w, const float* b, float* out, hipStream_t st) {
-    AFAN_PROF("bn_nhwc_coef_kernel", 24.0 * C, st);
-    coef_kernel<<<(unsigned)((C + BLOCK - 1) / BLOCK), BLOCK, 0, st>>>((int)C, mean, invstd, w, b, out);
-    AFAN_LAUNCH_CHECK();
-    return AFAN_OK;
-}
+int running_updates() { return g_running_updates; }
 int set_running_updates(int n) {
     const int old = g_running_updates;
     g_running_updates = n < 0 ? 1 : n;     // 0: normalise with the batch moments, leave the running statistics alone (a deferred update)

@@ -23,6 +23,7 @@
 // (Measured-and-lost variants — 256-row tiles, producer waves on the two-stage launches, a half-step software pipeline,
 // streaming stores, register-streamed weights — are described in NOTES.md 9.5 and no longer compiled in.)
 #include "afan_common.h"
+#include "afan_bn_nhwc.h"
 #include "afan_conv_c64.h"
 #include "afan_conv_stem.h"
 #include "afan_conv_params.h"
@@ -37,12 +38,6 @@
 
 using namespace afan;
 using namespace afan_conv;
-
-namespace afan_nhwc {   // afan_bn_nhwc.hip: accumulator copies per channel / doubles per accumulator block
-int acc_slot_count(int64_t C);
-int64_t acc_doubles(int64_t C);
-int set_running_updates(int n);
-}
 
 namespace {
 
@@ -1707,11 +1702,9 @@ struct FwdBn {
     float* stats; float* running_mean; float* running_var; int64_t* num_batches; int relu; void* barrier;
 };
 static void set_fwd_bnf(ConvP& p, const FwdBn& b, int64_t M) {
-    const int pending = afan_nhwc::set_running_updates(1);
-    afan_nhwc::set_running_updates(pending);
     p.bnf = 1; p.bar = (unsigned*)b.barrier; p.y2 = (uint16_t*)b.y_act;
     p.bnf_w = b.weight; p.bnf_b = b.bias; p.bnf_eps = b.eps; p.bnf_mom = b.momentum;
-    p.bnf_rmean = b.running_mean; p.bnf_rvar = b.running_var; p.bnf_nbt = b.num_batches; p.bnf_updates = pending;
+    p.bnf_rmean = b.running_mean; p.bnf_rvar = b.running_var; p.bnf_nbt = b.num_batches; p.bnf_updates = afan_nhwc::running_updates();
     p.bnf_stats = b.stats; p.bnf_relu = b.relu ? 1 : 0;
     p.bnf_inv_m = 1.0 / (double)M;
     p.bnf_unbias = M > 1 ? (float)((double)M / (double)(M - 1)) : 1.0f;
