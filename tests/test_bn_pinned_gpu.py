@@ -93,6 +93,10 @@ C_DB = {k: 3.0 * v for k, v in DB_MEASURED.items()}
 # invstd: train-f32-4x6x8x8-nchw-cancel, train-bf16-3x304x5x7 (15 rows per fp32 thread sum), train-f32-5x200x6x5, acc0-bf16-65x16x64x64,
 # acc0-f32-2x1024x33x29
 STAT_MEAN_MEASURED = {"nchw": 1.69, "slab_f32sum": 0.80, "slab_f64sum": 1.12, "acc_f32sum": 0.79, "acc_f64sum": 0.79}
+# ... and of accumulators a CONVOLUTION epilogue filled (bf16 tile minus a non-integer shift summed in fp32 within a row tile, f64 across
+# tiles), consumed by afan_bn_train_forward_acc[_dual] or inside the launch: tests/test_conv_fused_pinned_gpu.py's table, where the
+# two-launch and the in-launch form alike pass 3 * 0.79 (worst, both forms: fwd_bn t64h_cols_8x8, 64-row tiles of 8 accumulator slots)
+STAT_MEAN_MEASURED["conv_acc_f64sum"] = 2.74
 STAT_INVSTD_MEASURED = {"nchw": 4.11, "slab_f32sum": 16.45, "slab_f64sum": 4.62, "acc_f32sum": 7.74, "acc_f64sum": 1.93}
 C_STAT_MEAN = {k: 3.0 * v for k, v in STAT_MEAN_MEASURED.items()}
 C_STAT_INVSTD = {k: 3.0 * v for k, v in STAT_INVSTD_MEASURED.items()}
