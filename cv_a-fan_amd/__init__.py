@@ -17,6 +17,6 @@ train_aug_sat_muti_advt is the entry point for cmd/run_det.sh), det_eval (the VO
 from . import _lib, ops  # noqa: F401
 from ._lib import AfanLibraryError, LIB_PATH  # noqa: F401
 from . import resnet_s, frozen, pgd, attack_algo, arena, grid_guard, train_step, learnable, seg_attack_algo, deeplab, seg_trainer, seg_data, seg_eval, det_ops, det_attack_algo, det_model, det_trainer, det_data, det_entry, det_eval, host, infer  # noqa: F401
-from .attack_algo import PGD, get_sample_points, linfball_proj, mix_feature, tensor_clamp  # noqa: F401
+from .attack_algo import PGD, get_sample_points, l2ball_proj, linfball_proj, mix_feature, tensor_clamp  # noqa: F401
 
 __version__ = "0.1.0"

@@ -27,6 +27,8 @@ SIGNATURES = {
     "afan_norms_workspace_floats": (_l, [_l, _l]),
     "afan_pgd_step_norms": (_i, [_p, _p, _i, _p, _p, _l, _l, _f, _f, _i, _p, _p, _p, _p]),
     "afan_perturb_norms": (_i, [_p, _p, _l, _l, _p, _p, _p, _p]),
+    "afan_pgd_step_l2_workspace_floats": (_l, [_l, _l]),
+    "afan_pgd_step_l2": (_i, [_p, _p, _i, _p, _p, _l, _l, _f, _f, _i, _p, _p, _p, _p]),
     "afan_axpy_noise": (_i, [_p, _p, _l, _f, _p, _p]),
     "afan_pgd_rand_start": (_i, [_p, _p, _p, _l, _l, _l, _l, _i, _f, _p, _p, _i, _p]),
     "afan_mix_feature": (_i, [_p, _p, _p, _l, _l, _l, _f, _i, _p]),

@@ -13,7 +13,7 @@ import torch
 from . import ops, pgd
 from .resnet_s import _dense, _like_layout, fused_criterion
 
-__all__ = ["PGD", "tensor_clamp", "linfball_proj", "mix_feature", "get_sample_points", "last_norms"]
+__all__ = ["PGD", "tensor_clamp", "linfball_proj", "l2ball_proj", "mix_feature", "get_sample_points", "last_norms"]
 
 _last = {"l2": None, "linf": None}
 
@@ -39,9 +39,23 @@ def linfball_proj(center, radius, t, in_place=True):
     return res
 
 
+def l2ball_proj(center, radius, t, in_place=True):
+    """attack_algo.py:21-33: project each sample t[b] onto the L2 ball of `radius` around center[b] (the projection-only form of
+    ops.pgd_step_l2_: two launches).  Two deliberate differences from the reference as written: a point inside the ball keeps its
+    bits, where the reference rounds every point through `/ dist * dist`; and a zero perturbation stays zero, where the reference
+    divides 0 / 0 and returns NaN."""
+    res = t if in_place else t.clone()
+    data = res.data
+    if _dense(data) is not data or data.dtype != torch.float32:
+        raise ValueError("l2ball_proj: t must be a dense fp32 tensor (contiguous NCHW or channels_last)")
+    ops.pgd_step_l2_(data, None, 0.0, x_clean=_like_layout(center.detach().float(), data), eps=float(radius), clip=True)
+    return res
+
+
 def PGD(x, loss_fn, y=None, model=None, steps=3, gamma=None, start_idx=1, layer_number=16, eps=(2 / 255),
-        randinit=False, clip=False, with_norms=False, grad0=None):
-    """K-step sign-gradient ascent on the feature map `x` (attack_algo.py:38-58).
+        randinit=False, clip=False, with_norms=False, grad0=None, norm="linf"):
+    """K-step sign-gradient ascent on the feature map `x` (attack_algo.py:38-58).  norm="l2" (an addition): the steps are
+    normalised-gradient steps and the projection is onto the L2 ball (pgd.step(norm="l2")); the random start is pgd.start's.
 
     Returns a NEW fp32 leaf tensor with requires_grad=True; `x` is not modified.  `with_norms=True`
     (an addition) fuses the per-sample L2/Linf perturbation norms into the last step; read them with
@@ -50,6 +64,7 @@ def PGD(x, loss_fn, y=None, model=None, steps=3, gamma=None, start_idx=1, layer_
     """
     if x.device.type != "cuda":
         raise ops.AfanLibraryError("PGD: x must live on the MI355X (no CPU path in this build)")
+    pgd._check_norm(norm)
     # keep whatever dense layout the feature map has (the bf16 backbone hands over channels-last tensors: a
     # .contiguous() here would transpose 64 MB to NCHW and the tail would transpose it back every PGD step)
     lp = getattr(model, "compute_dtype", torch.float32) == torch.bfloat16
@@ -60,7 +75,11 @@ def PGD(x, loss_fn, y=None, model=None, steps=3, gamma=None, start_idx=1, layer_
     x, x_adv, shadow = ops.pgd_init(_dense(x.detach()), want_shadow=lp and grad0 is None and not randinit)
     if lp and shadow is None:
         shadow = torch.empty_like(x, dtype=torch.bfloat16)
-    if randinit:
+    if randinit and norm == "l2":
+        # pgd.start's L2 start (a point of the eps-sphere along a host-drawn Gaussian direction), written with the shadow
+        u = _like_layout(torch.randn(x_adv.shape).to(x.device, non_blocking=True), x_adv)
+        ops.pgd_step_l2_(x_adv, u, eps, clip=False, shadow=shadow)
+    elif randinit:
         # the reference draws the noise on the CPU default generator (attack_algo.py:44); same stream here
         ops.axpy_noise_(x_adv, torch.rand(x_adv.shape).to(x.device, non_blocking=True), eps, shadow)
     l2 = linf = None
@@ -73,9 +92,9 @@ def PGD(x, loss_fn, y=None, model=None, steps=3, gamma=None, start_idx=1, layer_
             xin = (shadow if lp else x_adv).detach().requires_grad_(True)
             grad = pgd.input_gradient(lambda t: loss_fn(model(t, end_point=layer_number, start_point=start_idx), y), xin)
         if with_norms and t == steps - 1:
-            l2, linf = pgd.step(x_adv, grad, gamma, x, eps, clip, shadow, norms=True)
+            l2, linf = pgd.step(x_adv, grad, gamma, x, eps, clip, shadow, norms=True, norm=norm)
         else:
-            pgd.step(x_adv, grad, gamma, x, eps, clip, shadow)
+            pgd.step(x_adv, grad, gamma, x, eps, clip, shadow, norm=norm)
     if with_norms:
         if l2 is None:
             l2, linf = ops.perturb_norms(x_adv, x)

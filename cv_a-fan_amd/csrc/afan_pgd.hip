@@ -1,5 +1,6 @@
 // PGD feature-ascent kernels for gfx950: sign-step (+ L-inf projection) fused with the per-sample
-// perturbation norms and the bf16 shadow copy; host-noise random start; device-drawn random start (Philox4x32-10).
+// perturbation norms and the bf16 shadow copy; host-noise random start; device-drawn random start (Philox4x32-10);
+// the L2 step: per-sample normalised gradient step + projection onto the L2 ball, three launches with deterministic sums.
 // Reference behaviour restated (not translated) from Classification/attack_algo.py:9-19,35-36,41-56
 // and Classification/main_perturb.py:188-192.  All of these are HBM-bound streaming kernels:
 // 16 B per lane per access, grid-stride, >= 2048 workgroups when the tensor allows it.
@@ -400,6 +401,222 @@ __global__ __launch_bounds__(BLOCK) void pgd_init_kernel(const S* __restrict__ x
     }
 }
 
+// ---- L2 step: normalised gradient step + projection onto the L2 ball (afan_hip.h states the arithmetic) ---------------------------
+// Workgroup blk = b * chunks + c owns elements [c * L2_CHUNK, (c + 1) * L2_CHUNK) of sample b.  Three launches: the partial sums of
+// g^2 (4 B/elt); the step, the shadow and the partial sums of d^2 (18 B/elt); the projection of the samples outside the ball
+// (14 B/elt of those).  A sample's partials are added again by every workgroup of the next launch, in one fixed order.
+constexpr int L2_CHUNK = 4096;
+
+// the block's sum, the same bits in every thread: butterfly, then the 4 wave sums in order
+__device__ __forceinline__ float block_sum_all(float v) {
+    __shared__ float s_w[BLOCK / AFAN_WAVE];
+    v = wave_sum(v);
+    if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = v;
+    __syncthreads();
+    float a = 0.f;
+#pragma unroll
+    for (int k = 0; k < BLOCK / AFAN_WAVE; ++k) a += s_w[k];
+    __syncthreads();  // (the next call writes s_w again)
+    return a;
+}
+
+__device__ __forceinline__ float sample_sum(const float* __restrict__ part, int chunks) {
+    float t = 0.f;
+    for (int i = threadIdx.x; i < chunks; i += BLOCK) t += part[i];
+    return block_sum_all(t);
+}
+
+template <typename G, bool VEC>
+__global__ __launch_bounds__(BLOCK) void l2_grad_ss_kernel(const G* __restrict__ grad, int64_t per_sample, int chunks,
+                                                           float* __restrict__ gpart) {
+    constexpr int W = Elt<G>::VEC;
+    const int64_t b = blockIdx.x / chunks, c = blockIdx.x - b * chunks;
+    const int64_t base = b * per_sample, lo = c * L2_CHUNK;
+    const int64_t hi = (lo + L2_CHUNK < per_sample) ? lo + L2_CHUNK : per_sample;
+    float ss = 0.f;
+    if (VEC) {  // per_sample % W == 0 and a 16-byte aligned base
+        for (int64_t j = lo + (int64_t)threadIdx.x * W; j < hi; j += BLOCK * W) {
+            float g[W];
+            Elt<G>::ldv(grad + base + j, g);
+#pragma unroll
+            for (int k = 0; k < W; ++k) ss += g[k] * g[k];
+        }
+    } else {
+        for (int64_t j = lo + threadIdx.x; j < hi; j += BLOCK) {
+            const float g = Elt<G>::ld(grad + base + j);
+            ss += g * g;
+        }
+    }
+    ss = block_sum_all(ss);
+    if (threadIdx.x == 0) gpart[blockIdx.x] = ss;
+}
+
+// STEP: there is a gradient.  DIST: x_clean is read and the partial sums of d^2 are written.
+template <typename G, bool STEP, bool DIST, bool SHADOW, bool VEC>
+__global__ __launch_bounds__(BLOCK) void l2_step_kernel(float* __restrict__ x_adv, const G* __restrict__ grad,
+                                                        const float* __restrict__ x_clean, uint16_t* __restrict__ shadow,
+                                                        int64_t per_sample, int chunks, float gamma,
+                                                        const float* __restrict__ gpart, float* __restrict__ dpart,
+                                                        float* __restrict__ gnorm_out) {
+    constexpr int W = Elt<G>::VEC;
+    const int64_t b = blockIdx.x / chunks, c = blockIdx.x - b * chunks;
+    const int64_t base = b * per_sample, lo = c * L2_CHUNK;
+    const int64_t hi = (lo + L2_CHUNK < per_sample) ? lo + L2_CHUNK : per_sample;
+    float a = 0.f, ng = 0.f;
+    bool skip = true;
+    if (STEP) {
+        ng = sqrtf(sample_sum(gpart + b * chunks, chunks));
+        skip = ng == 0.f;  // (a NaN norm is not zero: the sample becomes NaN)
+        a = gamma / ng;
+    }
+    if (gnorm_out && c == 0 && threadIdx.x == 0) gnorm_out[b] = ng;
+    float ss = 0.f;
+    if (VEC) {
+        for (int64_t j = lo + (int64_t)threadIdx.x * W; j < hi; j += BLOCK * W) {
+            const int64_t i = base + j;
+            float g[W];
+            if (STEP) Elt<G>::ldv(grad + i, g);
+#pragma unroll
+            for (int q = 0; q < W; q += 4) {
+                float xa[4], xc[4];
+                Elt<float>::ldv(x_adv + i + q, xa);
+                if (DIST) Elt<float>::ldv(x_clean + i + q, xc);
+                if (STEP) {
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) {
+                        const float p = a * g[q + k];
+                        xa[k] = skip ? xa[k] : xa[k] + p;
+                    }
+                    Elt<float>::stv(x_adv + i + q, xa);
+                }
+                if (SHADOW) {
+                    u16x4 s;
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) s[k] = f2bf(xa[k]);
+                    *reinterpret_cast<u16x4*>(shadow + i + q) = s;
+                }
+                if (DIST) {
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) {
+                        const float d = xa[k] - xc[k];
+                        ss += d * d;
+                    }
+                }
+            }
+        }
+    } else {
+        for (int64_t j = lo + threadIdx.x; j < hi; j += BLOCK) {
+            const int64_t i = base + j;
+            float xa = x_adv[i];
+            if (STEP) {
+                const float p = a * Elt<G>::ld(grad + i);
+                xa = skip ? xa : xa + p;
+                x_adv[i] = xa;
+            }
+            if (SHADOW) shadow[i] = f2bf(xa);
+            if (DIST) {
+                const float d = xa - x_clean[i];
+                ss += d * d;
+            }
+        }
+    }
+    if (DIST) {
+        ss = block_sum_all(ss);
+        if (threadIdx.x == 0) dpart[blockIdx.x] = ss;
+    }
+}
+
+// The workgroups of a sample inside the ball (nd <= eps, or nd = NaN) return at once: launch 2 wrote its final values and shadow.
+template <bool SHADOW, bool VEC>
+__global__ __launch_bounds__(BLOCK) void l2_project_kernel(float* __restrict__ x_adv, const float* __restrict__ x_clean,
+                                                           uint16_t* __restrict__ shadow, int64_t per_sample, int chunks,
+                                                           float eps, const float* __restrict__ dpart,
+                                                           float* __restrict__ dnorm_out) {
+    const int64_t b = blockIdx.x / chunks, c = blockIdx.x - b * chunks;
+    const float nd = sqrtf(sample_sum(dpart + b * chunks, chunks));
+    const bool outside = nd > eps;
+    if (dnorm_out && c == 0 && threadIdx.x == 0) dnorm_out[b] = outside ? eps : nd;
+    if (!outside) return;
+    const float s = eps / nd;
+    const int64_t base = b * per_sample, lo = c * L2_CHUNK;
+    const int64_t hi = (lo + L2_CHUNK < per_sample) ? lo + L2_CHUNK : per_sample;
+    if (VEC) {
+        for (int64_t j = lo + (int64_t)threadIdx.x * 4; j < hi; j += BLOCK * 4) {
+            const int64_t i = base + j;
+            float xa[4], xc[4];
+            Elt<float>::ldv(x_adv + i, xa);
+            Elt<float>::ldv(x_clean + i, xc);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const float d = xa[k] - xc[k];
+                const float q = d * s;
+                xa[k] = xc[k] + q;
+            }
+            Elt<float>::stv(x_adv + i, xa);
+            if (SHADOW) {
+                u16x4 sh;
+#pragma unroll
+                for (int k = 0; k < 4; ++k) sh[k] = f2bf(xa[k]);
+                *reinterpret_cast<u16x4*>(shadow + i) = sh;
+            }
+        }
+    } else {
+        for (int64_t j = lo + threadIdx.x; j < hi; j += BLOCK) {
+            const int64_t i = base + j;
+            const float xc = x_clean[i];
+            const float d = x_adv[i] - xc;
+            const float q = d * s;
+            const float t = xc + q;
+            x_adv[i] = t;
+            if (SHADOW) shadow[i] = f2bf(t);
+        }
+    }
+}
+
+template <typename G, bool STEP>
+int launch_step_l2(float* x_adv, const void* grad, const float* x_clean, uint16_t* shadow, int64_t batch, int64_t per_sample,
+                   int chunks, float gamma, float eps, bool dist, float* ws, float* gnorm, float* dnorm, hipStream_t st) {
+    constexpr int W = Elt<G>::VEC;
+    const unsigned grid = (unsigned)(batch * chunks);
+    const double elts = (double)batch * (double)per_sample;
+    float* gpart = ws;
+    float* dpart = ws + (int64_t)grid;
+    const bool xvec = aligned(x_adv, 16) && (!dist || aligned(x_clean, 16)) && (!shadow || aligned(shadow, 8));
+    const bool gvec = !STEP || (per_sample % W == 0 && aligned(grad, 16));
+    if (STEP) {
+        AFAN_PROF("l2_grad_ss_kernel", elts * sizeof(G), st);
+        if (gvec) l2_grad_ss_kernel<G, true><<<grid, BLOCK, 0, st>>>((const G*)grad, per_sample, chunks, gpart);
+        else l2_grad_ss_kernel<G, false><<<grid, BLOCK, 0, st>>>((const G*)grad, per_sample, chunks, gpart);
+        AFAN_LAUNCH_CHECK();
+    }
+    {
+        const bool vec = xvec && gvec && per_sample % W == 0;
+        AFAN_PROF("l2_step_kernel", elts * (4.0 + (STEP ? 4.0 + sizeof(G) : 0.0) + (dist ? 4 : 0) + (shadow ? 2 : 0)), st);
+#define AFAN_L2(DIST, SHADOW)                                                                                                     \
+    if (vec) l2_step_kernel<G, STEP, DIST, SHADOW, true><<<grid, BLOCK, 0, st>>>(x_adv, (const G*)grad, x_clean, shadow, per_sample, \
+                                                                                  chunks, gamma, gpart, dpart, gnorm);             \
+    else l2_step_kernel<G, STEP, DIST, SHADOW, false><<<grid, BLOCK, 0, st>>>(x_adv, (const G*)grad, x_clean, shadow, per_sample,   \
+                                                                               chunks, gamma, gpart, dpart, gnorm);
+        if (dist) { if (shadow) { AFAN_L2(true, true) } else { AFAN_L2(true, false) } }
+        else { if (shadow) { AFAN_L2(false, true) } else { AFAN_L2(false, false) } }
+#undef AFAN_L2
+        AFAN_LAUNCH_CHECK();
+    }
+    if (dist) {
+        const bool vec = xvec && per_sample % 4 == 0;
+        AFAN_PROF("l2_project_kernel", elts * (8.0 + 4.0 + (shadow ? 2 : 0)), st);  // (upper bound: every sample outside the ball)
+        if (shadow) {
+            if (vec) l2_project_kernel<true, true><<<grid, BLOCK, 0, st>>>(x_adv, x_clean, shadow, per_sample, chunks, eps, dpart, dnorm);
+            else l2_project_kernel<true, false><<<grid, BLOCK, 0, st>>>(x_adv, x_clean, shadow, per_sample, chunks, eps, dpart, dnorm);
+        } else {
+            if (vec) l2_project_kernel<false, true><<<grid, BLOCK, 0, st>>>(x_adv, x_clean, shadow, per_sample, chunks, eps, dpart, dnorm);
+            else l2_project_kernel<false, false><<<grid, BLOCK, 0, st>>>(x_adv, x_clean, shadow, per_sample, chunks, eps, dpart, dnorm);
+        }
+        AFAN_LAUNCH_CHECK();
+    }
+    return AFAN_OK;
+}
+
 template <typename G, bool CLIP, bool SHADOW>
 int launch_step(float* x_adv, const void* grad, const float* x_clean, uint16_t* shadow, int64_t n,
                 float gamma, float eps, hipStream_t st) {
@@ -519,6 +736,42 @@ int afan_perturb_norms(const float* x_adv, const float* x_clean, int64_t batch, 
     return launch_step_norms<float, false, false, false>(const_cast<float*>(x_adv), nullptr, x_clean,
                                                          nullptr, batch, per_sample, 0.f, 0.f, partial,
                                                          l2_out, linf_out, (hipStream_t)stream);
+}
+
+static int64_t l2_chunks(int64_t per_sample) { return per_sample / L2_CHUNK + (per_sample % L2_CHUNK != 0); }  // (no overflow)
+
+int64_t afan_pgd_step_l2_workspace_floats(int64_t batch, int64_t per_sample) {
+    if (batch <= 0 || per_sample <= 0) return 0;
+    const int64_t chunks = l2_chunks(per_sample);
+    if (chunks > INT32_MAX / batch) return 0;  // (afan_pgd_step_l2 refuses the shape)
+    return 2 * batch * chunks;
+}
+
+int afan_pgd_step_l2(float* x_adv, const void* grad, int grad_dtype, const float* x_clean,
+                     uint16_t* shadow_bf16, int64_t batch, int64_t per_sample,
+                     float gamma, float eps, int clip, float* workspace,
+                     float* gnorm_out, float* dnorm_out, afan_stream_t stream) {
+    if (batch < 0 || per_sample < 0) return AFAN_ESHAPE;
+    if (batch == 0 || per_sample == 0) return AFAN_OK;
+    const int64_t chunks = l2_chunks(per_sample);
+    if (chunks > INT32_MAX / batch || per_sample > INT64_MAX / batch) return AFAN_ESHAPE;
+    const bool dist = clip || dnorm_out;
+    if (!x_adv || !workspace || (dist && !x_clean)) return AFAN_ENULL;
+    if (grad && grad_dtype != AFAN_F32 && grad_dtype != AFAN_BF16) return AFAN_EDTYPE;
+    if (!aligned(x_adv, 4) || (grad && !aligned(grad, grad_dtype == AFAN_F32 ? 4 : 2)) || (dist && !aligned(x_clean, 4)) ||
+        (shadow_bf16 && !aligned(shadow_bf16, 2)) || !aligned(workspace, 4) || (gnorm_out && !aligned(gnorm_out, 4)) ||
+        (dnorm_out && !aligned(dnorm_out, 4)))
+        return AFAN_EALIGN;
+    hipStream_t st = (hipStream_t)stream;
+    const float radius = clip ? eps : __builtin_inff();  // (the norm alone: no sample is outside)
+    if (!grad)
+        return launch_step_l2<float, false>(x_adv, nullptr, x_clean, shadow_bf16, batch, per_sample, (int)chunks, gamma, radius, dist,
+                                            workspace, gnorm_out, dnorm_out, st);
+    if (grad_dtype == AFAN_F32)
+        return launch_step_l2<float, true>(x_adv, grad, x_clean, shadow_bf16, batch, per_sample, (int)chunks, gamma, radius, dist,
+                                           workspace, gnorm_out, dnorm_out, st);
+    return launch_step_l2<uint16_t, true>(x_adv, grad, x_clean, shadow_bf16, batch, per_sample, (int)chunks, gamma, radius, dist,
+                                          workspace, gnorm_out, dnorm_out, st);
 }
 
 int afan_axpy_noise(float* x_adv, const float* u, int64_t n, float eps, uint16_t* shadow_bf16,

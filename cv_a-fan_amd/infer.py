@@ -268,9 +268,15 @@ class Attacker:
     normalisation's 1 / std and the sign step.  The whole attack (steps x (forward, loss, backward, step), the clamp, the final
     forward, loss and accuracy) is ONE hipGraph per batch shape, captured on the shape's second sight; nothing synchronises with the
     host.  Everything else (fp32, NCHW, another criterion, Bottleneck networks) runs attack_eager(): the same schedule through the
-    model's own eval-mode autograd (resnet_s._BNEvalFn), which the fused path equals bit for bit."""
+    model's own eval-mode autograd (resnet_s._BNEvalFn), which the fused path equals bit for bit.
 
-    def __init__(self, model, criterion, eps, gamma, steps, randinit=False):
+    norm="l2": the same schedule under the L2 threat model — normalised-gradient steps projected onto the L2 ball of radius eps
+    (pgd.step(norm="l2"), three launches inside the same graph), the host draws a Gaussian direction for the random start
+    (pgd.start); eps and gamma are L2 lengths in the same pixel units.  norm="linf" (the default) is the attack described above."""
+
+    def __init__(self, model, criterion, eps, gamma, steps, randinit=False, norm="linf"):
+        pgd._check_norm(norm)
+        self.norm = norm
         self.model, self.criterion = model, criterion
         self.eps, self.gamma, self.steps, self.randinit = float(eps), float(gamma), int(steps), bool(randinit)
         self.ev = evaluator_for(model, criterion)
@@ -354,11 +360,11 @@ class Attacker:
         return ops.affine_relu_backward(gx.float().contiguous(), None, self.inv_std, False)[0]
 
     def _fused_attack(self, x, target, u):
-        x, x_adv = pgd.start(x, self.eps, self.randinit, u)
+        x, x_adv = pgd.start(x, self.eps, self.randinit, u, norm=self.norm)
         for _ in range(self.steps):
             logits, saved = self._forward(x_adv)
             _, dlogits = ops.cross_entropy(logits, target)
-            pgd.step(x_adv, self._backward(dlogits, saved), self.gamma, x, self.eps, True)
+            pgd.step(x_adv, self._backward(dlogits, saved), self.gamma, x, self.eps, True, norm=self.norm)
         pgd.clamp01_(x_adv)
         out = self.ev._forward(x_adv)
         return x_adv, self.criterion(out, target).float(), accuracy(out.float(), target)
@@ -367,11 +373,11 @@ class Attacker:
     def attack_eager(self, inp, target, u=None):
         """The same schedule through the model's own eval-mode forward and autograd (any dtype, layout and criterion)."""
         m = self.model
-        x, x_adv = pgd.start(inp.detach().float().contiguous(), self.eps, self.randinit, u)
+        x, x_adv = pgd.start(inp.detach().float().contiguous(), self.eps, self.randinit, u, norm=self.norm)
         crit = resnet_s.fused_criterion(self.criterion, m)
         loss_of = lambda t: crit(m(t, end_point=m.layer_number, start_point=0), target)
         for _ in range(self.steps):
-            pgd.ascend(x_adv, loss_of, self.gamma, x, self.eps, True)
+            pgd.ascend(x_adv, loss_of, self.gamma, x, self.eps, True, norm=self.norm)
         pgd.clamp01_(x_adv)
         with torch.no_grad():
             out = m(x_adv, end_point=m.layer_number, start_point=0)
@@ -385,7 +391,9 @@ class Attacker:
             raise ops.AfanLibraryError("Attacker.attack: images [N, 3, H, W] on the MI355X")
         x = inp.detach().float().contiguous()
         # the host draws the random start (the reference's attack_algo.py:44), whichever path runs
-        u = torch.rand(x.shape).to(x.device, non_blocking=True) if self.randinit else None
+        # (uniform for the L-inf box, a Gaussian direction for the L2 sphere)
+        draw = torch.randn if self.norm == "l2" else torch.rand
+        u = draw(x.shape).to(x.device, non_blocking=True) if self.randinit else None
         if not self.fused:
             return self.attack_eager(x, target, u)
         with torch.no_grad():

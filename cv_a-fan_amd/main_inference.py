@@ -2,8 +2,10 @@
 (flags :28-32, main :38-53, validate :57-96), so `bash cmd/run_test.sh` works.  Additions (all optional): --arch, --dtype,
 --layout, --synthetic, and robust accuracy: --attack_steps N (> 0: after the clean pass, an N-step L-inf PGD on every test image
 through the eval-mode model, infer.Attacker; `Robust:` lines in the format of the `Test:` lines and a final `robust_accuracy` line),
---attack_eps, --attack_gamma (radius and step size in /255 pixel units), --attack_randinit.  --attack_steps 0 (the default) is the
-clean evaluation alone, its output unchanged.
+--attack_eps, --attack_gamma (radius and step size in /255 pixel units), --attack_randinit, --attack_norm {linf,l2} (the threat
+model; l2: normalised-gradient steps projected onto the L2 ball, eps and gamma are L2 lengths in the same /255 units, so the usual
+CIFAR-10 L2 setting eps = 0.5 is --attack_eps 127.5).  --attack_steps 0 (the default) is the clean evaluation alone, its output
+unchanged.
 
 The checkpoint's `state_dict` is a main_perturb.py checkpoint's or one in the reference's layout (the same keys).  The
 CIFAR-10 test split is evaluated in file order with its last partial batch; the evaluation is cls_entry.validate
@@ -37,13 +39,18 @@ parser.add_argument("--attack_steps", type=int, default=0, help="PGD steps of th
 parser.add_argument("--attack_eps", type=float, default=8.0, help="L-inf radius of the attack, in /255 pixel units")
 parser.add_argument("--attack_gamma", type=float, default=2.0, help="PGD step size, in /255 pixel units")
 parser.add_argument("--attack_randinit", action="store_true", help="start the attack at a uniform random point of the eps-ball")
+parser.add_argument("--attack_norm", choices=("linf", "l2"), default="linf",
+                    help="threat model of the attack; l2: --attack_eps and --attack_gamma are L2 lengths, still in /255 pixel units "
+                         "(eps = 0.5 is --attack_eps 127.5), and --attack_randinit starts on the eps-sphere")
 
 
 def robust_validate(val_loader, model, criterion, args, log):
     """The robust counterpart of cls_entry.validate: every batch attacked (infer.Attacker), the adversarial loss and precision
     kept on the device and read back at --print_freq batches and at the end, in batch order."""
     model.eval()
-    at = infer.Attacker(model, criterion, args.attack_eps / 255.0, args.attack_gamma / 255.0, args.attack_steps, args.attack_randinit)
+    norm = getattr(args, "attack_norm", "linf")
+    how = {} if norm == "linf" else {"norm": norm}          # (the L-inf attack is constructed as it always was)
+    at = infer.Attacker(model, criterion, args.attack_eps / 255.0, args.attack_gamma / 255.0, args.attack_steps, args.attack_randinit, **how)
     at.refresh()
     return cls_entry.evaluate(val_loader, lambda inp, target: at.attack(inp, target)[1:], "Robust", "robust_accuracy", args, log)
 

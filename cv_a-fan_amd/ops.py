@@ -349,6 +349,40 @@ def perturb_norms(x_adv, x_clean):
     return out[0], out[1]
 
 
+def pgd_step_l2_(x_adv, grad, gamma, x_clean=None, eps=0.0, clip=False, shadow=None, want_norms=False):
+    """In place, per sample (x_adv[b], any dense layout): x_adv += gamma * grad / ||grad||_2 [then the projection onto the L2 ball of
+    radius eps around x_clean: a sample outside is rescaled, one inside keeps its bits].  grad=None: the projection alone.  A
+    deterministic chain of three launches (afan_pgd_step_l2), capturable.  want_norms (needs x_clean): returns (x_adv, gnorm, dnorm),
+    the per-sample gradient norm and final perturbation norm as the launches computed them."""
+    lib = _lib.load()
+    _need(x_adv, "x_adv", torch.float32)
+    if grad is not None:
+        _need(grad, "grad")
+        if grad.dtype not in _DT or grad.numel() != x_adv.numel():
+            raise TypeError("grad must be fp32/bf16 with x_adv's number of elements")
+    if clip or want_norms:
+        _need(x_clean, "x_clean", torch.float32)
+        if x_clean.numel() != x_adv.numel():
+            raise ValueError("x_clean must match x_adv")
+    else:
+        x_clean = None
+    if shadow is not None:
+        _need(shadow, "shadow", torch.bfloat16)
+    if x_adv.dim() < 1:
+        raise ValueError("x_adv must have a batch dimension")
+    _same_layout(x_adv, grad, x_clean, shadow)
+    batch = x_adv.shape[0]
+    per = x_adv.numel() // max(batch, 1)
+    out = torch.empty(2, batch, dtype=torch.float32, device=x_adv.device) if want_norms else None
+    if x_adv.numel():
+        ws = _workspace(x_adv, lib.afan_pgd_step_l2_workspace_floats(batch, per), "l2_step")
+        check(lib.afan_pgd_step_l2(_ptr(x_adv), _ptr(grad), _DT[grad.dtype] if grad is not None else 0, _ptr(x_clean), _ptr(shadow),
+                                   batch, per, float(gamma), float(eps), int(bool(clip)), _ptr(ws),
+                                   _ptr(out[0]) if want_norms else None, _ptr(out[1]) if want_norms else None, _stream(x_adv)),
+              "afan_pgd_step_l2")
+    return (x_adv, out[0], out[1]) if want_norms else x_adv
+
+
 def axpy_noise_(x_adv, u, eps, shadow=None):
     """In place: x_adv += (2u-1)*eps with host-drawn u already uploaded."""
     lib = _lib.load()

@@ -80,6 +80,40 @@ int afan_pgd_step_norms(float* x_adv, const void* grad, int grad_dtype, const fl
 int afan_perturb_norms(const float* x_adv, const float* x_clean, int64_t batch, int64_t per_sample,
                        float* partial, float* l2_out, float* linf_out, afan_stream_t stream);
 
+/* L2 PGD step: the gradient normalised per sample, then the projection onto the L2 ball of radius eps around x_clean — the step that
+ * goes with the reference's l2ball_proj (Classification/attack_algo.py:21-33 and its twins under Segmentation/ and Detection/,
+ * which no reference code calls).  Sample b is the contiguous block of per_sample elements at b * per_sample, whatever the
+ * tensor's layout.  Per sample, one correctly rounded fp32 operation per line, no FMA contraction:
+ *   Sg = sum(g_i * g_i)                        g: the fp32 gradient, or the bf16 gradient widened (exact)
+ *   ng = sqrt(Sg)
+ *   ng == 0: x_new_i = x_adv_i (same bits);  else  a = gamma / ng,  p_i = a * g_i,  x_new_i = x_adv_i + p_i
+ *   clip:  d_i = x_new_i - x_clean_i   (x_new as it is stored, fp32),  Sd = sum(d_i * d_i),  nd = sqrt(Sd)
+ *          nd > eps:  s = eps / nd,  q_i = d_i * s,  x_adv_i = x_clean_i + q_i;   otherwise x_adv_i = x_new_i, not rescaled
+ * The two differences from l2ball_proj as written: a sample inside the ball keeps its bits (the reference rounds it through
+ * / dist * dist), and a zero perturbation stays zero (the reference computes 0 / 0 = NaN).  A NaN in a sample's gradient makes that
+ * sample NaN through the lines above (ng = NaN is not 0) and no other.  nd = NaN is not > eps: the sample is not rescaled.
+ * grad == NULL: the projection alone (x_new = x_adv, grad_dtype ignored) — the library's l2ball_proj.
+ * shadow_bf16 (nullable): the bf16 (RNE) copy of the final x_adv.  gnorm_out, dnorm_out (nullable, [batch] fp32): ng (0 when
+ * grad == NULL) and the final perturbation norm, nd or eps where the sample was projected; dnorm_out without clip needs x_clean
+ * and reports nd of the un-projected iterate.
+ * Sums: a thread adds its products in index order over its 4096-element chunk of the sample (16 of them), then the 64-lane
+ * butterfly, the block's 4 wave sums in order: one fp32 partial per chunk in `workspace`
+ * (afan_pgd_step_l2_workspace_floats(batch, per_sample) floats).  Every workgroup of the next launch adds its sample's partials
+ * again (a thread's chain over ceil(chunks / 256) of them, butterfly, 4 waves): no float atomics, the same bits on every run.
+ * Three launches on `stream` (two without clip and dnorm_out, two with grad == NULL), algorithmic HBM bytes per element with an
+ * fp32 gradient:  1. partial Sg: 4 (read g);  2. step, shadow, partial Sd: 18 (read x_adv, g, x_clean; write x_adv 4, shadow 2);
+ * 3. projection: 14 (read x_adv, x_clean; write x_adv, shadow) for the samples outside the ball, whose workgroups are the only ones
+ * that pass the test — inside, launch 2 already wrote the final values.  36 in all against afan_pgd_step's 18.
+ * Errors: batch == 0 or per_sample == 0 returns 0 without a launch; a negative size, or more than 2^31 - 1 chunks, AFAN_ESHAPE;
+ * x_adv or workspace NULL, clip (or dnorm_out) without x_clean AFAN_ENULL; a grad_dtype other than AFAN_F32 / AFAN_BF16 with a
+ * gradient AFAN_EDTYPE; a pointer not aligned to its element AFAN_EALIGN.  16-byte aligned tensors (shadow: 8) with per_sample a
+ * multiple of 4 (bf16 gradient: 8) take the 16-byte body, anything else the scalar one.  No allocation, no synchronisation. */
+int64_t afan_pgd_step_l2_workspace_floats(int64_t batch, int64_t per_sample);
+int afan_pgd_step_l2(float* x_adv, const void* grad, int grad_dtype, const float* x_clean,
+                     uint16_t* shadow_bf16, int64_t batch, int64_t per_sample,
+                     float gamma, float eps, int clip, float* workspace,
+                     float* gnorm_out, float* dnorm_out, afan_stream_t stream);
+
 /* Random start.  Replaces attack_algo.py:42-44:  x_adv += (2.0*u - 1.0) * eps  with u ~ U[0,1) drawn by
  * the caller on the HOST generator (the reference draws it on the CPU, so parity needs the host's
  * stream of numbers) and uploaded to `u`.  Rounding: fl(fl(fl(2u)-1)*eps) then one add, no FMA.
