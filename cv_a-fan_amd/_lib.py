@@ -40,6 +40,8 @@ SIGNATURES = {
     "afan_head_forward": (_i, [_p, _i, _l, _l, _l, _p, _p, _l, _p, _p, _p]),
     "afan_head_backward": (_i, [_p, _p, _p, _l, _l, _l, _l, _p, _i, _p, _p, _i, _p]),
     "afan_cross_entropy": (_i, [_p, _p, _l, _l, _p, _p, _p]),
+    "afan_head_ce": (_i, [_p, _p, _i, _l, _l, _l, _p, _p, _p, _l, _p, _f, _p, _p, _p, _p, _p, _p, _p]),
+    "afan_loss_mean": (_i, [_p, _l, _p, _p]),
     "afan_mix_w_workspace_floats": (_l, []),
     "afan_mix_w": (_i, [_p, _p, _p, _p, _i, _l, _p]),
     "afan_mix_w_backward": (_i, [_p, _i, _p, _p, _l, _p, _p, _i, _p]),
@@ -53,6 +55,8 @@ SIGNATURES = {
     "afan_bn_train_forward_acc_dual": (_i, [_p, _p, _p, _i, _l, _l, _l, _f, _f, _p, _p, _p, _p, _p, _p, _p, _f, _f, _p, _p, _p, _p,
                                             _p, _p, _p, _p]),
     "afan_bn_backward_acc": (_i, [_p, _p, _p, _p, _p, _i, _l, _l, _l, _p, _i, _p, _i, _p, _p, _i, _i, _p]),
+    "afan_bn_backward_rows": (_i, [_p, _p, _p, _p, _p, _i, _l, _l, _l, _p, _p, _p, _p, _i, _p]),
+    "afan_bn_backward_acc_rows": (_i, [_p, _p, _p, _p, _p, _i, _l, _l, _l, _p, _p, _p, _p, _i, _p]),
     "afan_bn_stats": (_i, [_p, _i, _i, _l, _l, _l, _f, _f, _p, _p, _p, _p, _p, _p]),
     "afan_bn_train_forward": (_i, [_p, _p, _p, _i, _i, _l, _l, _l, _f, _f, _p, _p, _i, _p, _p, _p, _p, _p, _p]),
     "afan_bn_apply": (_i, [_p, _p, _p, _i, _i, _l, _l, _l, _p, _p, _p, _p, _i, _p, _p]),

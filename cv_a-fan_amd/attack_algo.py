@@ -53,7 +53,7 @@ def l2ball_proj(center, radius, t, in_place=True):
 
 
 def PGD(x, loss_fn, y=None, model=None, steps=3, gamma=None, start_idx=1, layer_number=16, eps=(2 / 255),
-        randinit=False, clip=False, with_norms=False, grad0=None, norm="linf"):
+        randinit=False, clip=False, with_norms=False, grad0=None, norm="linf", tail_end=False):
     """K-step sign-gradient ascent on the feature map `x` (attack_algo.py:38-58).  norm="l2" (an addition): the steps are
     normalised-gradient steps and the projection is onto the L2 ball (pgd.step(norm="l2")); the random start is pgd.start's.
 
@@ -61,6 +61,8 @@ def PGD(x, loss_fn, y=None, model=None, steps=3, gamma=None, start_idx=1, layer_
     (an addition) fuses the per-sample L2/Linf perturbation norms into the last step; read them with
     `last_norms()`.  `grad0` (an addition; not with randinit): a positive multiple of d(loss)/d(x) at x itself, already
     computed by the caller — the first ascent step uses it instead of running the tail on x (sign() ignores the scale).
+    `tail_end=True` (an addition): the caller allows the one-launch end of each tail pass (resnet_s._HeadCEFn) where the model and
+    the criterion take it; the default keeps the separate launches, and with them the bits of every schedule that does not ask.
     """
     if x.device.type != "cuda":
         raise ops.AfanLibraryError("PGD: x must live on the MI355X (no CPU path in this build)")
@@ -84,13 +86,18 @@ def PGD(x, loss_fn, y=None, model=None, steps=3, gamma=None, start_idx=1, layer_
         ops.axpy_noise_(x_adv, torch.rand(x_adv.shape).to(x.device, non_blocking=True), eps, shadow)
     l2 = linf = None
     loss_fn = fused_criterion(loss_fn, model)
+    # the library's own criterion on a model that takes the target: head, loss gradient and the last BatchNorm's sums in one launch,
+    # no loss value (only the gradient is used here)
+    ce_kw = {}
+    if tail_end and getattr(model, "_afan_tail_end", False) and getattr(loss_fn, "_afan_fused", False) and isinstance(y, torch.Tensor):
+        ce_kw = {"ce_target": y, "ce_root": ops.one(x.device), "ce_value": False}
     for t in range(steps):
         if t == 0 and grad0 is not None:
             grad = grad0
         else:
             # the tail consumes the bf16 shadow written by the previous step's kernel (no separate cast)
             xin = (shadow if lp else x_adv).detach().requires_grad_(True)
-            grad = pgd.input_gradient(lambda t: loss_fn(model(t, end_point=layer_number, start_point=start_idx), y), xin)
+            grad = pgd.input_gradient(lambda t: loss_fn(model(t, end_point=layer_number, start_point=start_idx, **ce_kw), y), xin)
         if with_norms and t == steps - 1:
             l2, linf = pgd.step(x_adv, grad, gamma, x, eps, clip, shadow, norms=True, norm=norm)
         else:

@@ -701,6 +701,31 @@ int afan_bn_backward_acc(const void* dy, const void* x, const void* y, void* dx,
     return e ? e : afan_nhwc::bwd_acc(r);
 }
 
+int afan_bn_backward_rows(const void* dy_rows, const void* x, const void* y, void* dx, void* d_residual, int dtype, int64_t n,
+                          int64_t c, int64_t hw, const float* save_stats, float* workspace, float* dweight, float* dbias,
+                          int accumulate, afan_stream_t stream) {
+    BnBwd r = request<BnBwd>(dtype, n, c, hw, /*relu*/ 1, stream);
+    r.dy = dy_rows; r.x = x; r.y = y; r.dx = dx; r.dres = d_residual;
+    r.stats = save_stats; r.ws = workspace;
+    r.dy_rows = 1;
+    r.dweight = dweight; r.dbias = dbias; r.accumulate = accumulate;
+    const int e = check(r, AFAN_NHWC, {dy_rows, x, y, dx, d_residual, save_stats, workspace}, {dy_rows, x, dx, y, d_residual});
+    return e ? e : afan_nhwc::bwd(r);
+}
+
+int afan_bn_backward_acc_rows(const void* dy_rows, const void* x, const void* y, void* dx, void* d_residual, int dtype,
+                              int64_t n, int64_t c, int64_t hw, const float* save_stats, double* acc, float* dweight,
+                              float* dbias, int accumulate, afan_stream_t stream) {
+    BnBwd r = request<BnBwd>(dtype, n, c, hw, /*relu*/ 1, stream);
+    r.dy = dy_rows; r.x = x; r.y = y; r.dx = dx; r.dres = d_residual;
+    r.stats = save_stats; r.acc = acc;
+    r.src = BnSource::AccReady;
+    r.dy_rows = 1;
+    r.dweight = dweight; r.dbias = dbias; r.accumulate = accumulate;
+    const int e = check(r, AFAN_NHWC, {dy_rows, x, y, dx, d_residual, save_stats, acc}, {dy_rows, x, dx, y, d_residual}, true, {acc});
+    return e ? e : afan_nhwc::bwd_acc(r);
+}
+
 
 int afan_normalize_nchw(const float* x, void* y, int out_dtype, int out_layout, int64_t n, int64_t c, int64_t hw,
                         const float* mean, const float* std, afan_stream_t stream) {

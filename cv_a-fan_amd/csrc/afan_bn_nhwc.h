@@ -56,6 +56,7 @@ struct BnBwd : BnReq {
     double* acc = nullptr;
     float *dweight = nullptr, *dbias = nullptr;
     int accumulate = 0;
+    int dy_rows = 0;                            // 1 (Slab or AccReady, one group): dy is one [C] row per image, the same at each of its hw positions
 };
 
 // f(T{}) with T the storage type of `dtype` (AFAN_F32: float, else bf16 bits)

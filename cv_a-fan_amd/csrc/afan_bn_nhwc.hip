@@ -328,11 +328,14 @@ __global__ __launch_bounds__(BLOCK) void apply_generic_kernel(const T* __restric
 }
 
 // ---- backward 1: partial sums of g and g*xhat -------------------------------------------------------------
-template <typename T, int VEC, bool RELU, bool HAVE_Y, bool ATOMIC = false>
+// ROWS (here and in bwd_apply_kernel): dy holds one [C] row per image, the same at each of the image's pixels (the classifier head's
+// gradient): vector v of the map reads vector (v / img_vec) * CV + v % CV of dy, img_vec = hw * CV.  Same terms in the same order as
+// with the map written out, so the same bits.
+template <typename T, int VEC, bool RELU, bool HAVE_Y, bool ATOMIC = false, bool ROWS = false>
 __global__ __launch_bounds__(BLOCK) void bwd_reduce_kernel(const T* __restrict__ dy, const T* __restrict__ x,
                                                            const T* __restrict__ y, int64_t nvec, int CV, int C,
                                                            const float* __restrict__ stats, float* __restrict__ ws,
-                                                           double* __restrict__ accd = nullptr, int NS = 1) {
+                                                           double* __restrict__ accd = nullptr, int NS = 1, int img_vec = 0) {
     const int c0 = (threadIdx.x % CV) * VEC;
     float mu[VEC], alpha[VEC], beta[VEC];
     ld_coef<VEC>(stats, c0, mu);
@@ -348,7 +351,8 @@ __global__ __launch_bounds__(BLOCK) void bwd_reduce_kernel(const T* __restrict__
 #pragma unroll 2
     for (int64_t v = (int64_t)blockIdx.x * BLOCK + threadIdx.x; v < nvec; v += stride) {
         float d[VEC], e[VEC], o[VEC];
-        LdV<T, VEC>::ld(dy + v * VEC, d);
+        if constexpr (ROWS) LdV<T, VEC>::ld(dy + ((int64_t)((uint32_t)v / (uint32_t)img_vec) * CV + threadIdx.x % CV) * VEC, d);   // (nvec < 2^31: host)
+        else LdV<T, VEC>::ld(dy + v * VEC, d);
         LdV<T, VEC>::ld(x + v * VEC, e);
         if (RELU && HAVE_Y) LdV<T, VEC>::ld(y + v * VEC, o);
 #pragma unroll
@@ -406,12 +410,12 @@ __global__ __launch_bounds__(BLOCK) void bwd_reduce_generic_kernel(const T* __re
 }
 
 // ---- backward 2: dx = g*alpha + (x-mean)*B + D (+ d_residual = g) ---------------------------------------------
-template <typename T, int VEC, bool RELU, bool HAVE_Y, bool DRES>
+template <typename T, int VEC, bool RELU, bool HAVE_Y, bool DRES, bool ROWS = false>
 __global__ __launch_bounds__(BLOCK) void bwd_apply_kernel(const T* __restrict__ dy, const T* __restrict__ x,
                                                           const T* __restrict__ y, T* __restrict__ dx,
                                                           T* __restrict__ dres, int64_t nvec, int CV, int C,
                                                           const float* __restrict__ stats,
-                                                          const float* __restrict__ coef) {
+                                                          const float* __restrict__ coef, int img_vec = 0) {
     const int c0 = (threadIdx.x % CV) * VEC;
     float mu[VEC], alpha[VEC], beta[VEC], B[VEC], D[VEC];
     ld_coef<VEC>(stats, c0, mu);
@@ -423,7 +427,8 @@ __global__ __launch_bounds__(BLOCK) void bwd_apply_kernel(const T* __restrict__ 
 #pragma unroll 4
     for (int64_t v = (int64_t)blockIdx.x * BLOCK + threadIdx.x; v < nvec; v += stride) {
         float d[VEC], e[VEC], o[VEC];
-        LdV<T, VEC>::ld(dy + v * VEC, d);
+        if constexpr (ROWS) LdV<T, VEC>::ld(dy + ((int64_t)((uint32_t)v / (uint32_t)img_vec) * CV + threadIdx.x % CV) * VEC, d);
+        else LdV<T, VEC>::ld(dy + v * VEC, d);
         LdV<T, VEC>::ld(x + v * VEC, e);
         if (RELU && HAVE_Y) LdV<T, VEC>::ld(y + v * VEC, o);
 #pragma unroll
@@ -691,14 +696,16 @@ __global__ __launch_bounds__(BLOCK) void apply_acc_dual_kernel(const T* __restri
 
 // backward: acc[slot][0][c] = sum g, acc[slot][1][c] = sum g*(x - mean) (f64) -> B, D per channel, same block-level
 // prologue; block 0 writes dweight / dbias.
-template <typename T, int VEC, bool RELU, bool HAVE_Y, bool DRES, bool GROUPED>
+// ROWS: dy holds one [C] row per image (the classifier head's gradient, the same at every pixel of the image): vector v of the map reads
+// vector (v / img_vec) * CV + v % CV of dy, img_vec = hw * CV vectors per image; everything else is the same expression.
+template <typename T, int VEC, bool RELU, bool HAVE_Y, bool DRES, bool GROUPED, bool ROWS = false>
 __global__ __launch_bounds__(BLOCK) void bwd_apply_acc_kernel(const T* __restrict__ dy, const T* __restrict__ x,
                                                               const T* __restrict__ y, T* __restrict__ dx,
                                                               T* __restrict__ dres, int64_t nvec, int CV, int C, int NS,
                                                               const float* __restrict__ stats,
                                                               const double* __restrict__ acc, double inv_m,
                                                               float* dweight, float* dbias, int accumulate,
-                                                              int64_t acc_stride) {
+                                                              int64_t acc_stride, int img_vec = 0) {
     // gridDim.y = image groups, as in apply_acc_kernel; block (0, 0) alone adds every group's sums to dweight / dbias
     extern __shared__ __attribute__((aligned(16))) float coef[];   // [2][C]: B | D
     const int grp = GROUPED ? blockIdx.y : 0, G = GROUPED ? gridDim.y : 1;
@@ -760,7 +767,8 @@ __global__ __launch_bounds__(BLOCK) void bwd_apply_acc_kernel(const T* __restric
 #pragma unroll 4
     for (int64_t v = (int64_t)blockIdx.x * BLOCK + threadIdx.x; v < nvec; v += stride) {
         float d[VEC], e[VEC], o[VEC];
-        LdV<T, VEC>::ld(dy + v * VEC, d);
+        if constexpr (ROWS) LdV<T, VEC>::ld(dy + ((int64_t)((uint32_t)v / (uint32_t)img_vec) * CV + threadIdx.x % CV) * VEC, d);   // (nvec < 2^31: host)
+        else LdV<T, VEC>::ld(dy + v * VEC, d);
         LdV<T, VEC>::ld(x + v * VEC, e);
         if (RELU && HAVE_Y) LdV<T, VEC>::ld(y + v * VEC, o);
 #pragma unroll
@@ -899,9 +907,16 @@ int backward(const BnBwd& r) {
     float* coef = r.ws + (int64_t)2 * C * MAX_G;  // [2][C] after the partials (16-byte aligned: C*MAX_G*8 bytes)
     const float* red = r.ws;
     int red_g = p.G;
+    // dy as one row per image (the end of a tail pass: stored ReLU mask, shortcut share wanted): the vector kernels' own order
+    const bool rows = r.dy_rows != 0;
+    const int img_vec = rows ? (int)(r.hw * p.CV) : 0;
+    if (rows && (r.src != BnSource::Slab || !p.vec || !r.relu || !r.y || !r.dres || p.nvec >= ((int64_t)1 << 31))) return AFAN_ESHAPE;
     if (r.src == BnSource::ConvPartials) {   // the producing dgrad's epilogue already took the sums
         red = r.partials;
         red_g = (int)r.partials_g;
+    } else if (rows) {
+        AFAN_PROF("bn_nhwc_bwd_reduce_kernel", p.tensor_bytes * 2, st);
+        bwd_reduce_kernel<T, NV, true, true, false, true><<<p.G, BLOCK, 0, st>>>(dy_, x_, y_, p.nvec, p.CV, (int)C, r.stats, r.ws, nullptr, 1, img_vec);
     } else {
         AFAN_PROF("bn_nhwc_bwd_reduce_kernel", p.tensor_bytes * (2 + mask_reads(r)), st);
         with_mask(r.relu, r.y, [&](auto RELU, auto HY) {
@@ -919,7 +934,8 @@ int backward(const BnBwd& r) {
     AFAN_LAUNCH_CHECK();
     const int grid = apply_grid(p, M * C);
     AFAN_PROF("bn_nhwc_bwd_apply_kernel", p.tensor_bytes * (3 + mask_reads(r) + (r.dres ? 1 : 0)), st);
-    with_mask(r.relu, r.y, [&](auto RELU, auto HY) { with_flag(r.dres, [&](auto DR) {
+    if (rows) bwd_apply_kernel<T, NV, true, true, true, true><<<grid, BLOCK, 0, st>>>(dy_, x_, y_, dx_, dres_, p.nvec, p.CV, (int)C, r.stats, coef, img_vec);
+    else with_mask(r.relu, r.y, [&](auto RELU, auto HY) { with_flag(r.dres, [&](auto DR) {
         if (p.vec) bwd_apply_kernel<T, NV, RELU(), HY(), DR()><<<grid, BLOCK, 0, st>>>(dy_, x_, y_, dx_, dres_, p.nvec, p.CV, (int)C, r.stats, coef);
         else bwd_apply_generic_kernel<T, RELU(), HY(), DR()><<<grid, BLOCK, 0, st>>>(dy_, x_, y_, dx_, dres_, M * C, (int)C, r.stats, coef);
     }); });
@@ -1002,6 +1018,17 @@ int backward_acc(const BnBwd& r) {
     const T* dy_ = (const T*)r.dy; const T* x_ = (const T*)r.x; const T* y_ = (const T*)r.y;
     T* dx_ = (T*)r.dx; T* dres_ = (T*)r.dres;
     const int NS = acc_slots(C);
+    if (r.dy_rows) {
+        // the end of a tail pass: the last block's BatchNorm (stored ReLU mask, shortcut share wanted) under the classifier head, whose
+        // gradient is one row per image; the head's launch took the sums (afan_head_ce)
+        if (!ready || groups != 1 || !r.relu || !r.y || !r.dres || p.nvec >= ((int64_t)1 << 31)) return AFAN_ESHAPE;
+        AFAN_PROF("bn_nhwc_bwd_apply_kernel", p.tensor_bytes * 4, st);
+        bwd_apply_acc_kernel<T, NV, true, true, true, false, true><<<apply_grid(p, M * C), BLOCK, (size_t)2 * C * sizeof(float), st>>>(
+            dy_, x_, y_, dx_, dres_, p.nvec, p.CV, (int)C, NS, r.stats, r.acc, 1.0 / (double)M, r.dweight, r.dbias, r.accumulate,
+            (acc_doubles(C) + 1) & ~(int64_t)1, (int)(r.hw * p.CV));
+        AFAN_LAUNCH_CHECK();
+        return AFAN_OK;
+    }
     if (!ready) {
         AFAN_PROF("bn_nhwc_bwd_reduce_kernel", p.tensor_bytes * (2 + mask_reads(r)), st);
         with_mask(r.relu, r.y, [&](auto RELU, auto HY) {

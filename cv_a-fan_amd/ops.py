@@ -23,7 +23,8 @@ class _Calls(dict):
     """The convolution counters are the dict's own items: what the logs and the tests enumerate (`dict(CALLS)`, `set(CALLS)`).
     Counters of launches outside the convolution path (`batch_crop_flip`, `seg_batch_aug`, `seg_batch_aug_jitter`, `det_batch_resize`:
     the loaders' kernels; `seg_confusion`:
-    validation's scoring kernel; `sat_points`: the layer-wise SAT evaluation's one-launch points) live in `.other` and are read and
+    validation's scoring kernel; `sat_points`: the layer-wise SAT evaluation's one-launch points; `head_ce`: the one-launch end of a
+    tail pass) live in `.other` and are read and
     written through the same subscript, `in` and `.get`, so that the enumerated table stays the convolution table
     (tests/test_host_logic.py::test_no_convolution_leaves_the_library pins `set(CALLS)` to the six convolution counters)."""
 
@@ -49,7 +50,7 @@ class _Calls(dict):
 
 CALLS = _Calls({"conv_fwd": 0, "conv_dgrad": 0, "conv_wgrad": 0, "conv_general": 0, "vendor_conv": 0, "conv_bn_fused": 0},
                {"batch_crop_flip": 0, "seg_batch_aug": 0, "seg_batch_aug_jitter": 0, "seg_confusion": 0, "det_batch_resize": 0,
-                "frozen_stem_image_grad": 0, "sat_points": 0})
+                "frozen_stem_image_grad": 0, "sat_points": 0, "head_ce": 0})
 
 
 def _need(t, name, dtype=None):
@@ -644,6 +645,52 @@ def head_backward(dlogits, weight, pooled, x_like, want_dx, dweight=None, dbias=
     return dx
 
 
+def head_ce(out, raw, stats, weight, bias, target, root, acc):
+    """The end of a tail pass in one launch (afan_head_ce): head_forward's (logits, pooled) of `out`, cross_entropy's row losses and
+    dlogits (times root: 1.0 or 0.5) against `target`, v [N, C] = head_backward's dx as one row per image, and the backward sums of the
+    BatchNorm that produced out = relu(bn(raw) + shortcut) (stats: its [4, C] block) added into the zeroed accumulator block `acc`
+    (None: no sums; bn_backward takes them from v in its own order).
+    Returns (logits, pooled, loss_row, dlogits, v)."""
+    lib = _lib.load()
+    _cl4(out, "out"), _cl4(raw, "raw")
+    _need(weight, "weight", torch.float32), _need(stats, "stats", torch.float32), _need(target, "target", torch.int64)
+    _same_layout(out, raw)
+    n, c, hw = _nchw(out)
+    k = weight.shape[0]
+    if stats.shape != (4, c) or not stats.is_contiguous() or target.shape != (n,) \
+            or (acc is not None and (acc.dtype != torch.float64 or acc.numel() < acc_block_doubles(c))):
+        raise ValueError("head_ce: stats [4, C], target [N] and one accumulator block of C channels (or None)")
+    dev = out.device
+    pooled = torch.empty(n, c, dtype=torch.float32, device=dev)
+    logits = torch.empty(n, k, dtype=torch.float32, device=dev)
+    loss_row = torch.empty(n, dtype=torch.float32, device=dev)
+    dlogits = torch.empty(n, k, dtype=torch.float32, device=dev)
+    v = torch.empty(n, c, dtype=torch.bfloat16, device=dev)
+    CALLS["head_ce"] += 1
+    check(lib.afan_head_ce(_ptr(out), _ptr(raw), AFAN_BF16, n, c, hw, _ptr(stats), _ptr(weight), _ptr(bias), k, _ptr(target),
+                           float(root), _ptr(pooled), _ptr(logits), _ptr(loss_row), _ptr(dlogits), _ptr(v), _ptr(acc), _stream(out)),
+          "afan_head_ce")
+    return logits, pooled, loss_row, dlogits, v
+
+
+def loss_mean(loss_row):
+    """Mean of head_ce's row losses as a 0-dim tensor, in cross_entropy's summation order (one one-workgroup launch)."""
+    _need(loss_row, "loss_row", torch.float32)
+    loss = torch.empty((), dtype=torch.float32, device=loss_row.device)
+    check(_lib.load().afan_loss_mean(_ptr(loss_row), loss_row.shape[0], _ptr(loss), _stream(loss_row)), "afan_loss_mean")
+    return loss
+
+
+def is_row_broadcast(dy, x):
+    """dy is one contiguous [C] row per image expanded over x's pixels (stride 0): what bn_backward reads without the map."""
+    if dy.dim() != 4 or dy.shape != x.shape or dy.dtype != x.dtype or not dy.is_cuda:
+        return False
+    n, c, h, w = dy.shape
+    sn, sc, sh, sw = dy.stride()
+    return (h * w > 1 and (sh == 0 or h == 1) and (sw == 0 or w == 1) and (sc == 1 or c == 1) and (sn == c or n == 1)
+            and dy.data_ptr() % 16 == 0)
+
+
 # ------------------------------------------------------------------------------------- BatchNorm
 def bn_stats(x, eps=1e-5, momentum=0.1, running_mean=None, running_var=None, num_batches=None):
     """Per-channel batch mean and 1/sqrt(var_biased + eps) (optionally updating running statistics)."""
@@ -891,15 +938,31 @@ def bn_backward(dy, x, y, stats, weight, bias, relu, want_dres, dweight=None, db
     """Returns (dx, d_residual|None). dweight/dbias (fp32 [C]) are written/accumulated when given.
     partials: ConvStats written by the dgrad that produced dy (conv_dgrad(..., bn_bwd=...)): skips the reduction pass."""
     lib = _lib.load()
-    _need(dy, "dy", x.dtype)
+    rows = is_row_broadcast(dy, x)
+    if rows and not ((partials is None or partials.acc is not None) and groups == 1 and relu and y is not None and want_dres
+                     and layout_of(x) == AFAN_NHWC and x.dtype in _DT
+                     and bool(lib.afan_bn_acc_supported(_DT[x.dtype], int(x.shape[1])))):      # (the 16-byte channel mapping)
+        dy, rows = dy.contiguous(memory_format=torch.channels_last), False     # (other forms read the written-out map)
+    if not rows:
+        _need(dy, "dy", x.dtype)
     _need(x, "x")
     if y is not None:
         _need(y, "y", x.dtype)
-    _same_layout(x, dy, y)
+    _same_layout(x, None if rows else dy, y)
     n, c, hw = _nchw(x)
     dx = dx_out if dx_out is not None else torch.empty_like(x)
     dres = (dres_out if dres_out is not None else torch.empty_like(x)) if want_dres else None
     _same_layout(x, dx, dres)
+    if rows and partials is None:          # the slab launches, dy read by rows: bit for bit what the written-out map gives
+        ws = _workspace(x, lib.afan_bn_workspace_floats(c), "bn")
+        check(lib.afan_bn_backward_rows(_ptr(dy), _ptr(x), _ptr(y), _ptr(dx), _ptr(dres), _DT[x.dtype], n, c, hw, _ptr(stats), _ptr(ws),
+                                        _ptr(dweight), _ptr(dbias), int(bool(accumulate)), _stream(x)), "afan_bn_backward_rows")
+        return dx, dres
+    if rows:
+        check(lib.afan_bn_backward_acc_rows(_ptr(dy), _ptr(x), _ptr(y), _ptr(dx), _ptr(dres), _DT[x.dtype], n, c, hw, _ptr(stats),
+                                            _ptr(partials.acc), _ptr(dweight), _ptr(dbias), int(bool(accumulate)), _stream(x)),
+              "afan_bn_backward_acc_rows")
+        return dx, dres
     # stand-alone reductions keep the slab + finalize kernels: their blocks all finish together, so the accumulator
     # atomics would arrive as one burst and serialise per address (measured 2x slower); a dgrad epilogue spreads them
     acc = partials.acc if partials is not None else None

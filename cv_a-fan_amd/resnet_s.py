@@ -679,7 +679,9 @@ def _bwd_last_bn(ctx, gout, bl, raw, out, stats):
     sums, d_raw, sc_done = _GradNote.read(gout, ctx.tail)
     if d_raw is not None:
         return d_raw, gout, sc_done                # the tensor handed back IS the shortcut's share
-    d_raw, dres = _bn_bwd_g(_like_layout(gout, out), raw, out, stats, bl, True, True, ctx.want_pgrad, sums, ctx.G)
+    # (a classifier-head node's gradient is one row per image expanded over the pixels: read as it is, never written out)
+    dy = gout if (getattr(gout, "_afan_rows", False) and ops.is_row_broadcast(gout, out)) else _like_layout(gout, out)
+    d_raw, dres = _bn_bwd_g(dy, raw, out, stats, bl, True, True, ctx.want_pgrad, sums, ctx.G)
     return d_raw, dres, None
 
 
@@ -1225,14 +1227,109 @@ def fused_criterion(criterion, model):
         return criterion
 
     def ce(out, y):
+        done = getattr(out, "_afan_ce", None)
+        if done is not None and done[0] is y:       # logits of a _HeadCEFn node run with this target: its loss, nothing launched
+            return done[1]
         if (out.is_cuda and out.dtype == torch.float32 and out.dim() == 2 and out.is_contiguous() and y.dtype == torch.int64
                 and y.dim() == 1 and 0 < out.numel() <= ops.CE_MAX_ELEMS):
             return _CEFn.apply(out, y)
         return criterion(out, y)
+    ce._afan_fused = True
     return ce
 
 
 _FUSED_HEAD = os.environ.get("AFAN_FUSED_HEAD", "1") != "0"   # 0: pool / flatten / linear as separate torch ops (A/B)
+_TAIL_END = os.environ.get("AFAN_TAIL_END", "1") != "0"       # 0: head, loss and the head's input gradient as launches of their own (A/B)
+# 2: the head launch also takes the last BatchNorm's backward sums (f64 accumulators, per image) and the apply folds them: two launches
+# fewer per pass, but ANOTHER summation order than the slab reduce — same terms, other last bits, which bf16 roundings and then the steps
+# amplify (parameters 2.6e-5 apart after one step).  The default keeps the slab order and with it every bit of the separate launches.
+_TAIL_END_SUMS = os.environ.get("AFAN_TAIL_END", "1") == "2"
+
+
+def _ce_root_value(root, device):
+    """1.0 / 0.5 for the cached root gradients ops.one() / ops.half() (pointer identity: no host read), else None."""
+    if not isinstance(root, torch.Tensor):
+        return None
+    if root.data_ptr() == ops.one(device).data_ptr():
+        return 1.0
+    if root.data_ptr() == ops.half(device).data_ptr():
+        return 0.5
+    return None
+
+
+def _head_ce_ok(x, lin, target, root):
+    """The tail-pass end as one launch (ops.head_ce): x is a block node's bf16 channels-last output of an ungrouped pass whose last
+    BatchNorm's sums can go to an accumulator block, a small classifier, an int64 target, the root gradient one() or half()."""
+    tail = getattr(x, "_afan_tail", None)
+    if not (_TAIL_END and _FUSED_CE and tail is not None and tail.G == 1 and _Flags.bn_groups == 1 and _Flags.block_fusion
+            and torch.is_grad_enabled() and x.requires_grad and _head_ok(x, lin)):
+        return False
+    n, c, hw = x.shape[0], x.shape[1], x.shape[2] * x.shape[3]
+    k = lin.out_features
+    return (x.dtype == torch.bfloat16 and tail.raw.shape == x.shape and tail.raw.dtype == x.dtype and tail.stats.dim() == 2
+            and (ops.bn_acc_ok(x) or not _TAIL_END_SUMS) and c % 8 == 0 and c // 8 <= 256 and 256 % (c // 8) == 0 and hw <= 64 and k <= 16
+            and n * k <= ops.CE_MAX_ELEMS and isinstance(target, torch.Tensor) and target.is_cuda and target.dtype == torch.int64
+            and target.dim() == 1 and target.shape[0] == n and target.is_contiguous()
+            and _ce_root_value(root, x.device) is not None)
+
+
+class _HeadCEFn(torch.autograd.Function):
+    """The classifier head, the cross-entropy against `target` and the head's input gradient (with _TAIL_END_SUMS also the backward sums
+    of the BatchNorm under the head) as ONE forward launch (ops.head_ce): returns (logits, loss).  loss is the mean cross-entropy where `want_value` (one more one-workgroup launch),
+    else an unwritten scalar that only roots the backward (PGD's passes use the gradient alone).  The backward, given the root
+    gradient the node was built for (ops.one() / ops.half(), by pointer as in _CEFn), launches the head's dW only and hands the
+    block node one gradient row per image expanded over the pixels, which its BatchNorm backward reads as rows (the sums, where taken,
+    riding on it: _GradNote's sums form); any other incoming gradient takes the separate launches (head_backward's map)."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, want_pgrad, target, root, want_value):
+        tail = x._afan_tail
+        ctx.set_materialize_grads(False)
+        root_value = _ce_root_value(root, x.device)
+        acc = ops.acc_take(x.device, x.shape[1]) if _TAIL_END_SUMS else None
+        logits, pooled, loss_row, dlogits, v = ops.head_ce(x, tail.raw, tail.stats, weight, bias, target, root_value, acc)
+        loss = ops.loss_mean(loss_row) if want_value else torch.empty((), dtype=torch.float32, device=x.device)
+        ctx.save_for_backward(x, weight, pooled, dlogits, v)
+        ctx.bias, ctx.pg, ctx.acc, ctx.root, ctx.root_value = bias, want_pgrad, acc, root, root_value
+        return logits, loss
+
+    @staticmethod
+    def backward(ctx, g_logits, g_loss):
+        x, weight, pooled, dlogits, v = ctx.saved_tensors
+        bias = ctx.bias
+        want_p = ctx.pg and ctx.needs_input_grad[1]
+        dw = db = None
+        direct = False
+        if want_p:
+            direct = _accumulates_in_place(weight) and (bias is None or _accumulates_in_place(bias))
+            if direct:
+                dw, db = weight.grad, (bias.grad if bias is not None else None)
+            else:
+                dw = torch.empty_like(weight)
+                db = torch.empty_like(bias) if bias is not None else None
+        given = g_logits is None and g_loss is not None and g_loss.data_ptr() == ctx.root.data_ptr()
+        if given:
+            if want_p:
+                ops.head_backward(dlogits, weight, pooled, x, False, dw, db, accumulate=direct)
+            dx = None
+            if ctx.needs_input_grad[0]:
+                n, c = v.shape
+                dx = v.view(n, c, 1, 1).expand(x.shape)
+                dx._afan_rows = True
+                if ctx.acc is not None:
+                    _GradNote.attach(dx, sums=ops.ConvStats(None, 0, None, ctx.acc))
+        else:
+            g = None
+            if g_loss is not None:
+                g = dlogits * (g_loss / ctx.root_value)
+            if g_logits is not None:
+                g = g_logits.float() if g is None else g + g_logits
+            if g is None:
+                return (None,) * 7
+            dx = ops.head_backward(g.contiguous(), weight, pooled, x, ctx.needs_input_grad[0], dw, db, accumulate=direct)
+        if direct:
+            dw = db = None
+        return dx, dw, db, None, None, None, None
 
 
 def _head_ok(x, lin):
@@ -1319,6 +1416,7 @@ class _HeadPool(nn.AdaptiveAvgPool2d):
 class ResNet(nn.Module):
     """Flat-Sequential ResNet with the slice protocol.  `widths`/`option` generalise the reference class
     (16-32-64, option A) to the build-defined ResNet-18-CIFAR (64-128-256-512, option B)."""
+    _afan_tail_end = True          # forward takes ce_target / ce_root / ce_value
 
     def __init__(self, block, num_blocks, num_classes=10, init_weight=1, widths=(16, 32, 64), option="A"):
         super().__init__()
@@ -1365,7 +1463,11 @@ class ResNet(nn.Module):
                 m.out_dtype = dtype
         return self
 
-    def forward(self, x, end_point=34, start_point=0):
+    def forward(self, x, end_point=34, start_point=0, ce_target=None, ce_root=None, ce_value=True):
+        """ce_target (with ce_root = the root gradient the caller will give the loss, ops.one() / ops.half()): the slice ends in the
+        classifier and its logits go to the mean cross-entropy against ce_target — where the shapes allow, head, loss and the backward
+        sums of the BatchNorm under the head run as one launch (_HeadCEFn) and fused_criterion's loss of these logits is that node's;
+        ce_value=False: the loss VALUE is not needed (a gradient-only pass).  Without ce_target nothing changes."""
         layers = list(self.sequential_model[start_point:end_point])
         if self.channels_last and x.dim() == 4 and x.is_floating_point():
             x = x if x.is_contiguous(memory_format=torch.channels_last) else \
@@ -1383,7 +1485,12 @@ class ResNet(nn.Module):
             elif (isinstance(L, _HeadPool) and i + 2 < n and isinstance(layers[i + 1], nn.Flatten)
                   and isinstance(layers[i + 2], nn.Linear) and _head_ok(_head_in(x), layers[i + 2])):
                 lin = layers[i + 2]
-                x = _HeadFn.apply(_head_in(x), lin.weight, lin.bias, _Flags.param_grads)
+                hx = _head_in(x)
+                if ce_target is not None and _head_ce_ok(hx, lin, ce_target, ce_root):
+                    x, loss = _HeadCEFn.apply(hx, lin.weight, lin.bias, _Flags.param_grads, ce_target, ce_root, bool(ce_value))
+                    x._afan_ce = (ce_target, loss)
+                else:
+                    x = _HeadFn.apply(hx, lin.weight, lin.bias, _Flags.param_grads)
                 i += 3
                 continue
             elif isinstance(L, nn.Linear):

@@ -206,6 +206,14 @@ class NullReducer:
         return None
 
 
+def _ce_kwargs(model, crit, target, root):
+    """What a tail pass that ends in `crit(logits, target)`, rooted with `root`, tells the model's slice forward (resnet_s.ResNet.forward's
+    ce_target / ce_root): only a model that takes them, only the library's own fused criterion."""
+    if getattr(model, "_afan_tail_end", False) and getattr(crit, "_afan_fused", False):
+        return {"ce_target": target, "ce_root": root}
+    return {}
+
+
 def _cut_chunks(arena, n_chunks):
     """[start, end, first_param_index) ranges cut at tensor boundaries, roughly equal in size."""
     bounds = arena.offsets + [arena.numel]
@@ -522,8 +530,9 @@ class AfanTrainer(StepTrainer):
         with ops.bn_running_updates(2):                 # main_perturb.py:173 + :196: the head, once for both
             fm_clean = m(inp, end_point=idx, start_point=0)
         xin = fm_clean.detach().requires_grad_(True)
+        ce_kw = _ce_kwargs(m, crit, target, half)       # head, loss and the last BatchNorm's sums as one launch where they can be
         with ops.record_bn_updates() as clean_bn:
-            output_clean = m(xin, end_point=ln, start_point=idx)
+            output_clean = m(xin, end_point=ln, start_point=idx, **ce_kw)
         loss_clean = crit(output_clean, target)
         with resnet_s.stash_wgrad():                    # the tail's weight gradients wait for the adversarial pass's operands
             torch.autograd.backward(loss_clean, grad_tensors=half)
@@ -532,12 +541,12 @@ class AfanTrainer(StepTrainer):
         feature_map = feature_map.float() if feature_map.dtype != torch.float32 else feature_map
         feature_map_adv = PGD(feature_map, self.criterion, y=target, model=m, steps=self.steps,
                               gamma=(self.gamma / 255), start_idx=idx, layer_number=ln, eps=(self.eps / 255),
-                              randinit=False, clip=self.clip, with_norms=True, grad0=g0)
+                              randinit=False, clip=self.clip, with_norms=True, grad0=g0, tail_end=True)
         l2, linf = last_norms()
         adv_in = getattr(feature_map_adv, "_afan_shadow", None)
         if adv_in is None:
             adv_in = feature_map_adv.detach()
-        output_adv = m(adv_in, end_point=ln, start_point=idx)                    # main_perturb.py:195
+        output_adv = m(adv_in, end_point=ln, start_point=idx, **ce_kw)           # main_perturb.py:195
         loss_adv = crit(output_adv, target)
         torch.autograd.backward(loss_adv, grad_tensors=half)    # weight gradients: clean + adversarial operands, one launch
         resnet_s.flush_wgrad(m)
@@ -585,10 +594,12 @@ class AfanTrainer(StepTrainer):
         crit = resnet_s.fused_criterion(self.criterion, m)
         half = ops.half(inp.device)
 
+        ce_kw = _ce_kwargs(m, crit, target, half)
+
         def run_segments(x0):
             ins, outs, h = [x0], [], x0
             for k, (a, b) in enumerate(segs):
-                o = m(h, end_point=b, start_point=a)
+                o = m(h, end_point=b, start_point=a, **(ce_kw if k + 1 == len(segs) else {}))
                 outs.append(o)
                 if k + 1 < len(segs):
                     h = o.detach().requires_grad_(True)
@@ -610,7 +621,7 @@ class AfanTrainer(StepTrainer):
         feature_map = feature_map.float() if feature_map.dtype != torch.float32 else feature_map
         feature_map_adv = PGD(feature_map, self.criterion, y=target, model=m, steps=self.steps,
                               gamma=(self.gamma / 255), start_idx=idx, layer_number=ln, eps=(self.eps / 255),
-                              randinit=False, clip=self.clip, with_norms=True, grad0=g0)
+                              randinit=False, clip=self.clip, with_norms=True, grad0=g0, tail_end=True)
         l2, linf = last_norms()
         adv_in = getattr(feature_map_adv, "_afan_shadow", None)
         if adv_in is None:

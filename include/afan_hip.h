@@ -300,6 +300,19 @@ int afan_bn_backward_acc(const void* dy, const void* x, const void* y, void* dx,
 /* groups = 2 (acc_ready only): x is two concatenated half-batches (n/2 images each) normalised separately in ONE launch:
  * acc holds one accumulator block per half (stride afan_bn_acc_doubles(c) rounded up to even), save_stats is [2][4*c],
  * the running statistics receive the two updates in order (first half, then second), dweight/dbias the sum. */
+/* afan_bn_backward (channels-last, relu = 1, no partials) whose dy is ONE [c] row per image, dy_rows [n][c], the same at each of the
+ * image's hw positions (the classifier head's gradient, afan_head_ce's v): the same launches adding the same terms in the same order,
+ * so every output is bit-equal to afan_bn_backward on the written-out map, which is never made.  y (the stored ReLU mask) and
+ * d_residual are required; channel counts of the 16-byte mapping only (c % 8 == 0 for bf16, 256 % (c / 8) == 0), else AFAN_ESHAPE. */
+int afan_bn_backward_rows(const void* dy_rows, const void* x, const void* y, void* dx, void* d_residual, int dtype, int64_t n,
+                          int64_t c, int64_t hw, const float* save_stats, float* workspace, float* dweight, float* dbias,
+                          int accumulate, afan_stream_t stream);
+/* afan_bn_backward_acc(relu = 1, acc_ready = 1, groups = 1) whose dy is ONE [c] row per image, dy_rows [n][c], the same at each of the
+ * image's hw positions (the classifier head's gradient, afan_head_ce's v, with that launch's sums in acc): same expression and
+ * outputs, the broadcast map is never written.  y (the stored ReLU mask) and d_residual are required. */
+int afan_bn_backward_acc_rows(const void* dy_rows, const void* x, const void* y, void* dx, void* d_residual, int dtype,
+                              int64_t n, int64_t c, int64_t hw, const float* save_stats, double* acc, float* dweight,
+                              float* dbias, int accumulate, afan_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Backbone convolutions (bf16, channels-last, fp32 accumulate on MFMA) — what torch.nn.Conv2d runs inside
@@ -836,6 +849,18 @@ int afan_head_backward(const float* dlogits, const float* weight, const float* p
  * n * k <= 65536 (one workgroup; rows summed in fixed order). */
 int afan_cross_entropy(const float* logits, const int64_t* target, int64_t n, int64_t k, float* loss, float* dlogits,
                        afan_stream_t stream);
+
+/* The end of a tail pass in one launch (256 threads per image): afan_head_forward's pooled / logits, afan_cross_entropy's row terms
+ * (loss_row[r] = logsumexp(logits[r]) - logits[r][target[r]]; dlogits as there, times `root`, the pass's root gradient: 1 or 1/2),
+ * v [n][c] (bf16) = afan_head_backward's dx, one row per image, and the backward sums of the BatchNorm that produced `out`
+ * (out = relu(bn(raw) + shortcut), stats its [4][c] block): g = out > 0 ? v : 0, sum g and sum g * (raw - mean) added into the
+ * zeroed accumulator block acc (double[afan_bn_acc_doubles(c)]) for afan_bn_backward_acc_rows; acc = NULL: no sums (the caller
+ * reduces, afan_bn_backward_rows).  All values bit-equal to the three launches'.  bf16 channels-last maps, c % 8 == 0, 256 % (c / 8) == 0, hw <= 64, k <= afan_head_max_classes(), n * k <= 65536.
+ * afan_loss_mean: loss[0] = mean of loss_row in afan_cross_entropy's summation order (bit-equal), where the value is consumed. */
+int afan_head_ce(const void* out, const void* raw, int dtype, int64_t n, int64_t c, int64_t hw, const float* stats,
+                 const float* weight, const float* bias, int64_t k, const int64_t* target, float root, float* pooled,
+                 float* logits, float* loss_row, float* dlogits, void* v, double* acc, afan_stream_t stream);
+int afan_loss_mean(const float* loss_row, int64_t n, float* loss, afan_stream_t stream);
 
 /* Batched KRSC -> CRSK transpose of every convolution weight of the parameter arena (the dgrad operands `wt`), one
  * launch per SGD step.  desc_dev: device array of n_desc x 8 int64 {src_off, dst_off, K, RS, C, first_tile, dst_RS, rs0}
