@@ -11,7 +11,7 @@ itself (input gradient, sign step) is pgd.py's; PGD keeps its one-launch start a
 import torch
 
 from . import ops, pgd
-from .resnet_s import _dense, _like_layout, fused_criterion
+from .resnet_s import _dense, _like_layout, fused_criterion, tail_end_kwargs
 
 __all__ = ["PGD", "tensor_clamp", "linfball_proj", "l2ball_proj", "mix_feature", "get_sample_points", "last_norms"]
 
@@ -88,9 +88,7 @@ def PGD(x, loss_fn, y=None, model=None, steps=3, gamma=None, start_idx=1, layer_
     loss_fn = fused_criterion(loss_fn, model)
     # the library's own criterion on a model that takes the target: head, loss gradient and the last BatchNorm's sums in one launch,
     # no loss value (only the gradient is used here)
-    ce_kw = {}
-    if tail_end and getattr(model, "_afan_tail_end", False) and getattr(loss_fn, "_afan_fused", False) and isinstance(y, torch.Tensor):
-        ce_kw = {"ce_target": y, "ce_root": ops.one(x.device), "ce_value": False}
+    ce_kw = tail_end_kwargs(model, loss_fn, y, ops.one(x.device), want_value=False) if tail_end else {}
     for t in range(steps):
         if t == 0 and grad0 is not None:
             grad = grad0

@@ -16,37 +16,138 @@ namespace {
 constexpr int BLOCK = 256;
 constexpr int MAXK = 16;      // classes handled with register accumulators; larger heads take the vendor GEMM (caller)
 
+// ---- the arithmetic, each expression once.  head_ce_kernel must give every bit of head_fwd_vec_kernel -> ce_fwd_kernel ->
+// head_bwd_dx_kernel, and loss_mean_kernel every bit of ce_fwd_kernel's mean: they call the same functions.  The kernels own
+// their data movement (what is loaded when, what stays in registers), these own the order of operations. ----
+
+// Ordered block sum: lanes by wave_sum, waves in index order, one final scale, stored by thread 0.
+template <int WAVES>
+__device__ __forceinline__ void block_sum_store(float local, float scale, float* dst) {
+    __shared__ float red[WAVES];
+    const float w = wave_sum(local);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = w;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        float s = 0.f;
+        for (int i = 0; i < WAVES; ++i) s += red[i];
+        dst[0] = s * scale;
+    }
+}
+
+// Pooled means and logit partials of a 256-thread image: add() per channel of a thread, finish() once.  w(k) = W[k][c] from wherever
+// the caller keeps it.
+struct Logits {
+    float part[MAXK];
+    __device__ __forceinline__ Logits() {
+#pragma unroll
+        for (int k = 0; k < MAXK; ++k) part[k] = 0.f;
+    }
+    // t = the channel's sum over the pixels: its mean goes to *pooled_c and into every class's partial
+    template <class WF>
+    __device__ __forceinline__ void add(float t, float inv, float* pooled_c, int K, WF w) {
+        const float m = t * inv;
+        *pooled_c = m;
+#pragma unroll
+        for (int k = 0; k < MAXK; ++k)
+            if (k < K) part[k] = fmaf(m, w(k), part[k]);
+    }
+    // thread k < K: store(bias() + the waves' sums in index order)
+    template <class BF, class SF>
+    __device__ __forceinline__ void finish(int K, BF bias, SF store) {
+        __shared__ float red[BLOCK / AFAN_WAVE][MAXK];
+#pragma unroll
+        for (int k = 0; k < MAXK; ++k) {
+            const float v = wave_sum(part[k]);
+            if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][k] = v;
+        }
+        __syncthreads();
+        if (threadIdx.x < K) {
+            float t = bias();
+            for (int w = 0; w < BLOCK / AFAN_WAVE; ++w) t += red[w][threadIdx.x];
+            store(t);
+        }
+    }
+};
+
+// Vector pooling (bf16 channels-last, C % 8 == 0, 256 % (C / 8) == 0): thread (pg, pc) of G = 256 / (C/8) pixel groups adds the
+// pixels p0, p0 + G, ... < HW of its 8-channel piece (xb points at it) onto s — zeros, or the sums of the sequence's earlier pixels —
+// and leaves the group's sums at grp_row = &grp[pg][pc * 8]; group_sum() adds a channel's groups in index order.
+__device__ __forceinline__ void add8(float (&s)[8], const u16x8& v) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) s[j] += bf2f(v[j]);
+}
+__device__ __forceinline__ void pool_group(float (&s)[8], const uint16_t* xb, int p0, int HW, int G, int C, float* grp_row) {
+    for (int p = p0; p < HW; p += G) add8(s, *reinterpret_cast<const u16x8*>(xb + (int64_t)p * C));
+#pragma unroll
+    for (int j = 0; j < 8; ++j) grp_row[j] = s[j];
+}
+__device__ __forceinline__ float group_sum(const float* grp, int G, int C, int c) {
+    float t = 0.f;
+    for (int g = 0; g < G; ++g) t += grp[g * C + c];
+    return t;
+}
+
+// Cross-entropy of one row of logits (nn.CrossEntropyLoss defaults): lse = max + log sum exp(l - max), loss = lse - l[target],
+// dlogit(k) = (exp(l[k] - lse) - [k == target]) / N.  A target outside [0, K) — torch asserts there — poisons the row with NaN
+// instead of reading out of range.
+struct CeRow {
+    float lse;
+    bool bad;
+    int t;
+    __device__ __forceinline__ CeRow(float m, float s, int64_t t64, int K)
+        : lse(m + logf(s)), bad(t64 < 0 || t64 >= K), t(bad ? 0 : (int)t64) {}
+    // max and sum by one thread walking the row
+    __device__ static __forceinline__ CeRow of(const float* l, int K, int64_t t64) {
+        float m = l[0];
+        for (int k = 1; k < K; ++k) m = fmaxf(m, l[k]);
+        float s = 0.f;
+        for (int k = 0; k < K; ++k) s += expf(l[k] - m);
+        return CeRow(m, s, t64, K);
+    }
+    __device__ __forceinline__ float loss(const float* l) const { return bad ? NAN : lse - l[t]; }
+    __device__ __forceinline__ float dlogit(float lk, int k, float invn) const {
+        return bad ? NAN : (expf(lk - lse) - (k == t ? 1.f : 0.f)) * invn;
+    }
+};
+
+// Head input gradient of one channel, the same at every pixel of the image: (sum_k dl[k] * W[k][c]) / HW, rounded to T.  Two forms of
+// the one chain: weights in memory (wc = &W[0][c]) walk k in a loop, weights in registers need the unrolled one.
+template <typename T>
+__device__ __forceinline__ T head_dx_round(float g, float inv) {
+    g *= inv;
+    T r;
+    Elt<T>::st(&r, g);
+    return r;
+}
+template <typename T>
+__device__ __forceinline__ T head_dx_value(const float* dl, int K, float inv, const float* wc, int C) {
+    float g = 0.f;
+    for (int k = 0; k < K; ++k) g = fmaf(dl[k], wc[(int64_t)k * C], g);
+    return head_dx_round<T>(g, inv);
+}
+template <typename T>
+__device__ __forceinline__ T head_dx_value(const float* dl, int K, float inv, const float (&wr)[MAXK]) {
+    float g = 0.f;
+#pragma unroll
+    for (int k = 0; k < MAXK; ++k)
+        if (k < K) g = fmaf(dl[k], wr[k], g);
+    return head_dx_round<T>(g, inv);
+}
+
 template <typename T>
 __global__ __launch_bounds__(BLOCK) void head_fwd_kernel(const T* __restrict__ x, const float* __restrict__ W,
                                                          const float* __restrict__ bias, float* __restrict__ pooled,
                                                          float* __restrict__ logits, int C, int HW, int K) {
     const int b = blockIdx.x;
     const T* xb = x + (int64_t)b * HW * C;
-    float part[MAXK];
-#pragma unroll
-    for (int k = 0; k < MAXK; ++k) part[k] = 0.f;
+    Logits lg;
     const float inv = 1.0f / (float)HW;
     for (int c = threadIdx.x; c < C; c += BLOCK) {
         float s = 0.f;
         for (int p = 0; p < HW; ++p) s += Elt<T>::ld(xb + (int64_t)p * C + c);
-        const float m = s * inv;
-        pooled[(int64_t)b * C + c] = m;
-#pragma unroll
-        for (int k = 0; k < MAXK; ++k)
-            if (k < K) part[k] = fmaf(m, W[(int64_t)k * C + c], part[k]);
+        lg.add(s, inv, pooled + (int64_t)b * C + c, K, [&](int k) { return W[(int64_t)k * C + c]; });
     }
-    __shared__ float red[BLOCK / AFAN_WAVE][MAXK];
-#pragma unroll
-    for (int k = 0; k < MAXK; ++k) {
-        const float v = wave_sum(part[k]);
-        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][k] = v;
-    }
-    __syncthreads();
-    if (threadIdx.x < K) {
-        float s = bias ? bias[threadIdx.x] : 0.f;
-        for (int w = 0; w < BLOCK / AFAN_WAVE; ++w) s += red[w][threadIdx.x];
-        logits[(int64_t)b * K + threadIdx.x] = s;
-    }
+    lg.finish(K, [&] { return bias ? bias[threadIdx.x] : 0.f; }, [&](float v) { logits[(int64_t)b * K + threadIdx.x] = v; });
 }
 
 // bf16 channels-last with C % 8 == 0 and 256 % (C / 8) == 0 (512 or 64 channels here): 16-byte loads, lanes along
@@ -56,45 +157,18 @@ __global__ __launch_bounds__(BLOCK) void head_fwd_vec_kernel(const uint16_t* __r
                                                              const float* __restrict__ bias, float* __restrict__ pooled,
                                                              float* __restrict__ logits, int C, int HW, int K) {
     __shared__ float grp[BLOCK * 8];                    // [G][C]
-    __shared__ float red[BLOCK / AFAN_WAVE][MAXK];
     const int b = blockIdx.x, P = C >> 3, G = BLOCK / P;
     const int pc = threadIdx.x % P, pg = threadIdx.x / P;
-    const uint16_t* xb = x + (int64_t)b * HW * C + pc * 8;
     float s[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) s[j] = 0.f;
-    for (int p = pg; p < HW; p += G) {
-        const u16x8 v = *reinterpret_cast<const u16x8*>(xb + (int64_t)p * C);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) s[j] += bf2f(v[j]);
-    }
-#pragma unroll
-    for (int j = 0; j < 8; ++j) grp[pg * C + pc * 8 + j] = s[j];
+    pool_group(s, x + (int64_t)b * HW * C + pc * 8, pg, HW, G, C, grp + pg * C + pc * 8);
     __syncthreads();
-    float part[MAXK];
-#pragma unroll
-    for (int k = 0; k < MAXK; ++k) part[k] = 0.f;
+    Logits lg;
     const float inv = 1.0f / (float)HW;
-    for (int c = threadIdx.x; c < C; c += BLOCK) {
-        float t = 0.f;
-        for (int g = 0; g < G; ++g) t += grp[g * C + c];
-        const float m = t * inv;
-        pooled[(int64_t)b * C + c] = m;
-#pragma unroll
-        for (int k = 0; k < MAXK; ++k)
-            if (k < K) part[k] = fmaf(m, W[(int64_t)k * C + c], part[k]);
-    }
-#pragma unroll
-    for (int k = 0; k < MAXK; ++k) {
-        const float v = wave_sum(part[k]);
-        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][k] = v;
-    }
-    __syncthreads();
-    if (threadIdx.x < K) {
-        float t = bias ? bias[threadIdx.x] : 0.f;
-        for (int w = 0; w < BLOCK / AFAN_WAVE; ++w) t += red[w][threadIdx.x];
-        logits[(int64_t)b * K + threadIdx.x] = t;
-    }
+    for (int c = threadIdx.x; c < C; c += BLOCK)
+        lg.add(group_sum(grp, G, C, c), inv, pooled + (int64_t)b * C + c, K, [&](int k) { return W[(int64_t)k * C + c]; });
+    lg.finish(K, [&] { return bias ? bias[threadIdx.x] : 0.f; }, [&](float v) { logits[(int64_t)b * K + threadIdx.x] = v; });
 }
 
 // dx: block per image, thread per channel
@@ -108,10 +182,8 @@ __global__ __launch_bounds__(BLOCK) void head_bwd_dx_kernel(const float* __restr
     const float inv = 1.0f / (float)HW;
     T* xb = dx + (int64_t)b * HW * C;
     for (int c = threadIdx.x; c < C; c += BLOCK) {
-        float g = 0.f;
-        for (int k = 0; k < K; ++k) g = fmaf(dl[k], W[(int64_t)k * C + c], g);
-        g *= inv;
-        for (int p = 0; p < HW; ++p) Elt<T>::st(xb + (int64_t)p * C + c, g);
+        const T g = head_dx_value<T>(dl, K, inv, W + c, C);
+        for (int p = 0; p < HW; ++p) xb[(int64_t)p * C + c] = g;
     }
 }
 
@@ -146,47 +218,30 @@ __global__ __launch_bounds__(64 * DW_SLICES) void head_bwd_dw_kernel(const float
 }
 
 // Mean cross-entropy of the classifier's logits (nn.CrossEntropyLoss defaults: main_perturb.py:71, attack_algo.py:51) and
-// its gradient in ONE launch: per row  lse = max + log sum exp(l - max),  loss_r = lse - l[target],
-// dlogits[r][k] = (exp(l[k] - lse) - [k == target]) / N;  loss = (sum_r loss_r) / N, rows summed in fixed order.
+// its gradient in ONE launch: per row CeRow's loss and dlogits;  loss = (sum_r loss_r) / N, rows summed in fixed order.
 // One block (N * K is a few thousand values here); in torch the same is log_softmax, nll_loss, a ones_like fill, two
 // backward kernels and a zero fill — at the end of every tail pass, K + 2 times per iteration.
 constexpr int CE_BLOCK = 256;
 __global__ __launch_bounds__(CE_BLOCK) void ce_fwd_kernel(const float* __restrict__ logits, const int64_t* __restrict__ target,
                                                           float* __restrict__ loss, float* __restrict__ dlogits, int N, int K) {
-    __shared__ float red[CE_BLOCK / AFAN_WAVE];
     const float invn = 1.0f / (float)N;
     float local = 0.f;
     for (int r = threadIdx.x; r < N; r += CE_BLOCK) {
         const float* l = logits + (int64_t)r * K;
-        float m = l[0];
-        for (int k = 1; k < K; ++k) m = fmaxf(m, l[k]);
-        float s = 0.f;
-        for (int k = 0; k < K; ++k) s += expf(l[k] - m);
-        const float lse = m + logf(s);
-        const int64_t t64 = target[r];
-        const bool bad = t64 < 0 || t64 >= K;       // torch asserts here: poison the loss instead of reading out of range
-        const int t = bad ? 0 : (int)t64;
-        local += bad ? NAN : lse - l[t];
+        const CeRow row = CeRow::of(l, K, target[r]);
+        local += row.loss(l);
         float* d = dlogits + (int64_t)r * K;
-        for (int k = 0; k < K; ++k) d[k] = bad ? NAN : (expf(l[k] - lse) - (k == t ? 1.f : 0.f)) * invn;
+        for (int k = 0; k < K; ++k) d[k] = row.dlogit(l[k], k, invn);
     }
-    const float w = wave_sum(local);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = w;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float s = 0.f;
-        for (int i = 0; i < CE_BLOCK / AFAN_WAVE; ++i) s += red[i];
-        loss[0] = s * invn;
-    }
+    block_sum_store<CE_BLOCK / AFAN_WAVE>(local, invn, loss);
 }
 
 // Many classes (ImageNet-shape heads): one WAVE per row, lanes stride over the classes; the 16 waves of the single
-// workgroup take rows w, w + 16, ...; row losses are summed per wave in row order and the waves in index order
-// (deterministic).  64 x 1000 logits: 313 us with the thread-per-row kernel above, ~10 us here.
+// workgroup take rows w, w + 16, ...; row losses are summed per wave in row order (on lane 0, the other lanes add zeros) and
+// the waves in index order (deterministic).  64 x 1000 logits: 313 us with the thread-per-row kernel above, ~10 us here.
 constexpr int CEW_WAVES = 16;
 __global__ __launch_bounds__(64 * CEW_WAVES) void ce_fwd_wide_kernel(const float* __restrict__ logits, const int64_t* __restrict__ target,
                                                                      float* __restrict__ loss, float* __restrict__ dlogits, int N, int K) {
-    __shared__ float red[CEW_WAVES];
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const float invn = 1.0f / (float)N;
     float local = 0.f;
@@ -198,61 +253,40 @@ __global__ __launch_bounds__(64 * CEW_WAVES) void ce_fwd_wide_kernel(const float
         float s = 0.f;
         for (int k = lane; k < K; k += 64) s += expf(l[k] - m);
         s = wave_sum(s);
-        const float lse = m + logf(s);
-        const int64_t t64 = target[r];
-        const bool bad = t64 < 0 || t64 >= K;
-        const int t = bad ? 0 : (int)t64;
-        if (lane == 0) local += bad ? NAN : lse - l[t];
+        const CeRow row(m, s, target[r], K);
+        if (lane == 0) local += row.loss(l);
         float* d = dlogits + (int64_t)r * K;
-        for (int k = lane; k < K; k += 64) d[k] = bad ? NAN : (expf(l[k] - lse) - (k == t ? 1.f : 0.f)) * invn;
+        for (int k = lane; k < K; k += 64) d[k] = row.dlogit(l[k], k, invn);
     }
-    if (lane == 0) red[w] = local;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float s = 0.f;
-        for (int i = 0; i < CEW_WAVES; ++i) s += red[i];
-        loss[0] = s * invn;
-    }
+    block_sum_store<CEW_WAVES>(local, invn, loss);
 }
 
 // The end of a tail pass in ONE launch, 256 threads per image: everything between the last block's output and its last BatchNorm's
 // backward sums is a function of the image's own out[b] and raw[b] —
-//   pooled, logits          head_fwd_vec_kernel's sums, term for term (pixel groups, then channels);
-//   loss_row, dlogits       ce_fwd_kernel's row expressions (dlogits also times `root`, the pass's root gradient: 1 or 1/2, exact);
-//   v[b][c]                 head_bwd_dx_kernel's value and rounding, once per image and not once per pixel;
-//   the BatchNorm's sums    g = out > 0 ? v : 0:  sum g  and  sum g * (raw - mean), bwd_reduce_kernel's terms, added to the f64
-//                           accumulator block acc[slot][2][C] (slot = image % NS) that bwd_apply_acc_kernel folds; acc = NULL: none
-//                           (the BatchNorm's own reduce launch then takes them from v, in its slab order).
-// The first HCE_IT pixel iterations' out / raw vectors stay in registers between the pooling and the sums (all of them at 512 channels
-// x 16 pixels and at 64 channels x 64 pixels); further ones are read again.  The launch is one dependent chain per image, so every
-// operand (the maps, the weights a thread uses twice, mean, target, bias) is requested before the first wait.
+//   pooled, logits          head_fwd_vec_kernel's: pool_group / group_sum, Logits;
+//   loss_row, dlogits       ce_fwd_kernel's: CeRow (dlogits also times `root`, the pass's root gradient: 1 or 1/2, exact);
+//   v[b][c]                 head_bwd_dx_kernel's: head_dx_value, once per image and not once per pixel;
+//   SUMS (acc given)        the BatchNorm's sums, g = out > 0 ? v : 0:  sum g  and  sum g * (raw - mean), bwd_reduce_kernel's terms,
+//                           added to the f64 accumulator block acc[slot][2][C] (slot = image % NS) that bwd_apply_acc_kernel folds.
+//                           Without SUMS the BatchNorm's own reduce launch takes them from v, in its slab order, and this launch
+//                           neither reads raw / stats nor holds anything for them.
+// The first HCE_IT pixel iterations' out (SUMS: and raw) vectors stay in registers between the pooling and the sums (all of them at
+// 512 channels x 16 pixels and at 64 channels x 64 pixels); further ones are read again.  The launch is one dependent chain per image,
+// so every operand (the maps, the weights a thread uses twice, mean, target, bias) is requested before the first wait.
 constexpr int HCE_IT = 4;
 constexpr int HCE_WIT = 2;      // channel iterations (c = tid + it * 256) whose K weights stay in registers for the logits and for v
-// IMGS images per workgroup (256 threads each): the images' sums are added in LDS, one accumulator add per channel and workgroup.
-// (batch 256, 512 channels x 16 pixels, 10 classes, in the step: 24.0 us before the operands were asked for up front, then 17.9 us with
-// one image per workgroup and 15.9 us with two: half the accumulator adds.  One is kept: an image's sum of g is then exact in fp32 —
-// its pixels' g are one bf16 value or zero — where two images' sums round once more, and 2 us do not show in the step.)
-constexpr int HCE_IMGS = 1;
-template <int IMGS>
-__global__ __launch_bounds__(BLOCK * IMGS) void head_ce_kernel(const uint16_t* __restrict__ out, const uint16_t* __restrict__ raw,
-                                                               const float* __restrict__ stats, const float* __restrict__ W,
-                                                               const float* __restrict__ bias, const int64_t* __restrict__ target,
-                                                               float root, float* __restrict__ pooled, float* __restrict__ logits,
-                                                               float* __restrict__ loss_row, float* __restrict__ dlogits,
-                                                               uint16_t* __restrict__ vrow, double* __restrict__ acc, int N, int C,
-                                                               int HW, int K, int NS) {
-    __shared__ float grp_[IMGS][2 * BLOCK * 8];         // pooling: [G][C]; the sums: [2][G][C]
-    __shared__ float vs_[IMGS][BLOCK * 8];              // v[b][.] as stored (bf16 values)
-    __shared__ float red_[IMGS][BLOCK / AFAN_WAVE][MAXK];
-    __shared__ float lg_[IMGS][MAXK], dl_[IMGS][MAXK];
-    const int img = IMGS == 1 ? 0 : threadIdx.x / BLOCK, tid = IMGS == 1 ? threadIdx.x : threadIdx.x % BLOCK;
-    const bool live = blockIdx.x * IMGS + img < N;      // (a workgroup's spare image repeats the last one and stores nothing)
-    const int b = live ? blockIdx.x * IMGS + img : N - 1;
-    float* grp = grp_[img];
-    float* vs = vs_[img];
-    float (*red)[MAXK] = red_[img];
-    float* lg = lg_[img];
-    float* dl = dl_[img];
+template <bool SUMS>
+__global__ __launch_bounds__(BLOCK) void head_ce_kernel(const uint16_t* __restrict__ out, const uint16_t* __restrict__ raw,
+                                                        const float* __restrict__ stats, const float* __restrict__ W,
+                                                        const float* __restrict__ bias, const int64_t* __restrict__ target,
+                                                        float root, float* __restrict__ pooled, float* __restrict__ logits,
+                                                        float* __restrict__ loss_row, float* __restrict__ dlogits,
+                                                        uint16_t* __restrict__ vrow, double* __restrict__ acc, int N, int C,
+                                                        int HW, int K, int NS) {
+    __shared__ float grp[(SUMS ? 3 : 1) * BLOCK * 8];   // pooling: [G][C]; SUMS: the sums [2][G][C], then v[b][.] as stored
+    __shared__ float lg[MAXK], dl[MAXK];
+    float* vs = grp + (SUMS ? 2 : 0) * BLOCK * 8;       // (SUMS only)
+    const int b = blockIdx.x, tid = threadIdx.x;
     const int P = C >> 3, G = BLOCK / P;
     const int pc = tid % P, pg = tid / P;
     const int64_t base = (int64_t)b * HW * C + pc * 8;
@@ -265,7 +299,7 @@ __global__ __launch_bounds__(BLOCK * IMGS) void head_ce_kernel(const uint16_t* _
         const int p = pg + it * G;
         if (p < HW) {
             xo[it] = *reinterpret_cast<const u16x8*>(xb + (int64_t)p * C);
-            xr[it] = *reinterpret_cast<const u16x8*>(rb + (int64_t)p * C);
+            if (SUMS) xr[it] = *reinterpret_cast<const u16x8*>(rb + (int64_t)p * C);
         }
     }
     float wr[HCE_WIT][MAXK];
@@ -276,8 +310,10 @@ __global__ __launch_bounds__(BLOCK * IMGS) void head_ce_kernel(const uint16_t* _
         for (int k = 0; k < MAXK; ++k) wr[it][k] = (c < C && k < K) ? W[(int64_t)k * C + c] : 0.f;
     }
     float mu[8];
+    if (SUMS) {
 #pragma unroll
-    for (int j = 0; j < 8; ++j) mu[j] = stats[pc * 8 + j];
+        for (int j = 0; j < 8; ++j) mu[j] = stats[pc * 8 + j];
+    }
     const int64_t t64 = target[b];
     const float bias_k = (tid < K && bias) ? bias[tid] : 0.f;
     float s[8];
@@ -285,104 +321,43 @@ __global__ __launch_bounds__(BLOCK * IMGS) void head_ce_kernel(const uint16_t* _
     for (int j = 0; j < 8; ++j) s[j] = 0.f;
 #pragma unroll
     for (int it = 0; it < HCE_IT; ++it)
-        if (pg + it * G < HW) {
-#pragma unroll
-            for (int j = 0; j < 8; ++j) s[j] += bf2f(xo[it][j]);
-        }
-    for (int p = pg + HCE_IT * G; p < HW; p += G) {
-        const u16x8 v = *reinterpret_cast<const u16x8*>(xb + (int64_t)p * C);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) s[j] += bf2f(v[j]);
-    }
-#pragma unroll
-    for (int j = 0; j < 8; ++j) grp[pg * C + pc * 8 + j] = s[j];
+        if (pg + it * G < HW) add8(s, xo[it]);
+    pool_group(s, xb, pg + HCE_IT * G, HW, G, C, grp + pg * C + pc * 8);
     __syncthreads();
-    float part[MAXK];
-#pragma unroll
-    for (int k = 0; k < MAXK; ++k) part[k] = 0.f;
+    Logits part;
     const float inv = 1.0f / (float)HW;
-    auto pool = [&](int c) {
-        float t = 0.f;
-        for (int g = 0; g < G; ++g) t += grp[g * C + c];
-        const float m = t * inv;
-        if (live) pooled[(int64_t)b * C + c] = m;
-        return m;
-    };
 #pragma unroll
     for (int it = 0; it < HCE_WIT; ++it) {
         const int c = tid + it * BLOCK;
-        if (c < C) {
-            const float m = pool(c);
-#pragma unroll
-            for (int k = 0; k < MAXK; ++k)
-                if (k < K) part[k] = fmaf(m, wr[it][k], part[k]);
-        }
+        if (c < C) part.add(group_sum(grp, G, C, c), inv, pooled + (int64_t)b * C + c, K, [&](int k) { return wr[it][k]; });
     }
-    for (int c = tid + HCE_WIT * BLOCK; c < C; c += BLOCK) {
-        const float m = pool(c);
-#pragma unroll
-        for (int k = 0; k < MAXK; ++k)
-            if (k < K) part[k] = fmaf(m, W[(int64_t)k * C + c], part[k]);
-    }
-#pragma unroll
-    for (int k = 0; k < MAXK; ++k)
-        if (k < K) {
-            const float v = wave_sum(part[k]);
-            if ((tid & 63) == 0) red[tid >> 6][k] = v;
-        }
-    __syncthreads();
-    if (tid < K) {
-        float t = bias_k;
-        for (int w = 0; w < BLOCK / AFAN_WAVE; ++w) t += red[w][tid];
-        if (live) logits[(int64_t)b * K + tid] = t;
-        lg[tid] = t;
-    }
+    for (int c = tid + HCE_WIT * BLOCK; c < C; c += BLOCK)
+        part.add(group_sum(grp, G, C, c), inv, pooled + (int64_t)b * C + c, K, [&](int k) { return W[(int64_t)k * C + c]; });
+    part.finish(K, [&] { return bias_k; }, [&](float v) { lg[tid] = logits[(int64_t)b * K + tid] = v; });
     __syncthreads();
     if (tid < AFAN_WAVE) {                              // the row's loss terms, every lane of the image's first wave for itself
-        const float invn = 1.0f / (float)N;
-        float m = lg[0];
-        for (int k = 1; k < K; ++k) m = fmaxf(m, lg[k]);
-        float e = 0.f;
-        for (int k = 0; k < K; ++k) e += expf(lg[k] - m);
-        const float lse = m + logf(e);
-        const bool bad = t64 < 0 || t64 >= K;
-        const int t = bad ? 0 : (int)t64;
-        if (tid == 0 && live) loss_row[b] = bad ? NAN : lse - lg[t];
-        if (tid < K) {
-            const float d = (bad ? NAN : (expf(lg[tid] - lse) - (tid == t ? 1.f : 0.f)) * invn) * root;
-            if (live) dlogits[(int64_t)b * K + tid] = d;
-            dl[tid] = d;
-        }
+        const CeRow row = CeRow::of(lg, K, t64);
+        if (tid == 0) loss_row[b] = row.loss(lg);
+        if (tid < K) dl[tid] = dlogits[(int64_t)b * K + tid] = row.dlogit(lg[tid], tid, 1.0f / (float)N) * root;
     }
     __syncthreads();
-    auto vput = [&](int c, float g) {
-        g *= inv;
-        const uint16_t u = f2bf(g);
-        if (live) vrow[(int64_t)b * C + c] = u;
-        vs[c] = bf2f(u);
+    auto vput = [&](int c, uint16_t u) {
+        vrow[(int64_t)b * C + c] = u;
+        if (SUMS) vs[c] = bf2f(u);
     };
 #pragma unroll
     for (int it = 0; it < HCE_WIT; ++it) {
         const int c = tid + it * BLOCK;
-        if (c < C) {
-            float g = 0.f;
-#pragma unroll
-            for (int k = 0; k < MAXK; ++k)
-                if (k < K) g = fmaf(dl[k], wr[it][k], g);
-            vput(c, g);
-        }
+        if (c < C) vput(c, head_dx_value<uint16_t>(dl, K, inv, wr[it]));
     }
-    for (int c = tid + HCE_WIT * BLOCK; c < C; c += BLOCK) {
-        float g = 0.f;
-        for (int k = 0; k < K; ++k) g = fmaf(dl[k], W[(int64_t)k * C + c], g);
-        vput(c, g);
-    }
-    if (!acc) return;                                   // no sums asked for (whole launch alike)
+    for (int c = tid + HCE_WIT * BLOCK; c < C; c += BLOCK)
+        vput(c, head_dx_value<uint16_t>(dl, K, inv, W + c, C));
+    if (!SUMS) return;
     __syncthreads();
     float vv[8], a0[8], a1[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
-        vv[j] = live ? vs[pc * 8 + j] : 0.f;
+        vv[j] = vs[pc * 8 + j];
         a0[j] = a1[j] = 0.f;
     }
     auto add = [&](const u16x8& o, const u16x8& r) {
@@ -404,31 +379,19 @@ __global__ __launch_bounds__(BLOCK * IMGS) void head_ce_kernel(const uint16_t* _
         grp[BLOCK * 8 + pg * C + pc * 8 + j] = a1[j];
     }
     __syncthreads();
-    double* dst = acc + (int64_t)(blockIdx.x & (NS - 1)) * 2 * C;
-    for (int item = threadIdx.x; item < 2 * C; item += BLOCK * IMGS) {
+    double* dst = acc + (int64_t)(b & (NS - 1)) * 2 * C;
+    for (int item = tid; item < 2 * C; item += BLOCK) {
         const int q = item / C, c = item - q * C;
-        float t = 0.f;
-#pragma unroll
-        for (int i = 0; i < IMGS; ++i)
-            for (int g = 0; g < G; ++g) t += grp_[i][q * BLOCK * 8 + g * C + c];
+        const float t = group_sum(grp + q * BLOCK * 8, G, C, c);
         if (t != 0.f) unsafeAtomicAdd(dst + (int64_t)q * C + c, (double)t);     // (an empty mask adds nothing)
     }
 }
 
 // The mean of head_ce_kernel's row losses where a pass consumes the loss value: ce_fwd_kernel's order (rows per thread, waves, block).
 __global__ __launch_bounds__(CE_BLOCK) void loss_mean_kernel(const float* __restrict__ loss_row, float* __restrict__ loss, int N) {
-    __shared__ float red[CE_BLOCK / AFAN_WAVE];
-    const float invn = 1.0f / (float)N;
     float local = 0.f;
     for (int r = threadIdx.x; r < N; r += CE_BLOCK) local += loss_row[r];
-    const float w = wave_sum(local);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = w;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float s = 0.f;
-        for (int i = 0; i < CE_BLOCK / AFAN_WAVE; ++i) s += red[i];
-        loss[0] = s * invn;
-    }
+    block_sum_store<CE_BLOCK / AFAN_WAVE>(local, 1.0f / (float)N, loss);
 }
 
 }  // namespace
@@ -446,8 +409,8 @@ int afan_head_ce(const void* out, const void* raw, int dtype, int64_t n, int64_t
     if (!out || !raw || !stats || !weight || !target || !pooled || !logits || !loss_row || !dlogits || !v) return AFAN_ENULL;
     if (!aligned(out, 16) || !aligned(raw, 16) || !aligned(v, 16) || !aligned(acc, 8)) return AFAN_EALIGN;
     hipStream_t st = (hipStream_t)stream;
-    AFAN_PROF("head_ce_kernel", 4.0 * n * hw * c, st);
-    head_ce_kernel<HCE_IMGS><<<(unsigned)((n + HCE_IMGS - 1) / HCE_IMGS), BLOCK * HCE_IMGS, 0, st>>>(
+    AFAN_PROF("head_ce_kernel", (acc ? 4.0 : 2.0) * n * hw * c, st);        // out, with the sums also raw
+    (acc ? head_ce_kernel<true> : head_ce_kernel<false>)<<<(unsigned)n, BLOCK, 0, st>>>(
         (const uint16_t*)out, (const uint16_t*)raw, stats, weight, bias, target, root, pooled, logits, loss_row, dlogits, (uint16_t*)v, acc,
         (int)n, (int)c, (int)hw, (int)k, afan_nhwc::acc_slot_count(c));
     AFAN_LAUNCH_CHECK();

@@ -408,6 +408,15 @@ def _accumulates_in_place(p):
     return isinstance(p, torch.nn.Parameter) and p.grad is not None and getattr(p, "_afan_arena_grad", False)
 
 
+def _head_grad_dst(weight, bias, want):
+    """(dw, db, direct) of the head's backward: direct = the kernel adds into weight.grad / bias.grad in place; else fresh tensors."""
+    if not want:
+        return None, None, False
+    if _accumulates_in_place(weight) and (bias is None or _accumulates_in_place(bias)):
+        return weight.grad, (bias.grad if bias is not None else None), True
+    return torch.empty_like(weight), (torch.empty_like(bias) if bias is not None else None), False
+
+
 def _own_conv_ok_shape(w, stride, padding, dilation=(1, 1)):
     if w.dtype != torch.bfloat16 or w.shape[2] != w.shape[3]:
         return False
@@ -1179,17 +1188,7 @@ class _HeadFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         x, weight, pooled = ctx.saved_tensors
-        bias = ctx.bias
-        want_p = ctx.pg and ctx.needs_input_grad[1]
-        dw = db = None
-        direct = False
-        if want_p:
-            direct = _accumulates_in_place(weight) and (bias is None or _accumulates_in_place(bias))
-            if direct:
-                dw, db = weight.grad, (bias.grad if bias is not None else None)
-            else:
-                dw = torch.empty_like(weight)
-                db = torch.empty_like(bias) if bias is not None else None
+        dw, db, direct = _head_grad_dst(weight, ctx.bias, ctx.pg and ctx.needs_input_grad[1])
         dx = ops.head_backward(g.float().contiguous(), weight, pooled, x, ctx.needs_input_grad[0], dw, db, accumulate=direct)
         if direct:
             dw = db = None
@@ -1273,10 +1272,20 @@ def _head_ce_ok(x, lin, target, root):
             and _ce_root_value(root, x.device) is not None)
 
 
+def tail_end_kwargs(model, criterion, target, root, want_value=True):
+    """What a tail pass ending in `criterion(logits, target)`, rooted with `root` (ops.one() / ops.half()), passes to the model's slice
+    forward to take the one-launch end (want_value=False: gradient only, PGD's passes); {}, the separate launches, unless the model takes
+    the arguments, the criterion is the library's fused one and the target a tensor.  The shapes are the forward's to judge."""
+    if getattr(model, "_afan_tail_end", False) and getattr(criterion, "_afan_fused", False) and isinstance(target, torch.Tensor):
+        return {"ce_target": target, "ce_root": root, "ce_value": bool(want_value)}
+    return {}
+
+
 class _HeadCEFn(torch.autograd.Function):
     """The classifier head, the cross-entropy against `target` and the head's input gradient (with _TAIL_END_SUMS also the backward sums
-    of the BatchNorm under the head) as ONE forward launch (ops.head_ce): returns (logits, loss).  loss is the mean cross-entropy where `want_value` (one more one-workgroup launch),
-    else an unwritten scalar that only roots the backward (PGD's passes use the gradient alone).  The backward, given the root
+    of the BatchNorm under the head) as ONE forward launch (ops.head_ce): returns (logits, loss).  loss is the mean cross-entropy where
+    `want_value` (one more one-workgroup launch), else an unwritten scalar that only roots the backward (PGD's passes use the gradient
+    alone).  The backward, given the root
     gradient the node was built for (ops.one() / ops.half(), by pointer as in _CEFn), launches the head's dW only and hands the
     block node one gradient row per image expanded over the pixels, which its BatchNorm backward reads as rows (the sums, where taken,
     riding on it: _GradNote's sums form); any other incoming gradient takes the separate launches (head_backward's map)."""
@@ -1296,20 +1305,10 @@ class _HeadCEFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_logits, g_loss):
         x, weight, pooled, dlogits, v = ctx.saved_tensors
-        bias = ctx.bias
-        want_p = ctx.pg and ctx.needs_input_grad[1]
-        dw = db = None
-        direct = False
-        if want_p:
-            direct = _accumulates_in_place(weight) and (bias is None or _accumulates_in_place(bias))
-            if direct:
-                dw, db = weight.grad, (bias.grad if bias is not None else None)
-            else:
-                dw = torch.empty_like(weight)
-                db = torch.empty_like(bias) if bias is not None else None
+        dw, db, direct = _head_grad_dst(weight, ctx.bias, ctx.pg and ctx.needs_input_grad[1])
         given = g_logits is None and g_loss is not None and g_loss.data_ptr() == ctx.root.data_ptr()
         if given:
-            if want_p:
+            if dw is not None:
                 ops.head_backward(dlogits, weight, pooled, x, False, dw, db, accumulate=direct)
             dx = None
             if ctx.needs_input_grad[0]:

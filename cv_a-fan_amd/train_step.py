@@ -206,14 +206,6 @@ class NullReducer:
         return None
 
 
-def _ce_kwargs(model, crit, target, root):
-    """What a tail pass that ends in `crit(logits, target)`, rooted with `root`, tells the model's slice forward (resnet_s.ResNet.forward's
-    ce_target / ce_root): only a model that takes them, only the library's own fused criterion."""
-    if getattr(model, "_afan_tail_end", False) and getattr(crit, "_afan_fused", False):
-        return {"ce_target": target, "ce_root": root}
-    return {}
-
-
 def _cut_chunks(arena, n_chunks):
     """[start, end, first_param_index) ranges cut at tensor boundaries, roughly equal in size."""
     bounds = arena.offsets + [arena.numel]
@@ -530,7 +522,7 @@ class AfanTrainer(StepTrainer):
         with ops.bn_running_updates(2):                 # main_perturb.py:173 + :196: the head, once for both
             fm_clean = m(inp, end_point=idx, start_point=0)
         xin = fm_clean.detach().requires_grad_(True)
-        ce_kw = _ce_kwargs(m, crit, target, half)       # head, loss and the last BatchNorm's sums as one launch where they can be
+        ce_kw = resnet_s.tail_end_kwargs(m, crit, target, half)     # head, loss and the head's gradient as one launch where they can be
         with ops.record_bn_updates() as clean_bn:
             output_clean = m(xin, end_point=ln, start_point=idx, **ce_kw)
         loss_clean = crit(output_clean, target)
@@ -594,7 +586,7 @@ class AfanTrainer(StepTrainer):
         crit = resnet_s.fused_criterion(self.criterion, m)
         half = ops.half(inp.device)
 
-        ce_kw = _ce_kwargs(m, crit, target, half)
+        ce_kw = resnet_s.tail_end_kwargs(m, crit, target, half)
 
         def run_segments(x0):
             ins, outs, h = [x0], [], x0

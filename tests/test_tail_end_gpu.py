@@ -4,7 +4,8 @@ that row), against the launches they replace: afan_head_forward -> afan_cross_en
 
   * logits, pooled, dlogits, the mean loss and v (expanded over the pixels) are the replaced launches' values BIT FOR BIT, for the
     root gradients 1 and 1/2; loss_row (which the replaced launches never store) is held to float64 within the roundings of
-    m + logf(s) - l[t]: three fp32 operations at magnitude <= max|logit| + log K, i.e. 3 spacings of fp32 there.
+    m + logf(s) - l[t]: three fp32 operations at magnitude <= max|logit| + log K, i.e. 3 spacings of fp32 there.  Both instantiations
+    of the kernel: with the accumulator block (the sums mode) and without it (the default launch, which takes no sums).
   * the two accumulator sums against a float64 sum of the same bf16 inputs, with the bounds tests/test_bn_pinned_gpu.py applies to the
     self-reducing accumulator form (C_DB / C_DW ["f32sum"], units of 2^-24 * sum |term|).
   * the row-reading apply against afan_bn_backward_acc on the materialised map, both given the SAME accumulator contents: bit for bit;
@@ -28,6 +29,11 @@ CL = torch.channels_last
 # (N, HW, C, K, flavour): the issue's grid, whole; "big": logits of magnitude ~80; "dead": a channel whose out is zero everywhere
 CASES = [(n, hw, c, k, "plain") for n, hw, c, k in itertools.product((3, 16), (1, 4, 16), (64, 512), (10, 16))]
 CASES += [(16, 16, 512, 10, "big"), (3, 4, 64, 16, "big"), (16, 16, 512, 10, "dead"), (3, 16, 64, 16, "dead")]
+# "loops": the two loops of head_ce_kernel behind its register-held operands — pixels p >= pg + 4 G (ragged, and at the HW cap of 64)
+# and channels c >= 512 (G = 2 and G = 1) — and the HW cap at 64 channels
+CASES += [(3, 25, 512, 10, "loops"), (3, 64, 512, 10, "loops"), (16, 64, 512, 16, "loops"), (3, 16, 1024, 10, "loops"),
+          (3, 4, 1024, 16, "loops"), (3, 1, 2048, 10, "loops"), (3, 64, 64, 10, "loops")]
+ROW_CASES = [c for c in CASES if c[1] > 1 and c[3] == 10 and c[4] != "loops"]
 
 
 def case_id(c):
@@ -36,7 +42,7 @@ def case_id(c):
 
 def _inputs(case, dev):
     n, hw, c, k, flavour = case
-    h = {1: 1, 4: 2, 16: 4}[hw]
+    h = {1: 1, 4: 2, 16: 4, 25: 5, 64: 8}[hw]
     gen = torch.Generator().manual_seed(1000 * n + 100 * hw + c + k + len(flavour))
     raw = (torch.randn(n, c, h, h, generator=gen) * 1.5 + 0.25)
     out = torch.relu(raw * 0.7 + torch.randn(n, c, h, h, generator=gen))
@@ -69,10 +75,10 @@ def _chain(ops, d, root):
     return logits, pooled, loss, dlogits, dx
 
 
-def _head_ce(pkg, d, root):
+def _head_ce(pkg, d, root, with_acc=True):
     ops = pkg.ops
     c = d["out"].shape[1]
-    acc = torch.zeros(ops.acc_block_doubles(c), dtype=torch.float64, device=d["out"].device)
+    acc = torch.zeros(ops.acc_block_doubles(c), dtype=torch.float64, device=d["out"].device) if with_acc else None
     logits, pooled, loss_row, dlogits, v = ops.head_ce(d["out"], d["raw"], d["stats"], d["weight"], d["bias"], d["target"], root, acc)
     return logits, pooled, loss_row, dlogits, v, acc
 
@@ -81,11 +87,25 @@ def _head_ce(pkg, d, root):
 @pytest.mark.parametrize("root", [1.0, 0.5])
 @pytest.mark.parametrize("case", CASES, ids=case_id)
 def test_head_ce_equals_the_launches_it_replaces(pkg, gpu, case, root):
+    """With the accumulator block: the sums mode's instantiation of the kernel."""
+    _check_head_ce(pkg, gpu, case, root, True)
+
+
+@gpu_mark
+@pytest.mark.parametrize("root", [1.0, 0.5])
+@pytest.mark.parametrize("case", CASES, ids=case_id)
+def test_head_ce_without_the_sums_equals_the_launches_it_replaces(pkg, gpu, case, root):
+    """acc = None, the default launch: the same five bit-equalities and loss_row bound (the parameter over acc given / None is two
+    test functions, so that the cases with acc keep the ids they had)."""
+    _check_head_ce(pkg, gpu, case, root, False)
+
+
+def _check_head_ce(pkg, gpu, case, root, with_acc):
     ops = pkg.ops
     n, hw, c, k, flavour = case
     d = _inputs(case, gpu)
     r_logits, r_pooled, r_loss, r_dlogits, r_dx = _chain(ops, d, root)
-    logits, pooled, loss_row, dlogits, v, acc = _head_ce(pkg, d, root)
+    logits, pooled, loss_row, dlogits, v, acc = _head_ce(pkg, d, root, with_acc)
     loss = ops.loss_mean(loss_row)
     torch.cuda.synchronize()
     if flavour == "big":
@@ -102,6 +122,8 @@ def test_head_ce_equals_the_launches_it_replaces(pkg, gpu, case, root):
     worst = float(((loss_row.double() - row64).abs() / tol).max())
     print(f"TAILEND loss_row {worst:.3f} of the bound {case_id(case)} root {root}")
     assert worst <= 1.0, "loss_row off float64"
+    if acc is None:         # the default launch: no sums taken
+        return
     # the two sums against float64 of the same bf16 inputs
     g = torch.where(d["out"].double() > 0, v.double().view(n, c, 1, 1).expand(n, c, *d["out"].shape[2:]), torch.zeros((), dtype=torch.float64, device=gpu))
     xm = d["raw"].double() - d["stats"][0].double().view(1, c, 1, 1)
@@ -121,7 +143,7 @@ def test_head_ce_equals_the_launches_it_replaces(pkg, gpu, case, root):
 
 @gpu_mark
 @pytest.mark.parametrize("accumulate", [False, True])
-@pytest.mark.parametrize("case", [c for c in CASES if c[1] > 1 and c[3] == 10], ids=case_id)
+@pytest.mark.parametrize("case", ROW_CASES, ids=case_id)
 def test_row_reading_apply_equals_the_map_reading_one(pkg, gpu, case, accumulate):
     ops = pkg.ops
     n, hw, c, k, _ = case
@@ -144,7 +166,7 @@ def test_row_reading_apply_equals_the_map_reading_one(pkg, gpu, case, accumulate
 
 @gpu_mark
 @pytest.mark.parametrize("accumulate", [False, True])
-@pytest.mark.parametrize("case", [c for c in CASES if c[1] > 1 and c[3] == 10], ids=case_id)
+@pytest.mark.parametrize("case", ROW_CASES, ids=case_id)
 def test_row_reading_slab_backward_equals_the_map_reading_one(pkg, gpu, case, accumulate):
     """afan_bn_backward_rows against afan_bn_backward on the written-out map: same launches, same order, every output bit for bit."""
     ops = pkg.ops
