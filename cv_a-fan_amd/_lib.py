@@ -27,6 +27,8 @@ SIGNATURES = {
     "afan_norms_workspace_floats": (_l, [_l, _l]),
     "afan_pgd_step_norms": (_i, [_p, _p, _i, _p, _p, _l, _l, _f, _f, _i, _p, _p, _p, _p]),
     "afan_perturb_norms": (_i, [_p, _p, _l, _l, _p, _p, _p, _p]),
+    "afan_pgd_packed_step": (_i, [_p, _p, _i, _p, _i, _l, _f, _f, _i, _p, _p]),
+    "afan_pgd_packed_last": (_i, [_p, _p, _i, _p, _i, _l, _l, _f, _f, _i, _p, _p, _p, _p, _p, _p, _p]),
     "afan_pgd_step_l2_workspace_floats": (_l, [_l, _l]),
     "afan_pgd_step_l2": (_i, [_p, _p, _i, _p, _p, _l, _l, _f, _f, _i, _p, _p, _p, _p]),
     "afan_axpy_noise": (_i, [_p, _p, _l, _f, _p, _p]),

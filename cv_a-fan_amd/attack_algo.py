@@ -8,6 +8,8 @@ per-sample norms fused in one pass; channel-moment re-normalisation in one pass)
 nn.Module on the GPU that follows the slice protocol `model(t, end_point=, start_point=)`.  The loop
 itself (input gradient, sign step) is pgd.py's; PGD keeps its one-launch start and the bf16 shadow.
 """
+import os
+
 import torch
 
 from . import ops, pgd
@@ -16,6 +18,17 @@ from .resnet_s import _dense, _like_layout, fused_criterion, tail_end_kwargs
 __all__ = ["PGD", "tensor_clamp", "linfball_proj", "l2ball_proj", "mix_feature", "get_sample_points", "last_norms"]
 
 _last = {"l2": None, "linf": None}
+# 1: the L-inf loop on a bf16 map keeps one byte of sign codes per element between its steps and writes the fp32 iterate once, after
+# the last (ops.pgd_packed_step_ / pgd_packed_last: the same bits); 0: the fp32 iterate of ops.pgd_init / pgd_step_ throughout (A/B)
+_PGD_PACKED = os.environ.get("AFAN_PGD_PACKED", "1") != "0"
+
+
+def pgd_packed_ok(x, model, steps, norm="linf", randinit=False):
+    """Whether PGD(x, ...) takes the packed route: a bf16 map on the GPU under a bf16 model, the L-inf attack from x itself, one to
+    ops.PGD_PACKED_MAX_STEPS steps, and the switch on.  The trainers ask before they decide which tensor to hand over."""
+    return bool(_PGD_PACKED and isinstance(x, torch.Tensor) and x.device.type == "cuda" and x.dtype == torch.bfloat16
+                and getattr(model, "compute_dtype", torch.float32) == torch.bfloat16 and norm == "linf" and not randinit
+                and 1 <= steps <= ops.PGD_PACKED_MAX_STEPS)
 
 
 def last_norms():
@@ -63,6 +76,8 @@ def PGD(x, loss_fn, y=None, model=None, steps=3, gamma=None, start_idx=1, layer_
     computed by the caller — the first ascent step uses it instead of running the tail on x (sign() ignores the scale).
     `tail_end=True` (an addition): the caller allows the one-launch end of each tail pass (resnet_s._HeadCEFn) where the model and
     the criterion take it; the default keeps the separate launches, and with them the bits of every schedule that does not ask.
+    A bf16 `x` under a bf16 model, norm="linf", no randinit and 1 <= steps <= 5 take the packed route (pgd_packed_ok, _pgd_packed):
+    the same values from fewer bytes; the result then also carries `_afan_clean32`, the fp32 copy of `x`.
     """
     if x.device.type != "cuda":
         raise ops.AfanLibraryError("PGD: x must live on the MI355X (no CPU path in this build)")
@@ -72,6 +87,9 @@ def PGD(x, loss_fn, y=None, model=None, steps=3, gamma=None, start_idx=1, layer_
     lp = getattr(model, "compute_dtype", torch.float32) == torch.bfloat16
     if grad0 is not None and (randinit or steps < 1):
         raise ValueError("grad0 is the gradient at x: not with randinit, and only when there is a first step")
+    if pgd_packed_ok(x, model, steps, norm, randinit):
+        return _pgd_packed(_dense(x.detach()), loss_fn, y, model, steps, gamma, start_idx, layer_number, eps, clip, with_norms, grad0,
+                           tail_end)
     # x (bf16 from the product's backbone, or fp32) -> fp32 x, its clone x_adv and, where the first tail pass needs it, the
     # bf16 shadow: one launch (with grad0 the first step's kernel writes the shadow; with randinit the noise kernel does)
     x, x_adv, shadow = ops.pgd_init(_dense(x.detach()), want_shadow=lp and grad0 is None and not randinit)
@@ -107,6 +125,37 @@ def PGD(x, loss_fn, y=None, model=None, steps=3, gamma=None, start_idx=1, layer_
     x_adv.requires_grad_(True)
     if lp:
         x_adv._afan_shadow = shadow  # bf16 copy of the final x_adv for the adv tail forward
+    return x_adv
+
+
+def _pgd_packed(x, loss_fn, y, model, steps, gamma, start_idx, layer_number, eps, clip, with_norms, grad0, tail_end):
+    """PGD's L-inf loop on the bf16 map x with no fp32 tensor before the last step: each step leaves its sign decision in one byte of
+    2-bit codes per element and the bf16 shadow the next tail pass reads; the last launch writes the fp32 iterate, the fp32 copy of
+    x (`_afan_clean32`: what the old route's start wrote) and the norms.  No start launch: the first tail pass reads x itself."""
+    if eps is None:
+        if clip:
+            raise ValueError("clip=True needs an eps")
+        eps = 0.0
+    codes = torch.empty_like(x, dtype=torch.uint8) if steps > 1 else None
+    shadow = torch.empty_like(x)
+    loss_fn = fused_criterion(loss_fn, model)
+    ce_kw = tail_end_kwargs(model, loss_fn, y, ops.one(x.device), want_value=False) if tail_end else {}
+    for t in range(steps):
+        if t == 0 and grad0 is not None:
+            grad = grad0
+        else:
+            xin = (x if t == 0 else shadow).detach().requires_grad_(True)
+            grad = pgd.input_gradient(lambda t: loss_fn(model(t, end_point=layer_number, start_point=start_idx, **ce_kw), y), xin)
+        grad = _like_layout(grad.detach(), x)
+        if t < steps - 1:
+            ops.pgd_packed_step_(x, grad, codes, t, gamma, eps, clip, shadow)
+        else:
+            x_adv, x32, l2, linf = ops.pgd_packed_last(x, grad, codes, t, gamma, eps, clip, shadow, want_x32=True, norms=with_norms)
+    if with_norms:
+        _last["l2"], _last["linf"] = l2, linf
+    x_adv.requires_grad_(True)
+    x_adv._afan_shadow = shadow
+    x_adv._afan_clean32 = x32
     return x_adv
 
 

@@ -24,7 +24,7 @@ class _Calls(dict):
     Counters of launches outside the convolution path (`batch_crop_flip`, `seg_batch_aug`, `seg_batch_aug_jitter`, `det_batch_resize`:
     the loaders' kernels; `seg_confusion`:
     validation's scoring kernel; `sat_points`: the layer-wise SAT evaluation's one-launch points; `head_ce`: the one-launch end of a
-    tail pass) live in `.other` and are read and
+    tail pass; `pgd_packed`: launches of the PGD steps that keep sign codes instead of an fp32 iterate) live in `.other` and are read and
     written through the same subscript, `in` and `.get`, so that the enumerated table stays the convolution table
     (tests/test_host_logic.py::test_no_convolution_leaves_the_library pins `set(CALLS)` to the six convolution counters)."""
 
@@ -50,7 +50,7 @@ class _Calls(dict):
 
 CALLS = _Calls({"conv_fwd": 0, "conv_dgrad": 0, "conv_wgrad": 0, "conv_general": 0, "vendor_conv": 0, "conv_bn_fused": 0},
                {"batch_crop_flip": 0, "seg_batch_aug": 0, "seg_batch_aug_jitter": 0, "seg_confusion": 0, "det_batch_resize": 0,
-                "frozen_stem_image_grad": 0, "sat_points": 0, "head_ce": 0})
+                "frozen_stem_image_grad": 0, "sat_points": 0, "head_ce": 0, "pgd_packed": 0})
 
 
 def _need(t, name, dtype=None):
@@ -330,6 +330,55 @@ def pgd_step_norms_(x_adv, grad, gamma, x_clean, eps=0.0, clip=False, shadow=Non
                                   batch, per, float(gamma), float(eps), int(bool(clip)), _ptr(ws),
                                   _ptr(out[0]), _ptr(out[1]), _stream(x_adv)), "afan_pgd_step_norms")
     return out[0], out[1]
+
+
+PGD_PACKED_MAX_STEPS = 5       # four stored 2-bit codes and the last step (afan_pgd_packed_last replays at most four)
+
+
+def _packed_args(x0, grad, codes, t, shadow):
+    _need(x0, "x0", torch.bfloat16)
+    _need(grad, "grad")
+    if grad.dtype not in _DT or grad.numel() != x0.numel():
+        raise TypeError("grad must be fp32/bf16 with x0's number of elements")
+    if codes is not None:
+        _need(codes, "codes", torch.uint8)
+    if shadow is not None:
+        _need(shadow, "shadow", torch.bfloat16)
+    _same_layout(x0, grad, codes, shadow)
+
+
+def pgd_packed_step_(x0, grad, codes, t, gamma, eps=0.0, clip=False, shadow=None):
+    """PGD step t (0..3) of the loop that carries sign codes instead of an fp32 iterate (afan_pgd_packed_step): the iterate is
+    replayed from the bf16 start x0 and the codes of steps 0..t-1, stepped along sign(grad), and leaves as step t's code in `codes`
+    (uint8, in place; t = 0 writes the whole byte) and as its bf16 `shadow` (in place).  Returns shadow."""
+    lib = _lib.load()
+    _packed_args(x0, grad, codes, t, shadow)
+    if codes is None or shadow is None:
+        raise ValueError("pgd_packed_step_ writes codes and shadow: both are required")
+    check(lib.afan_pgd_packed_step(_ptr(x0), _ptr(grad), _DT[grad.dtype], _ptr(codes), int(t), x0.numel(), float(gamma), float(eps),
+                                   int(bool(clip)), _ptr(shadow), _stream(x0)), "afan_pgd_packed_step")
+    CALLS["pgd_packed"] += 1
+    return shadow
+
+
+def pgd_packed_last(x0, grad, codes, t, gamma, eps=0.0, clip=False, shadow=None, want_x32=True, norms=True):
+    """The last step of that loop, `t` (0..4) codes replayed (afan_pgd_packed_last): (x_adv, x32, l2, linf) — the fp32 iterate, the
+    fp32 copy of x0 (None unless want_x32) and the per-sample norms of x_adv - x0 with the bits of pgd_step_norms_ (None unless
+    norms); `shadow` (optional, in place) receives x_adv's bf16 copy.  codes may be None when t == 0."""
+    lib = _lib.load()
+    _packed_args(x0, grad, codes, t, shadow)
+    batch = x0.shape[0] if x0.dim() else 1
+    per = x0.numel() // max(batch, 1)
+    x_adv = torch.empty_like(x0, dtype=torch.float32)
+    x32 = torch.empty_like(x0, dtype=torch.float32) if want_x32 else None
+    out = torch.empty(2, batch, dtype=torch.float32, device=x0.device) if norms else None
+    if x0.numel():
+        ws = _workspace(x0, lib.afan_norms_workspace_floats(batch, per), "norms") if norms else None
+        check(lib.afan_pgd_packed_last(_ptr(x0), _ptr(grad), _DT[grad.dtype], _ptr(codes), int(t), batch, per, float(gamma), float(eps),
+                                       int(bool(clip)), _ptr(x32), _ptr(x_adv), _ptr(shadow), _ptr(ws), _ptr(out[0]) if norms else None,
+                                       _ptr(out[1]) if norms else None, _stream(x0)), "afan_pgd_packed_last")
+        CALLS["pgd_packed"] += 1
+    return x_adv, x32, (out[0] if norms else None), (out[1] if norms else None)
 
 
 def perturb_norms(x_adv, x_clean):

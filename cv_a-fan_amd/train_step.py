@@ -19,8 +19,16 @@ import torch.distributed as dist
 
 from . import ops
 from .arena import ArenaSGD, ParamArena
-from .attack_algo import PGD, last_norms
+from .attack_algo import PGD, last_norms, pgd_packed_ok
 from .grid_guard import GuardedTrainer
+
+
+def _pgd_input(feature_map, model, steps, randinit=False):
+    """What the trainers hand to PGD: the bf16 map itself where PGD takes the packed route (attack_algo.pgd_packed_ok: its last launch
+    writes the fp32 copy the step returns, `_afan_clean32`), else the fp32 map as before."""
+    if pgd_packed_ok(feature_map, model, steps, randinit=randinit):
+        return feature_map
+    return feature_map.float() if feature_map.dtype != torch.float32 else feature_map
 
 
 def warmup_lr(step, optimizer, warm_up_steps=200, max_lr=0.1):
@@ -530,11 +538,12 @@ class AfanTrainer(StepTrainer):
             torch.autograd.backward(loss_clean, grad_tensors=half)
         g0 = xin.grad
         feature_map = fm_clean.detach()
-        feature_map = feature_map.float() if feature_map.dtype != torch.float32 else feature_map
+        feature_map = _pgd_input(feature_map, m, self.steps)
         feature_map_adv = PGD(feature_map, self.criterion, y=target, model=m, steps=self.steps,
                               gamma=(self.gamma / 255), start_idx=idx, layer_number=ln, eps=(self.eps / 255),
                               randinit=False, clip=self.clip, with_norms=True, grad0=g0, tail_end=True)
         l2, linf = last_norms()
+        feature_map = getattr(feature_map_adv, "_afan_clean32", feature_map)     # the packed route's fp32 copy of the map
         adv_in = getattr(feature_map_adv, "_afan_shadow", None)
         if adv_in is None:
             adv_in = feature_map_adv.detach()
@@ -610,11 +619,12 @@ class AfanTrainer(StepTrainer):
                 c_outs[k].backward(c_ins[k + 1].grad)
         g0 = xin.grad
         feature_map = fm_clean.detach()
-        feature_map = feature_map.float() if feature_map.dtype != torch.float32 else feature_map
+        feature_map = _pgd_input(feature_map, m, self.steps)
         feature_map_adv = PGD(feature_map, self.criterion, y=target, model=m, steps=self.steps,
                               gamma=(self.gamma / 255), start_idx=idx, layer_number=ln, eps=(self.eps / 255),
                               randinit=False, clip=self.clip, with_norms=True, grad0=g0, tail_end=True)
         l2, linf = last_norms()
+        feature_map = getattr(feature_map_adv, "_afan_clean32", feature_map)     # the packed route's fp32 copy of the map
         adv_in = getattr(feature_map_adv, "_afan_shadow", None)
         if adv_in is None:
             adv_in = feature_map_adv.detach()
@@ -671,13 +681,14 @@ class AfanTrainer(StepTrainer):
         else:
             with torch.no_grad():  # (.detach()): values and BN side effects are identical
                 feature_map = m(inp, end_point=idx, start_point=0)
-        feature_map = feature_map.float() if feature_map.dtype != torch.float32 else feature_map
+        feature_map = _pgd_input(feature_map, m, self.steps, self.randinit)
         from . import resnet_s as _rsb
         with _rsb.bn_branch(m, "adv"):
             feature_map_adv = PGD(feature_map, self.criterion, y=target, model=m, steps=self.steps,
                                   gamma=(self.gamma / 255), start_idx=idx, layer_number=ln, eps=(self.eps / 255),
                                   randinit=self.randinit, clip=self.clip, with_norms=True)
         l2, linf = last_norms()
+        feature_map = getattr(feature_map_adv, "_afan_clean32", feature_map)     # the packed route's fp32 copy of the map
         # The reference feeds the requires_grad leaf itself and so also computes a never-used d(loss)/d(x_adv)
         # (SURVEY.md §9.7); feeding the detached tensor (its bf16 shadow on the bf16 path) is parity-neutral.
         adv_in = getattr(feature_map_adv, "_afan_shadow", None)

@@ -80,6 +80,36 @@ int afan_pgd_step_norms(float* x_adv, const void* grad, int grad_dtype, const fl
 int afan_perturb_norms(const float* x_adv, const float* x_clean, int64_t batch, int64_t per_sample,
                        float* partial, float* l2_out, float* linf_out, afan_stream_t stream);
 
+/* The L-inf PGD loop on a bf16 start WITHOUT an fp32 iterate between its steps (csrc/afan_pgd_packed.hip).  x0: the start, bf16,
+ * exact in fp32 (xc below is its widened value).  The iterate after step t is
+ *   x_0 = xc;   x_{s+1} = step(x_s, sign_s)   with step = afan_pgd_step's arithmetic, operation by operation:
+ *   d = fl32(gamma * sign_s) (exact);  v = fl32(x_s + d);  clip: lo = fl32(xc - eps), hi = fl32(xc + eps); v < lo -> lo; then v > hi -> hi
+ * a pure function of x0, the signs and the two scalars.  Between steps only one byte of 2-bit codes per element is kept, step s in
+ * bits 2s..2s+1:   0 = zero gradient (sign 0: gamma * 0.f is still added, so an iterate of -0 becomes +0 as in afan_pgd_step),
+ *                  1 = positive,  2 = negative,  3 = NaN gradient (the iterate becomes NaN and stays NaN; its payload is not kept).
+ * A launch replays steps 0..t-1 in registers from x0 and the byte, applies step t from `grad` (fp32 or bf16: only its sign is
+ * used) and gives the fp32 values afan_pgd_init -> afan_pgd_step ... would hold, bit for bit (a NaN's payload excepted).
+ *
+ * afan_pgd_packed_step, t in 0..3: writes the byte (the earlier codes kept, step t's code above them, the higher bits zero; t = 0
+ * reads no byte and writes the whole one: no memset) and the bf16 (RNE) shadow of the new iterate, the next tail pass's input.
+ * HBM bytes per element with a bf16 gradient: 7 at t = 0 (x0 2, grad 2, code 1, shadow 2), then 8 — against afan_pgd_step's 12.
+ * afan_pgd_packed_last, t in 0..4 (the number of codes to replay): writes the fp32 x_adv, optionally x32 (the fp32 copy of x0:
+ * what afan_pgd_init wrote) and the shadow, and — unless l2 == NULL — the per-sample L2 / Linf norms of x_adv - x0 with the bits
+ * of afan_pgd_step_norms: the same (slices, batch) grid of 4096-element slices, the same elements per thread in the same add
+ * order, the same NaN-propagating max, the same finalize launch over `workspace` (afan_norms_workspace_floats(batch, per_sample)
+ * floats; not read when l2 == NULL).  15 B/elt (x0 2, grad 2, code 1, x_adv 4, x32 4, shadow 2) against 16 for
+ * afan_pgd_step_norms plus 14 for the cast and afan_pgd_init it stands for.
+ * Errors: t out of range, a negative size, per_sample == 0 or batch > 65535 AFAN_ESHAPE; n == 0 / batch == 0 returns 0 without a
+ * launch; x0, grad, codes (afan_pgd_packed_last: only when t > 0), shadow (afan_pgd_packed_step) or x_adv NULL, or l2 without
+ * linf and workspace, AFAN_ENULL; an unknown grad_dtype AFAN_EDTYPE.  Misalignment is never an error: tensors aligned to the
+ * lane's access (step: 8 elements, 16 B of x0 / grad / shadow and 8 B of codes; last: 4 elements and per_sample % 4 == 0) take
+ * the wide body, anything else the scalar one.  No allocation, no synchronisation. */
+int afan_pgd_packed_step(const uint16_t* x0, const void* grad, int grad_dtype, uint8_t* codes, int t, int64_t n, float gamma,
+                         float eps, int clip, uint16_t* shadow, afan_stream_t stream);
+int afan_pgd_packed_last(const uint16_t* x0, const void* grad, int grad_dtype, const uint8_t* codes, int t, int64_t batch,
+                         int64_t per_sample, float gamma, float eps, int clip, float* x32, float* x_adv, uint16_t* shadow,
+                         float* workspace, float* l2, float* linf, afan_stream_t stream);
+
 /* L2 PGD step: the gradient normalised per sample, then the projection onto the L2 ball of radius eps around x_clean — the step that
  * goes with the reference's l2ball_proj (Classification/attack_algo.py:21-33 and its twins under Segmentation/ and Detection/,
  * which no reference code calls).  Sample b is the contiguous block of per_sample elements at b * per_sample, whatever the
