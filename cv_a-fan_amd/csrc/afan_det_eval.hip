@@ -38,6 +38,9 @@ __device__ __forceinline__ unsigned ordered(float f) {
     return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 
+// Tensor.clamp(min=0, max=limit) on one coordinate, a NaN handed through (afan_det_targets.hip's clip_coord, the same expression)
+__device__ __forceinline__ float clip_coord(float v, float limit) { return v < 0.f ? 0.f : (v > limit ? limit : v); }
+
 __device__ __forceinline__ float area_incl(const float4 a) { return (a.z - a.x + 1.f) * (a.w - a.y + 1.f); }
 
 // nms.cu:36-49 on one pair
@@ -86,10 +89,10 @@ __global__ __launch_bounds__(TB) void det_class_nms_kernel(const float4* __restr
             const float scx = (s.x + s.z) / 2.f, scy = (s.y + s.w) / 2.f, sw = s.z - s.x, sh = s.w - s.y;
             const float cx = d.x * sw + scx, cy = d.y * sh + scy, w = expf(d.z) * sw, h = expf(d.w) * sh;
             float4 o = make_float4(cx - w / 2.f, cy - h / 2.f, cx + w / 2.f, cy + h / 2.f);
-            o.x = fminf(fmaxf(o.x, 0.f), right);
-            o.z = fminf(fmaxf(o.z, 0.f), right);
-            o.y = fminf(fmaxf(o.y, 0.f), bottom);
-            o.w = fminf(fmaxf(o.w, 0.f), bottom);
+            o.x = clip_coord(o.x, right);
+            o.z = clip_coord(o.z, right);
+            o.y = clip_coord(o.y, bottom);
+            o.w = clip_coord(o.w, bottom);
             box[n] = o;
             area[n] = area_incl(o);
             kept[n] = 0;

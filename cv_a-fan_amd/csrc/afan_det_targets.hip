@@ -18,9 +18,10 @@ namespace {
 
 constexpr int TB = 256;
 
-// float -> unsigned whose order is the floats' (negative values below positive; a positive NaN above everything, as
-// torch.max propagates it)
+// float -> unsigned whose order is the floats' (negative values below positive; a NaN of either sign above everything, as
+// torch.max propagates it: the division hands back NaNs with the sign bit set, whose own pattern would order below every number)
 __device__ __forceinline__ unsigned ordered(float f) {
+    if (f != f) return 0xffffffffu;
     const unsigned u = __float_as_uint(f);
     return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
@@ -42,6 +43,10 @@ __device__ __forceinline__ float iou_cont(const float4 a, const float4 b) {
 __device__ __forceinline__ bool takes_over(float v, float best) { return v > best || (v != v && best == best); }
 
 // ---- decode + clip ----------------------------------------------------------------------------------------------------------
+// bbox.py:89-92 on one coordinate: Tensor.clamp(min=0, max=limit), which hands a NaN through (fminf / fmaxf would return the
+// bound); afan_det_eval.hip's decode holds the same expression
+__device__ __forceinline__ float clip_coord(float v, float limit) { return v < 0.f ? 0.f : (v > limit ? limit : v); }
+
 __global__ __launch_bounds__(TB) void box_decode_clip_kernel(const float4* __restrict__ src, const float4* __restrict__ t,
                                                              float4* __restrict__ out, int64_t n, float right, float bottom) {
     const int64_t i = (int64_t)blockIdx.x * TB + threadIdx.x;
@@ -50,10 +55,10 @@ __global__ __launch_bounds__(TB) void box_decode_clip_kernel(const float4* __res
     const float scx = (s.x + s.z) / 2.f, scy = (s.y + s.w) / 2.f, sw = s.z - s.x, sh = s.w - s.y;
     const float cx = d.x * sw + scx, cy = d.y * sh + scy, w = expf(d.z) * sw, h = expf(d.w) * sh;
     float4 o = make_float4(cx - w / 2.f, cy - h / 2.f, cx + w / 2.f, cy + h / 2.f);
-    o.x = fminf(fmaxf(o.x, 0.f), right);
-    o.z = fminf(fmaxf(o.z, 0.f), right);
-    o.y = fminf(fmaxf(o.y, 0.f), bottom);
-    o.w = fminf(fmaxf(o.w, 0.f), bottom);
+    o.x = clip_coord(o.x, right);
+    o.z = clip_coord(o.z, right);
+    o.y = clip_coord(o.y, bottom);
+    o.w = clip_coord(o.w, bottom);
     out[i] = o;
 }
 

@@ -766,7 +766,9 @@ int afan_nms_top(const float* boxes, const int64_t* order, int64_t n, float thre
  * (left, top, right, bottom), indices int64, all pointers device memory.
  *
  * afan_box_decode_clip — bbox.py:54-64 `apply_transformer` then :89-92 `clip` to [0, right] x [0, bottom]; n boxes.
- * afan_box_assign — IoU (bbox.py:66-82) of boxes [B,N,4] with gt [B,G,4]: assign [B,N] = the best ground truth (first maximum),
+ *   A NaN coordinate stays NaN through the clip, as through Tensor.clamp (afan_det_class_nms's decode likewise).
+ * afan_box_assign — IoU (bbox.py:66-82) of boxes [B,N,4] with gt [B,G,4]: assign [B,N] = the best ground truth (first maximum;
+ *   a NaN IoU takes over from any number, and a ground truth whose column holds one has no tying box, as torch.max gives),
  *   labels [B,N] by mode 0 (anchors, region_proposal_network.py:66-82: -1; 0 below lo; 1 at hi and above, or tying a ground truth's
  *   best positive IoU) or mode 1 (proposals, model.py:256-264: -1; 0 below lo; gt_classes[b, assign] at lo and above).  workspace:
  *   B*G*4 bytes (mode 0).
