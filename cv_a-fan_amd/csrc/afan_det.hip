@@ -29,7 +29,8 @@ constexpr int W64 = 64;
 // t_sane: the threshold is in [1e-3, 1] (wave-uniform).  ~28 instructions per pair against ~50 with the division's branches
 // (the mask kernel is VALU-bound: 72 M pairs for 12 000 boxes).
 __device__ __forceinline__ float box_area_incl(const float* a) { return (a[2] - a[0] + 1.f) * (a[3] - a[1] + 1.f); }
-// v_max / v_min without the canonicalisation fmaxf() adds for operands straight from memory (a NaN box is nobody's input)
+// v_max / v_min without the canonicalisation fmaxf() adds for operands straight from memory; a quiet NaN coordinate yields the
+// other operand as fmaxf() does (pinned with the rest of the pair test by tests/test_nms_pinned_gpu.py; signalling NaNs are not)
 __device__ __forceinline__ float vmax(float a, float b) { float r; asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
 __device__ __forceinline__ float vmin(float a, float b) { float r; asm("v_min_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
 __device__ __forceinline__ bool iou_over(const float* a, float sa, const float* b, float sb, float thresh, int inclusive, bool t_sane) {
