@@ -27,6 +27,7 @@
 #include "afan_conv_c64.h"
 #include "afan_conv_stem.h"
 #include "afan_conv_params.h"
+#include "afan_conv_s2walk.h"
 #include <stdlib.h>
 
 #ifndef AFAN_CONV_DRES_EARLY
@@ -2131,6 +2132,11 @@ int afan_conv_dgrad_sc_nhwc_bf16(const void* dy, const void* dy_sc, const void* 
                                  int64_t wi, int64_t ci, int64_t co, const void* bn_x, const float* bn_stats, int bn_relu,
                                  const void* bn_y, float* bn_partials, double* bn_acc, afan_stream_t stream) {
     if (!dy_sc) return AFAN_ENULL;
+    // the plain form on an even lattice: one workgroup walks its tile's four parity classes (afan_conv_s2walk.hip; the same bits)
+    int rc = AFAN_OK;
+    if (!bn_x && !bn_stats && !bn_y && !bn_partials && !bn_acc &&
+        afan_s2walk::try_launch(dy, dy_sc, wt10, dx, n, hi, wi, ci, co, (hipStream_t)stream, &rc))
+        return rc;
     DgradReq r;
     r.dy_sc = dy_sc;
     r.bn_x = bn_x; r.bn_stats = bn_stats; r.bn_relu = bn_relu; r.bn_y = bn_y; r.bn_partials = bn_partials; r.bn_acc = bn_acc;

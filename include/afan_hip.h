@@ -432,6 +432,11 @@ int afan_conv_dgrad_dual_nhwc_bf16(const void* dy, const void* wt, void* d3, voi
 int afan_conv_dgrad_sc_nhwc_bf16(const void* dy, const void* dy_sc, const void* wt10, void* dx, int64_t n, int64_t hi,
                                  int64_t wi, int64_t ci, int64_t co, const void* bn_x, const float* bn_stats, int bn_relu,
                                  const void* bn_y, float* bn_partials, double* bn_acc, afan_stream_t stream);
+/* on != 0 (the default; AFAN_S2_WALK=0 in the environment: off at load): a call of afan_conv_dgrad_sc_nhwc_bf16 without BatchNorm
+ * operands, with hi and wi even and ci, co multiples of 64, runs as ONE set of workgroups that each walk the four output-parity
+ * classes of their tile (csrc/afan_conv_s2walk.hip) instead of one set per class: the same summation order, the same bits.  Every
+ * other call, and every call while off, takes the four-class launch.  Returns the previous setting. */
+int afan_conv_s2walk(int on);
 /* ---- convolution + train-mode BatchNorm in ONE launch (round 5) --------------------------------------------------------------
  * Replaces, for the chain conv - bn - relu - conv - bn - (+shortcut) - relu of Classification/resnet_s.py:72-77 run K + 2 times per
  * iteration by attack_algo.py:48-56 / main_perturb.py:195-196, the pair (afan_conv_fwd_nhwc_bf16 with stats_acc,
