@@ -23,6 +23,7 @@ SIGNATURES = {
     "afan_version": (_i, []),
     "afan_arch": (C.c_char_p, []),
     "afan_pgd_step": (_i, [_p, _p, _i, _p, _p, _l, _f, _f, _i, _p]),
+    "afan_pgd_step_clamp": (_i, [_p, _p, _i, _p, _p, _l, _f, _f, _i, _f, _f, _p]),
     "afan_tensor_clamp": (_i, [_p, _p, _p, _l, _p]),
     "afan_norms_workspace_floats": (_l, [_l, _l]),
     "afan_pgd_step_norms": (_i, [_p, _p, _i, _p, _p, _l, _l, _f, _f, _i, _p, _p, _p, _p]),

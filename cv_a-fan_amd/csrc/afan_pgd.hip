@@ -1,5 +1,6 @@
 // PGD feature-ascent kernels for gfx950: sign-step (+ L-inf projection) fused with the per-sample
-// perturbation norms and the bf16 shadow copy; host-noise random start; device-drawn random start (Philox4x32-10);
+// perturbation norms and the bf16 shadow copy; the image attacks' last step with the clamp to scalar bounds in the
+// same launch (Detection/attack_algo.py:171-177); host-noise random start; device-drawn random start (Philox4x32-10);
 // the L2 step: per-sample normalised gradient step + projection onto the L2 ball, three launches with deterministic sums.
 // Reference behaviour restated (not translated) from Classification/attack_algo.py:9-19,35-36,41-56
 // and Classification/main_perturb.py:188-192.  All of these are HBM-bound streaming kernels:
@@ -18,17 +19,31 @@ __device__ __forceinline__ float sign_of(float g) {
     return (g != g) ? g : (float)((g > 0.f) - (g < 0.f));
 }
 
+// attack_algo.py:9-19 on one element: two compares in its order (NaN compares false and passes through; -0 stays -0 against +0)
+__device__ __forceinline__ float clamp_one(float t, float lo, float hi) {
+    if (t < lo) t = lo;  // attack_algo.py:14-15
+    if (t > hi) t = hi;  // attack_algo.py:16-17
+    return t;
+}
+
+template <bool CLIP>
+__device__ __forceinline__ float project_one(float t, float xc, float eps) {
+    // attack_algo.py:36 materialises centre-radius / centre+radius first
+    return CLIP ? clamp_one(t, xc - eps, xc + eps) : t;
+}
+
 template <bool CLIP>
 __device__ __forceinline__ float step_one(float xa, float g, float xc, float gamma, float eps) {
     float d = gamma * sign_of(g);  // exact: +-gamma, 0 or NaN
     float t = xa + d;              // the single rounding of attack_algo.py:53
-    if (CLIP) {
-        float lo = xc - eps;  // attack_algo.py:36 materialises centre-radius / centre+radius first
-        float hi = xc + eps;
-        if (t < lo) t = lo;  // attack_algo.py:14-15 (NaN compares false and passes through)
-        if (t > hi) t = hi;  // attack_algo.py:16-17
-    }
-    return t;
+    return project_one<CLIP>(t, xc, eps);
+}
+
+// the last step of an image attack: step_one (STEP; else the iterate as it stands, steps = 0), then the clamp to [lo, hi]
+template <bool STEP, bool CLIP>
+__device__ __forceinline__ float step_clamp_one(float xa, float g, float xc, float gamma, float eps, float lo, float hi) {
+    const float t = STEP ? step_one<CLIP>(xa, g, xc, gamma, eps) : project_one<CLIP>(xa, xc, eps);
+    return clamp_one(t, lo, hi);
 }
 
 template <typename G> struct GradVec4;
@@ -80,6 +95,49 @@ __global__ __launch_bounds__(BLOCK) void pgd_step_kernel(float* __restrict__ x_a
     } else {
         for (int64_t i = tid; i < n; i += nthreads) {
             float t = step_one<CLIP>(x_adv[i], Elt<G>::ld(grad + i), CLIP ? x_clean[i] : 0.f, gamma, eps);
+            x_adv[i] = t;
+            if (SHADOW) shadow[i] = f2bf(t);
+        }
+    }
+}
+
+// ---- the last step with scalar bounds: pgd_step_kernel's body with two more compares (STEP = false: no gradient is read) --------
+template <typename G, bool STEP, bool CLIP, bool SHADOW, bool VEC>
+__global__ __launch_bounds__(BLOCK) void pgd_step_clamp_kernel(float* __restrict__ x_adv,
+                                                               const G* __restrict__ grad,
+                                                               const float* __restrict__ x_clean,
+                                                               uint16_t* __restrict__ shadow, int64_t n,
+                                                               float gamma, float eps, float lo, float hi) {
+    const int64_t tid = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
+    const int64_t nthreads = (int64_t)gridDim.x * BLOCK;
+    if (VEC) {
+        const int64_t nvec = n >> 2;
+        for (int64_t v = tid; v < nvec; v += nthreads) {
+            const int64_t i = v << 2;
+            float xa[4], g[4] = {0.f, 0.f, 0.f, 0.f}, xc[4] = {0.f, 0.f, 0.f, 0.f};
+            Elt<float>::ldv(x_adv + i, xa);
+            if (STEP) GradVec4<G>::ld(grad + i, g);
+            if (CLIP) Elt<float>::ldv(x_clean + i, xc);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) xa[k] = step_clamp_one<STEP, CLIP>(xa[k], g[k], xc[k], gamma, eps, lo, hi);
+            Elt<float>::stv(x_adv + i, xa);
+            if (SHADOW) {
+                u16x4 s;
+#pragma unroll
+                for (int k = 0; k < 4; ++k) s[k] = f2bf(xa[k]);
+                *reinterpret_cast<u16x4*>(shadow + i) = s;
+            }
+        }
+        // ragged tail (n % 4 elements)
+        const int64_t i = (nvec << 2) + tid;
+        if (i < n) {
+            float t = step_clamp_one<STEP, CLIP>(x_adv[i], STEP ? Elt<G>::ld(grad + i) : 0.f, CLIP ? x_clean[i] : 0.f, gamma, eps, lo, hi);
+            x_adv[i] = t;
+            if (SHADOW) shadow[i] = f2bf(t);
+        }
+    } else {
+        for (int64_t i = tid; i < n; i += nthreads) {
+            float t = step_clamp_one<STEP, CLIP>(x_adv[i], STEP ? Elt<G>::ld(grad + i) : 0.f, CLIP ? x_clean[i] : 0.f, gamma, eps, lo, hi);
             x_adv[i] = t;
             if (SHADOW) shadow[i] = f2bf(t);
         }
@@ -634,6 +692,24 @@ int launch_step(float* x_adv, const void* grad, const float* x_clean, uint16_t* 
     return AFAN_OK;
 }
 
+template <typename G, bool STEP, bool CLIP, bool SHADOW>
+int launch_step_clamp(float* x_adv, const void* grad, const float* x_clean, uint16_t* shadow, int64_t n,
+                      float gamma, float eps, float lo, float hi, hipStream_t st) {
+    const bool vec = aligned(x_adv, 16) && (!STEP || aligned(grad, 4 * sizeof(G))) &&
+                     (!CLIP || aligned(x_clean, 16)) && (!SHADOW || aligned(shadow, 8));
+    const int64_t lanes = vec ? (n + 3) / 4 : n;  // launch_step's grid: one lane per 4 (1) elements, capped, grid-stride beyond
+    const int grid = grid_for(lanes, BLOCK);
+    AFAN_PROF("pgd_step_clamp_kernel", n * (8.0 + (STEP ? sizeof(G) : 0) + (CLIP ? 4 : 0) + (SHADOW ? 2 : 0)), st);
+    if (vec)
+        pgd_step_clamp_kernel<G, STEP, CLIP, SHADOW, true><<<grid, BLOCK, 0, st>>>(
+            x_adv, (const G*)grad, x_clean, shadow, n, gamma, eps, lo, hi);
+    else
+        pgd_step_clamp_kernel<G, STEP, CLIP, SHADOW, false><<<grid, BLOCK, 0, st>>>(
+            x_adv, (const G*)grad, x_clean, shadow, n, gamma, eps, lo, hi);
+    AFAN_LAUNCH_CHECK();
+    return AFAN_OK;
+}
+
 template <typename G, bool CLIP, bool SHADOW, bool STEP>
 int launch_step_norms(float* x_adv, const void* grad, const float* x_clean, uint16_t* shadow,
                       int64_t batch, int64_t per_sample, float gamma, float eps, float* partial,
@@ -688,6 +764,31 @@ int afan_pgd_step(float* x_adv, const void* grad, int grad_dtype, const float* x
     }
     if (grad_dtype == AFAN_F32) { AFAN_DISPATCH(float) }
     AFAN_DISPATCH(uint16_t)
+#undef AFAN_DISPATCH
+}
+
+int afan_pgd_step_clamp(float* x_adv, const void* grad, int grad_dtype, const float* x_clean,
+                        uint16_t* shadow_bf16, int64_t n, float gamma, float eps, int clip,
+                        float lo, float hi, afan_stream_t stream) {
+    if (n < 0) return AFAN_ESHAPE;
+    if (n == 0) return AFAN_OK;
+    if (!x_adv || (clip && !x_clean)) return AFAN_ENULL;
+    if (grad && grad_dtype != AFAN_F32 && grad_dtype != AFAN_BF16) return AFAN_EDTYPE;
+    if (!aligned(x_adv, 4) || (grad && !aligned(grad, grad_dtype == AFAN_F32 ? 4 : 2)) ||
+        (clip && !aligned(x_clean, 4)) || (shadow_bf16 && !aligned(shadow_bf16, 2)))
+        return AFAN_EALIGN;
+    hipStream_t st = (hipStream_t)stream;
+#define AFAN_DISPATCH(G, STEP)                                                                                            \
+    if (clip) {                                                                                                           \
+        if (shadow_bf16) return launch_step_clamp<G, STEP, true, true>(x_adv, grad, x_clean, shadow_bf16, n, gamma, eps, lo, hi, st); \
+        return launch_step_clamp<G, STEP, true, false>(x_adv, grad, x_clean, shadow_bf16, n, gamma, eps, lo, hi, st);     \
+    } else {                                                                                                              \
+        if (shadow_bf16) return launch_step_clamp<G, STEP, false, true>(x_adv, grad, x_clean, shadow_bf16, n, gamma, eps, lo, hi, st); \
+        return launch_step_clamp<G, STEP, false, false>(x_adv, grad, x_clean, shadow_bf16, n, gamma, eps, lo, hi, st);    \
+    }
+    if (!grad) { AFAN_DISPATCH(float, false) }
+    if (grad_dtype == AFAN_F32) { AFAN_DISPATCH(float, true) }
+    AFAN_DISPATCH(uint16_t, true)
 #undef AFAN_DISPATCH
 }
 

@@ -9,6 +9,7 @@ behaviour of the reference's `Detection/attack_algo.py`, and the loop body of `D
     get_sample_points / mix_feature / tensor_clamp / linfball_proj                      (shared with attack_algo.py)
     det_train_step(model, optimizer, image_batch, bboxes_batch, labels_batch, loss_settings)   train_aug_sat_muti_advt.py:70-172
     det_train_phases(...)                         the same iteration as a generator with the backward cut at the backbone's output
+    det_final_step / det_base_step / det_adv_step      train_aug_final.py:78-163, train_baseline.py:76-89, train_baseline_advtrain.py:75-93
 
 `model` is anything that follows the reference's protocol (`Detection/model.py:40-185`):
 `model.train().forward({'x', 'adv', 'out_idx', 'flag'}, bboxes, labels)` -> four per-image loss tensors, a feature map
@@ -137,14 +138,36 @@ def rpn_roi_PGD(layer="roi", rpn_roi_output_dict=None, y=None, model=None, steps
     assert False
 
 
-def adv_input(x=None, y=None, model=None, steps=3, eps=None, gamma=None, randinit=False, clip=False, noise_ahead=None):
-    """:153-178: image-space PGD under the sum of the four losses, clamped to [0, 1] at the end."""
+# The image attack's last step and its final clamp in one launch (pgd.step(clamp=(0, 1)): afan_pgd_step_clamp) instead of the step,
+# two fills and afan_tensor_clamp; the same bits.  The module attribute is read at call time.  Decided by the project's rule for every
+# switch — on only where the iteration gains more than the two arms' combined min-max spread (tools/probe/det_adv_time.py,
+# profiles/det_adv_time.jsonl; README "Detection PGD training").  Measured: the launch alone 0.047 ms against 0.100 ms at 8 x 3 x 600 x 904, but
+# on a 30 - 68 ms iteration that gain (0.05 ms) is below every pair's spread (1.2 - 18 ms), so OFF; AFAN_DET_ADV_CLAMP=1 turns it on.
+ADV_FUSED_CLAMP = os.environ.get("AFAN_DET_ADV_CLAMP", "0") == "1"
+
+
+def adv_input(x=None, y=None, model=None, steps=3, eps=None, gamma=None, randinit=False, clip=False, noise_ahead=None, noise="host",
+              start=None, clamp=True):
+    """:153-178: image-space PGD under the sum of the four losses, clamped to [0, 1] at the end.  Additions, each with a default that
+    keeps the reference's behaviour: noise ("host" | "device": where the random start is drawn, pgd.start); start: the iterate to
+    continue from instead of x (+ the random start), as eval_PGD has it; clamp=False: no final clamp, so that a run can be cut into
+    steps.  With ADV_FUSED_CLAMP the last step carries the clamp (steps = 0: one gradient-less launch)."""
+    fresh = randinit and start is None
     # (the random start's draw may have been made ahead of time: NoiseAhead)
-    x, x_adv = pgd.start(x, eps, randinit, noise_ahead.take(x.shape) if (randinit and noise_ahead is not None) else None)
+    u = noise_ahead.take(x.shape) if (fresh and noise == "host" and noise_ahead is not None) else None
+    x, x_adv = pgd.start(x, eps, fresh, u, noise=noise)
+    if start is not None:
+        x_adv.copy_(start)
     loss_of = lambda t: compute_loss(*model.train().forward({"x": t, "adv": None, "out_idx": -1, "flag": "clean"}, y["bb"], y["lb"]))
-    for _ in range(steps):
-        pgd.ascend(x_adv, loss_of, gamma, x, eps, clip)
-    return pgd.clamp01_(x_adv).requires_grad_(True)
+    if not (clamp and ADV_FUSED_CLAMP):
+        for _ in range(steps):
+            pgd.ascend(x_adv, loss_of, gamma, x, eps, clip)
+        return (pgd.clamp01_(x_adv) if clamp else x_adv).requires_grad_(True)
+    for t in range(steps):
+        pgd.ascend(x_adv, loss_of, gamma, x, eps, clip, clamp=(0.0, 1.0) if t == steps - 1 else None)
+    if steps == 0:      # (:174-175 projects inside the loop only: no projection here)
+        pgd.step(x_adv, None, 0.0, None, None, False, clamp=(0.0, 1.0))
+    return x_adv.requires_grad_(True)
 
 
 def eval_PGD(x, y=None, model=None, steps=3, eps=None, gamma=None, idx=1, randinit=False, clip=False, start=None):
@@ -403,5 +426,46 @@ def det_base_phases(model, optimizer, image_batch, bboxes_batch, labels_batch, o
     if not defer_step:
         optimizer.step()
     out.update({"loss": loss.detach(), "losses": torch.stack([t.detach().mean() for t in four])})
+    return
+    yield
+
+
+def det_adv_step(model, optimizer, image_batch, bboxes_batch, labels_batch, **settings):
+    """One iteration of Detection/train_baseline_advtrain.py:75-93 (see det_adv_phases)."""
+    out = {}
+    for _ in det_adv_phases(model, optimizer, image_batch, bboxes_batch, labels_batch, out, **settings):
+        pass
+    return out
+
+
+def det_adv_phases(model, optimizer, image_batch, bboxes_batch, labels_batch, out, *, steps=1, eps=2.0, gamma=0.5, randinit=False, clip=False,
+                   noise="host", noise_ahead=None, defer_step=False):
+    """One iteration of Detection/train_baseline_advtrain.py:75-93 — PGD training, the model a robust mAP is compared against — as a
+    generator (it yields nothing): adv_input on the batch with eps / 255 and gamma / 255 (`steps` attack passes, each a train-mode
+    forward and an input gradient under dgrad_only on frozen BatchNorm: no parameter gradient, no running statistic, nothing left
+    behind), ONE train-mode forward {'x': adv, 'adv': None, 'out_idx': -1, 'flag': 'clean'}, the sum of the four losses' means,
+    zero_grad, backward, the step.  The host generator is read in the reference's order: the random start first (noise="host"), then
+    each pass's sampling draws.  noise="device": the start is drawn inside its own launch from the device's generator (pgd.start), the
+    host generator sees the sampling draws only, and the seed of the draw comes back as out["noise_seed"].  noise_ahead (host noise
+    with randinit): the next iteration's start is drawn behind this iteration's backward (NoiseAhead).
+    out: loss, losses (the four means), adv (the adversarial batch) and, with noise="device" and randinit, noise_seed."""
+    y = {"bb": bboxes_batch, "lb": labels_batch}
+    if hasattr(model, "begin_iteration"):
+        model.begin_iteration()
+    adv = adv_input(x=image_batch, y=y, model=model, steps=steps, eps=(eps / 255), gamma=(gamma / 255), randinit=randinit, clip=clip,
+                    noise_ahead=noise_ahead, noise=noise)
+    seed = getattr(adv, "_afan_noise_seed", None)
+    adv = adv.detach()          # (the reference carries the clamp's graph back to the image: a gradient nobody reads)
+    four = model.train().forward({"x": adv, "adv": None, "out_idx": -1, "flag": "clean"}, bboxes_batch, labels_batch)
+    loss = compute_loss(*four)
+    optimizer.zero_grad()
+    loss.backward()
+    if noise_ahead is not None and randinit and noise == "host":      # every draw of this iteration is behind us
+        noise_ahead.draw(image_batch.shape)
+    if not defer_step:
+        optimizer.step()
+    out.update({"loss": loss.detach(), "losses": torch.stack([t.detach().mean() for t in four]), "adv": adv})
+    if seed is not None:
+        out["noise_seed"] = seed
     return
     yield

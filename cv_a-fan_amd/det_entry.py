@@ -123,7 +123,32 @@ def get_base_argparser():
     return _common_flags(parser)
 
 
+def get_adv_argparser():
+    """train_baseline_advtrain.py:127-160, flag for flag (no --pertub_idx: the attack is on the image)."""
+    parser = argparse.ArgumentParser()
+    # PGD Setting
+    parser.add_argument('--steps', default=1, type=int, help='PGD-steps')
+    parser.add_argument('--gamma', help='index of PGD gamma', default=0.5, type=float)
+    parser.add_argument('--eps', default=2, type=float)
+    parser.add_argument('--randinit', action="store_true", help="whether using apex")
+    parser.add_argument('--clip', action="store_true", help="whether using apex")
+    return _common_flags(parser)
+
+
 ADDITIONS = ("synthetic", "dtype", "layout", "seed")
+ADV_ADDITIONS = ADDITIONS + ("noise",)
+# Where train_baseline_advtrain.py draws --randinit's start when --noise is not given.  Decided by the project's rule for every switch:
+# "device" only where one iteration gains more than the two arms' combined min-max spread (tools/probe/det_adv_time.py (b),
+# profiles/det_adv_time.jsonl; README "Detection PGD training").  Measured at 600 x 904: 10.1 ms against 12.7 ms (host) and 20.0 ms
+# (host, drawn ahead) at batch 1, spreads 2.5 and 4.3 ms; 30.6 ms against 68.0 and 61.7 ms at batch 8, spreads 3.9 and 15.4 ms: device.
+ADV_NOISE_DEFAULT = "device"
+
+
+def get_full_adv_argparser():
+    parser = get_full_argparser(get_adv_argparser())
+    parser.add_argument("--noise", default=ADV_NOISE_DEFAULT, choices=["host", "device"],
+                        help="where --randinit's start is drawn: torch's CPU generator as the reference does, or inside the start's own launch")
+    return parser
 
 
 def get_full_argparser(parser=None):
@@ -500,3 +525,59 @@ def main_base(program, argv=None):
     cfg = config(args)
     return _run(program, args, cfg, base_checkpoints_dir(args), [], trainer=trainer_factory("base"),
                 first_line="Training Baseline ! DATASET:[{}] DIR:[{}]".format(args.dataset, args.data_dir))
+
+
+def adv_exp_name(args):
+    """train_baseline_advtrain.py:167-169"""
+    name = "s" + str(args.steps) + "g" + str(args.gamma) + "e" + str(args.eps)
+    if args.randinit:
+        name += "_rand"
+    if args.clip:
+        name += "_clip"
+    return name
+
+
+def adv_checkpoints_dir(args, create=False):
+    """train_baseline_advtrain.py:175-179.  create: make the directory too, with the reference's `create dir:[...]` line only where it
+    did not exist (main_adv leaves that to _run, behind the refusals)."""
+    path = os.path.join(args.outputs_dir, 'ckpt-{:s}-{:s}-{:s}'.format(adv_exp_name(args), args.dataset, args.backbone))
+    if create and not os.path.exists(path):
+        print("create dir:[{}]".format(path))
+        os.makedirs(path)
+    return path
+
+
+def check_unbuilt_adv(args):
+    check_unbuilt_model(args)
+    if args.steps < 0:
+        raise ValueError(f"--steps {args.steps}: a number of PGD steps, 0 or more")
+
+
+def adv_settings(args):
+    """The keyword settings of det_attack_algo.det_adv_phases from the parsed flags."""
+    return dict(steps=args.steps, eps=args.eps, gamma=args.gamma, randinit=args.randinit, clip=args.clip, noise=args.noise)
+
+
+def adv_banner(args):
+    """train_baseline_advtrain.py:195-199"""
+    return ["-" * 100, "INFO: PID   : [{}]".format(os.getpid()),
+            "EXP: Dataset:[{}] ADV Training Step:[{}] Gamma:[{}] Eps:[{}] Randinit:[{}] Clip:[{}]"
+            .format(args.dataset, args.steps, args.gamma, args.eps, args.randinit, args.clip), "-" * 100]
+
+
+def adv_trainer_factory(settings, noise_ahead=False):
+    return lambda model, cfg: det_trainer.DetTrainer(model, lr=cfg["learning_rate"], momentum=cfg["momentum"], weight_decay=cfg["weight_decay"],
+                                                     phases="adv", adv=settings, noise_ahead=noise_ahead)
+
+
+def main_adv(program, argv=None):
+    """train_baseline_advtrain.py:126-202: PGD training on the image.  --noise host (the reference's draw) with --seed S: every
+    iteration's host generator is seeded from (S, step), so a run resumed with -r draws what the uninterrupted run drew.  --noise
+    device: the start comes from the device's own generator word, which is NOT one of the checkpoint's four keys (they are the
+    reference's), so a resumed run draws other starts than the uninterrupted one.  Host noise is NOT drawn one iteration ahead
+    (DetTrainer(noise_ahead=True) is there for it): on this iteration it gained less than the spread (profiles/det_adv_time.jsonl)."""
+    args = get_full_adv_argparser().parse_args(argv)
+    print_args(args, 100)
+    check_unbuilt_adv(args)
+    cfg = config(args)
+    return _run(program, args, cfg, adv_checkpoints_dir(args), adv_banner(args), trainer=adv_trainer_factory(adv_settings(args)))

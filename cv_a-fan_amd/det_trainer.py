@@ -12,7 +12,7 @@ config/train_config.py; the learning-rate schedule (WarmUpMultiStepLR, :48) step
 import torch
 
 from .arena import ArenaSGD, ParamArena
-from .det_attack_algo import det_base_phases, det_final_phases, det_train_phases, parse_mix_layer
+from .det_attack_algo import det_adv_phases, det_base_phases, det_final_phases, det_train_phases, parse_mix_layer
 from .train_step import StepTrainer
 
 # everything behind the conv4 feature map: layer4 (= detection.hidden), the RPN and the two heads.  The backbone's unused ImageNet
@@ -27,14 +27,17 @@ class DetTrainer(StepTrainer):
     """Of StepTrainer only the exchange set-up: frozen BatchNorm (no grid barrier on this path: flush_guard() is the uniform no-op),
     no graph of its own, and a step of three inputs."""
 
-    PHASES = ("sat", "final", "base")
+    PHASES = ("sat", "final", "base", "adv")
+    ADV_DEFAULTS = dict(steps=1, eps=2.0, gamma=0.5, randinit=False, clip=False, noise="host")
 
     def __init__(self, model, *, lr=0.001, momentum=0.9, weight_decay=0.0005, loss_settings=1, group=None, allreduce_chunks=4,
-                 segmented=None, arena=None, noise_ahead=False, phases="sat", final=None):
+                 segmented=None, arena=None, noise_ahead=False, phases="sat", final=None, adv=None):
         """phases: which iteration step() runs on the same arena, SGD and exchange — "sat" (train_aug_sat_muti_advt.py, the default),
-        "final" (train_aug_final.py:78-163 with the keyword settings of det_attack_algo.det_final_phases in `final`) or "base"
-        (train_baseline.py:76-89).  The two new ones run their backward in one part: with a process group the whole arena is
-        reduced at finish()."""
+        "final" (train_aug_final.py:78-163 with the keyword settings of det_attack_algo.det_final_phases in `final`), "base"
+        (train_baseline.py:76-89) or "adv" (train_baseline_advtrain.py:75-93, PGD training, with the settings of
+        det_attack_algo.det_adv_phases in `adv`: steps, eps, gamma, randinit, clip, noise; noise_ahead=True draws the next iteration's
+        host random start behind this one's backward, as for "sat").  These three run their backward in one part: with a process
+        group the whole arena is reduced at finish()."""
         if phases not in self.PHASES:
             raise ValueError(f"phases: one of {self.PHASES}, not {phases!r}")
         self.phases = phases
@@ -43,6 +46,15 @@ class DetTrainer(StepTrainer):
             if self.final.get("pertub_idx_se") not in (1, 2, 3):
                 raise ValueError(f"final['pertub_idx_se']: a backbone layer 1..3, not {self.final.get('pertub_idx_se')!r}")
             parse_mix_layer(self.final.get("mix_layer"))
+        self.adv = dict(self.ADV_DEFAULTS, **(adv or {}))
+        if phases == "adv":
+            unknown = sorted(set(self.adv) - set(self.ADV_DEFAULTS))
+            if unknown:
+                raise ValueError(f"adv: unknown settings {unknown} (known: {sorted(self.ADV_DEFAULTS)})")
+            if isinstance(self.adv["steps"], bool) or not isinstance(self.adv["steps"], int) or self.adv["steps"] < 0:
+                raise ValueError(f"adv['steps']: a number of PGD steps >= 0, not {self.adv['steps']!r}")
+            if self.adv["noise"] not in ("host", "device"):
+                raise ValueError(f"adv['noise']: 'host' or 'device', not {self.adv['noise']!r}")
         self.loss_settings = int(loss_settings)
         self.arena = arena if arena is not None else ParamArena(model, skip=UNUSED_PARAMS)
         self.optimizer = ArenaSGD(self.arena, lr, momentum, weight_decay)
@@ -67,8 +79,13 @@ class DetTrainer(StepTrainer):
             out = {}
             if self.reducer is not None:
                 self.reducer.begin(explicit=True)
-            gen = (det_final_phases(self.model, self.optimizer, images, bboxes, labels, out, defer_step=True, **self.final)
-                   if self.phases == "final" else det_base_phases(self.model, self.optimizer, images, bboxes, labels, out, defer_step=True))
+            if self.phases == "final":
+                gen = det_final_phases(self.model, self.optimizer, images, bboxes, labels, out, defer_step=True, **self.final)
+            elif self.phases == "adv":
+                gen = det_adv_phases(self.model, self.optimizer, images, bboxes, labels, out, defer_step=True, noise_ahead=self.noise_ahead,
+                                     **self.adv)
+            else:
+                gen = det_base_phases(self.model, self.optimizer, images, bboxes, labels, out, defer_step=True)
             for _ in gen:
                 pass
             if self.reducer is not None:

@@ -24,7 +24,9 @@ class _Calls(dict):
     Counters of launches outside the convolution path (`batch_crop_flip`, `seg_batch_aug`, `seg_batch_aug_jitter`, `det_batch_resize`:
     the loaders' kernels; `seg_confusion`:
     validation's scoring kernel; `sat_points`: the layer-wise SAT evaluation's one-launch points; `head_ce`: the one-launch end of a
-    tail pass; `pgd_packed`: launches of the PGD steps that keep sign codes instead of an fp32 iterate) live in `.other` and are read and
+    tail pass; `pgd_packed`: launches of the PGD steps that keep sign codes instead of an fp32 iterate; `pgd_step_clamp` /
+    `tensor_clamp`: calls of afan_pgd_step_clamp and afan_tensor_clamp, which show whether an image attack ended in the one launch
+    or in the composition) live in `.other` and are read and
     written through the same subscript, `in` and `.get`, so that the enumerated table stays the convolution table
     (tests/test_host_logic.py::test_no_convolution_leaves_the_library pins `set(CALLS)` to the six convolution counters)."""
 
@@ -50,7 +52,7 @@ class _Calls(dict):
 
 CALLS = _Calls({"conv_fwd": 0, "conv_dgrad": 0, "conv_wgrad": 0, "conv_general": 0, "vendor_conv": 0, "conv_bn_fused": 0},
                {"batch_crop_flip": 0, "seg_batch_aug": 0, "seg_batch_aug_jitter": 0, "seg_confusion": 0, "det_batch_resize": 0,
-                "frozen_stem_image_grad": 0, "sat_points": 0, "head_ce": 0, "pgd_packed": 0})
+                "frozen_stem_image_grad": 0, "sat_points": 0, "head_ce": 0, "pgd_packed": 0, "pgd_step_clamp": 0, "tensor_clamp": 0})
 
 
 def _need(t, name, dtype=None):
@@ -298,6 +300,29 @@ def pgd_step_(x_adv, grad, gamma, x_clean=None, eps=0.0, clip=False, shadow=None
     return x_adv
 
 
+def pgd_step_clamp_(x_adv, grad, gamma, x_clean=None, eps=0.0, clip=False, shadow=None, lo=0.0, hi=1.0):
+    """In place, one launch (afan_pgd_step_clamp): pgd_step_ followed by the clamp to the scalar bounds [lo, hi] — the bits of
+    pgd_step_ and then tensor_clamp_ with filled bound tensors.  grad=None: no step, the projection (with clip) and the clamp only."""
+    lib = _lib.load()
+    _need(x_adv, "x_adv", torch.float32)
+    if grad is not None:
+        _need(grad, "grad")
+        if grad.dtype not in _DT or grad.numel() != x_adv.numel():
+            raise TypeError("grad must be fp32/bf16 with x_adv's number of elements")
+    if clip:
+        _need(x_clean, "x_clean", torch.float32)
+        if x_clean.numel() != x_adv.numel():
+            raise ValueError("x_clean must match x_adv")
+    if shadow is not None:
+        _need(shadow, "shadow", torch.bfloat16)
+    _same_layout(x_adv, grad, x_clean if clip else None, shadow)
+    check(lib.afan_pgd_step_clamp(_ptr(x_adv), _ptr(grad), _DT[grad.dtype] if grad is not None else 0, _ptr(x_clean) if clip else None,
+                                  _ptr(shadow), x_adv.numel(), float(gamma), float(eps), int(bool(clip)), float(lo), float(hi),
+                                  _stream(x_adv)), "afan_pgd_step_clamp")
+    CALLS["pgd_step_clamp"] += 1
+    return x_adv
+
+
 def tensor_clamp_(t, lo, hi):
     lib = _lib.load()
     _need(t, "t", torch.float32)
@@ -306,6 +331,7 @@ def tensor_clamp_(t, lo, hi):
     if lo.numel() != t.numel() or hi.numel() != t.numel():
         raise ValueError("min/max must match t")
     check(lib.afan_tensor_clamp(_ptr(t), _ptr(lo), _ptr(hi), t.numel(), _stream(t)), "afan_tensor_clamp")
+    CALLS["tensor_clamp"] += 1
     return t
 
 

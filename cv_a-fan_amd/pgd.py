@@ -5,6 +5,7 @@
     step(x_adv, grad, gamma, x, eps, clip)   x_adv += gamma * sign(grad) [projected onto the eps-ball around x]: one launch
     ascend(x_adv, loss_of, ...)           input_gradient at x_adv, then step
     clamp01_(x_adv)                       the image attacks' final clamp
+    step(..., clamp=(lo, hi))             the last step and that clamp in one launch (det_attack_algo.adv_input behind its switch)
 
 A caller that already has the first step's gradient (`grad0`) skips ascend at t == 0 and calls step with it.
 
@@ -72,16 +73,24 @@ def input_gradient(loss_of, leaves):
     return grads if many else grads[0]
 
 
-def step(x_adv, grad, gamma, x, eps, clip, shadow=None, norms=False, norm="linf"):
+def step(x_adv, grad, gamma, x, eps, clip, shadow=None, norms=False, norm="linf", clamp=None):
     """In place, one launch: x_adv += gamma * sign(grad), then the projection onto [x - eps, x + eps] when clip; `shadow` receives the
     bf16 copy of the result.  norms=True: the launch also returns the per-sample (l2, linf) of x_adv - x.
     norm="l2": x_adv += gamma * grad / ||grad||_2 per sample, then the projection onto the L2 ball of radius eps around x when clip
-    (ops.pgd_step_l2_); norms=True composes ops.perturb_norms after it."""
+    (ops.pgd_step_l2_); norms=True composes ops.perturb_norms after it.
+    clamp=(lo, hi), L-inf only and without norms: the same launch also clamps the result to the scalar bounds — an image attack's last
+    step and its final clamp (ops.pgd_step_clamp_: the bits of step, then clamp01_); grad may then be None (no step: steps = 0)."""
     _check_norm(norm)
+    if clamp is not None and (norm != "linf" or norms):
+        raise ValueError("clamp=(lo, hi) is built for the L-inf step without norms (norm='linf', norms=False)")
     if eps is None:
         if clip:
             raise ValueError("clip=True needs an eps")
         eps = 0.0
+    if clamp is not None:
+        lo, hi = clamp
+        ops.pgd_step_clamp_(x_adv, None if grad is None else _like_layout(grad.detach(), x_adv), gamma, x, eps, clip, shadow, lo, hi)
+        return None
     grad = _like_layout(grad.detach(), x_adv)
     if norm == "l2":
         ops.pgd_step_l2_(x_adv, grad, gamma, x, eps, clip, shadow)
@@ -91,11 +100,11 @@ def step(x_adv, grad, gamma, x, eps, clip, shadow=None, norms=False, norm="linf"
     ops.pgd_step_(x_adv, grad, gamma, x, eps, clip, shadow)
 
 
-def ascend(x_adv, loss_of, gamma, x, eps, clip, shadow=None, norm="linf"):
-    """One ascent step at x_adv; the model reads the bf16 shadow of x_adv where there is one (no separate cast)."""
+def ascend(x_adv, loss_of, gamma, x, eps, clip, shadow=None, norm="linf", clamp=None):
+    """One ascent step at x_adv; the model reads the bf16 shadow of x_adv where there is one (no separate cast).  clamp: step's."""
     _check_norm(norm)
     xin = (x_adv if shadow is None else shadow).detach().requires_grad_(True)
-    step(x_adv, input_gradient(loss_of, xin), gamma, x, eps, clip, shadow, norm=norm)
+    step(x_adv, input_gradient(loss_of, xin), gamma, x, eps, clip, shadow, norm=norm, clamp=clamp)
 
 
 def clamp01_(x_adv):

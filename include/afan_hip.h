@@ -59,7 +59,24 @@ int afan_pgd_step(float* x_adv, const void* grad, int grad_dtype, const float* x
                   uint16_t* shadow_bf16, int64_t n, float gamma, float eps, int clip,
                   afan_stream_t stream);
 
-/* tensor_clamp with arbitrary bound tensors.  Replaces Classification/attack_algo.py:9-19 (in place:
+/* The LAST step of an image-space PGD with the final clamp to scalar bounds in the same launch: Detection/attack_algo.py:171-177
+ * (`x_adv.data.add_(gamma * sign(grad))`, linfball_proj, then `torch.clamp(x_adv, 0, 1.0)`).  Per element, operation by operation:
+ *   v = what afan_pgd_step leaves: fl32(x_adv + fl32(gamma) * sign(grad)), sign(0) = 0, sign(NaN) = NaN; with clip the two compares
+ *       against fl32(x_clean - eps) and fl32(x_clean + eps);
+ *   then afan_tensor_clamp's two compares in its order: v < lo -> lo, then v > hi -> hi (NaN passes through; -0 stays -0 against
+ *       lo = +0) — the bits of afan_pgd_step followed by afan_tensor_clamp with bound tensors filled with lo and hi.
+ * grad == NULL: no step (the reference's steps = 0), only the projection (with clip) and the clamp; grad_dtype is then not read.
+ * shadow_bf16: optional, receives the round-to-nearest-even bf16 of the final value.
+ * Algorithmic HBM bytes: 12 B/elt (fp32 grad), 16 B/elt with clip; +2 with the shadow; 8 (12 with clip) without a gradient.  The
+ * composition it stands for costs 40: the step's 16, two fills of 4 and the clamp's 16.
+ * Errors: n == 0 returns 0 without a launch; n < 0 AFAN_ESHAPE; x_adv NULL, or clip without x_clean, AFAN_ENULL; a grad_dtype other
+ * than AFAN_F32 / AFAN_BF16 with a gradient AFAN_EDTYPE; a pointer not aligned to its element AFAN_EALIGN.  16-byte aligned tensors
+ * (bf16 gradient, shadow: 8) take the 16-byte body, anything else the scalar one.  No allocation, no synchronisation. */
+int afan_pgd_step_clamp(float* x_adv, const void* grad, int grad_dtype, const float* x_clean,
+                        uint16_t* shadow_bf16, int64_t n, float gamma, float eps, int clip,
+                        float lo, float hi, afan_stream_t stream);
+
+/* tensor_clamp with arbitrary bound tensors. Replaces Classification/attack_algo.py:9-19 (in place:
  * t<lo -> lo, then t>hi -> hi; NaN passes through).  linfball_proj (:35-36) is afan_pgd_step with gamma=0. */
 int afan_tensor_clamp(float* t, const float* lo, const float* hi, int64_t n, afan_stream_t stream);
 
